@@ -15,9 +15,13 @@ under a launcher (WORLD_SIZE set) it is a rank.
   --mode handoff | independent | cooperative: that mode only (cooperative: all ranks share ONE block per step, strong scaling:
           Hessian / activation broadcast, sample-sharded all_reduce for the wide subset, llmc_amd/dist/layer_shard.py).
   --dry   GPU-less plumbing check (gloo, CPU stand-ins instead of kernels, tiny shapes): tests/test_bench_spawn.py.
-  --workload awq | fp8: BASELINE configs[2] / configs[4] (tools/bench_extras.py), also reported under "extra" of the default line.
+  --workload awq | fp8: BASELINE configs[2] / configs[4] (tools/bench_extras.py), also reported under "extra" of the --full line.
+  --full  everything beyond the headline, after it: the CPU baseline, the secondary workloads ("extra"), parity_live, and for
+          N > 1 without --mode the other two modes (independent_value / cooperative_value). Off by default: a plain run sets
+          up, warms up, times --steps steps and prints the line.
+  --dump-outputs DIR  after the timed steps, what the last step returned to its caller as DIR/<name>.npy (see dump_outputs).
 
-Prints ONE JSON line on rank 0 (contract in the task statement): metric/value + roofline + cpu_baseline.
+Prints ONE JSON line on rank 0 (contract in the task statement): metric/value/ms_per_step + roofline (+ cpu_baseline with --full).
 """
 import argparse
 import json
@@ -96,9 +100,59 @@ def parse_args(argv=None):
     ap.add_argument('--overlap', type=int, default=3,
                     help='streams for the subsets\' chains, widest first, the last takes the rest (3 beats 2 and 4); 0 = serial')
     ap.add_argument('--dry', action='store_true', help='GPU-less plumbing check (gloo + CPU stand-ins)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the secondary workloads reported under "extra" (N = 1 only)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what the headline does not need: CPU baseline, "extra" workloads, parity_live, '
+                         'the other modes for N > 1 (a plain run does none of it)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the secondary workloads reported under "extra" (N = 1 only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB in all)')
     return ap.parse_args(argv)
+
+
+# ---- --dump-outputs: the last timed step's results, comparable between two builds run with the same arguments -------------
+DUMP_BUDGET = 64 << 20        # bytes, all files together
+DUMP_SAMPLE = 1 << 19         # elements kept of a larger array (halved until the budget holds)
+
+
+def flatten_outputs(prefix, o, out, seen=None):
+    """name -> tensor for every tensor in a nested result (dicts by key, lists by position); a tensor reached twice (the
+    permutation a subset's layers share) is kept under its first name."""
+    import torch
+    seen = set() if seen is None else seen
+    if torch.is_tensor(o):
+        if id(o) not in seen:
+            seen.add(id(o))
+            out[prefix] = o
+    elif isinstance(o, dict):
+        for k, v in o.items():
+            flatten_outputs(f'{prefix}.{k}', v, out, seen)
+    elif isinstance(o, (list, tuple)):
+        for i, v in enumerate(o):
+            flatten_outputs(f'{prefix}.{i}', v, out, seen)
+    return out
+
+
+def dump_outputs(path, arrays):
+    """Write every tensor of `arrays` (name -> tensor) as path/<name>.npy: floating point (16-bit, fp8 and fp32) as float32,
+    fp64 and integers as float64, each exact. An array of more than `cap` elements becomes the 1-D sample at `cap` flat indices
+    drawn without replacement by a fixed seed, ascending: the same elements in every run of the same shape. `cap` starts
+    at DUMP_SAMPLE and is halved until all files together fit DUMP_BUDGET."""
+    import numpy as np
+    import torch
+    arrays = {k: v for k, v in arrays.items() if torch.is_tensor(v)}
+    wide = lambda t: t.dtype == torch.float64 or not t.is_floating_point()
+    cap = DUMP_SAMPLE
+    while sum(min(t.numel(), cap) * (8 if wide(t) else 4) for t in arrays.values()) > DUMP_BUDGET:
+        cap //= 2
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.double() if wide(t) else t.float()        # before the gather: no index kernels for fp8 needed
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + '.npy'), t.cpu().numpy())
 
 
 def maybe_spawn(args):
@@ -353,7 +407,7 @@ def run_extras(args):
     out = {}
     assert os.path.exists(extras)
     for key, (script, flags) in runs.items():
-        cmd = [sys.executable, script, '--gpus', '1', '--no-cpu-baseline', '--no-extras', '--dtype', args.dtype] + flags
+        cmd = [sys.executable, script, '--gpus', '1', '--full', '--no-cpu-baseline', '--no-extras', '--dtype', args.dtype] + flags
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
             line = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -667,11 +721,23 @@ def main():
     bad = [int(t.item()) for t in _infos(last) if int(t.item()) != 0]
     if bad:
         raise SystemExit(f'bench.py: a Hessian was not positive definite (leading minors {bad}): results invalid')
+    if args.dump_outputs and rank == 0:
+        # per subset, in block order: <input>.<layer>.{weight,scales,zeros,loss} (+ <layer>_packed: the vllm codes); perm and
+        # info, shared by the layers of a subset, once under its first layer
+        arrays, seen = {}, set()
+        if coop:
+            flatten_outputs('out', last, arrays)
+        else:
+            for (name, _, layers), outs in zip(groups, last):
+                labels = [l for l, _ in layers] + [l + '_packed' for l, _ in layers] if len(outs) >= len(layers) else []
+                for i, o in enumerate(outs):
+                    flatten_outputs(f'{name}.{labels[i] if i < len(labels) else i}', o, arrays, seen)
+        dump_outputs(args.dump_outputs, arrays)
     # what THIS run's last step computed, against fp64 on the same resident samples: diag(H) is the only part of the chain
     # whose last bits are used before the factorisation (actorder's sort key, the damping mean) and is not the reference's
     # arithmetic bit for bit; everything downstream is bit-exact given H (tests). One narrow and the wide input.
     parity_live = None
-    if not args.dry and not coop and getattr(ops, 'accs', None):
+    if args.full and not args.dry and not coop and getattr(ops, 'accs', None):
         try:
             parity_live = {}
             for name in (groups[1][0], groups[-1][0]):
@@ -698,9 +764,9 @@ def main():
              f'applied to its calibration input) handed owner-to-owner over RCCL send/recv (xGMI ring), overlapped with the next step'
              if handoff else f'layer-sharded x{world}, no data-path traffic'))
 
-    # ---- the other modes, a few steps each, outside the timed region (N > 1 default only)
+    # ---- the other modes, a few steps each, outside the timed region (N > 1 default only, --full)
     secondary = {}
-    if auto:
+    if auto and args.full:
         last = None
         release(ctx)
         k2 = max(2, min(4, args.steps))
@@ -776,14 +842,14 @@ def main():
             out.update(secondary)    # independent_value / cooperative_value (layers/s, a few steps each, outside the timed region) or *_error
         if handoff_error is not None:
             out['handoff_error'] = handoff_error              # the run fell back to the ownership without the hand-off
-        if world == 1 and not args.no_extras and not args.dry and args.model == 'llama3-8b' and args.variant == 'w_only':
+        if args.full and world == 1 and not args.no_extras and not args.dry and args.model == 'llama3-8b' and args.variant == 'w_only':
             last = None
             release(ctx)            # the secondary workloads are child processes on the same GPU
             out['extra'] = run_extras(args)
             pk = out['extra'].get('gptq_vllm_variant_packed', {})
             # SURVEY 8d's full layer definition (... -> INT4 codes packed), first-class beside `value` (a few steps of the same script)
             out['value_packed'], out['ms_per_step_packed'] = pk.get('value'), pk.get('ms_per_step')
-        if world == 1 and not args.no_cpu_baseline and not args.dry:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.dry:
             try:
                 out['cpu_baseline'] = cpu_baseline(args.model, args.n_seq, args.seq_len, cfg)
             except Exception as e:  # the baseline must never take the GPU number down with it

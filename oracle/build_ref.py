@@ -55,14 +55,14 @@ def build(verbose=False):
     return OUT
 
 
-OUT_GPU = os.path.join(HERE, '_ref_gpu')
+OUT_GPU = os.path.join(OUT, 'plain')   # inside oracle/_ref/: the one build product of the reference that travels to the GPU box
 
 
 def build_gpu():
-    """oracle/_ref_gpu/ : a PLAIN copy of the reference's llmc package (no rewrite at all). On the GPU box the unmodified
+    """oracle/_ref/plain/ : a PLAIN copy of the reference's llmc package (no rewrite at all). On the GPU box the unmodified
     reference runs on the MI355X through PyTorch-ROCm (last sentence): the third arm of
     tools/parity_envelope.py and the source of the Triton-kernel goldens (tools/fp8_triton_golden.py). Git-ignored,
-    travels with the gpurun snapshot, never imported by the product."""
+    travels with oracle/_ref/ to the GPU box, never imported by the product."""
     if not os.path.isdir(os.path.join(REF, 'llmc')):
         return None
     stamp = os.path.join(OUT_GPU, '.built')

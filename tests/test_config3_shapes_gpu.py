@@ -213,8 +213,8 @@ def test_quantize_stacked_70b_down_shape_runs_on_the_hip_path(factor_k28672, mon
 
 # ---- AWQ at configs[2] ---------------------------------------------------------------------------------------------------
 
-needs_ref = pytest.mark.skipif(not os.path.isdir(os.path.join(ROOT, 'oracle', '_ref_gpu', 'llmc')),
-                               reason='oracle/_ref_gpu (plain copy of the reference, made by __graft_entry__.build()) is absent')
+needs_ref = pytest.mark.skipif(not os.path.isdir(os.path.join(ROOT, 'oracle', '_ref', 'plain', 'llmc')),
+                               reason='oracle/_ref/plain (plain copy of the reference, made by __graft_entry__.build()) is absent')
 
 
 def awq_arms(tmp_path, rows, K, N, seed):

@@ -1,15 +1,12 @@
 """Every YAML the reference ships under configs/quantization/ for the four registered algorithms (GPTQ, Awq, RTN, SpQR), read as it
 is: the mirrored class either accepts the `quant` section at construction (config plumbing, quantizer construction, special keys —
-no compute) or refuses it with a NotImplementedError that says why. Runs where /root/reference exists (the build container);
-the table it produces is committed as profiles/r04_config_acceptance.txt."""
-import glob
+no compute) or refuses it with a NotImplementedError that says why. The files are read from tests/golden/ref_quant_configs.json
+(recorded from the reference by oracle/make_golden_configs.py); the table it produces is committed as
+profiles/r04_config_acceptance.txt."""
+import json
 import os
 
-import pytest
-import yaml
-
-REF = '/root/reference/configs/quantization'
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason='the reference tree is only present in the build container')
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'ref_quant_configs.json')
 
 ALGOS = ('GPTQ', 'Awq', 'RTN', 'SpQR')
 # configurations of the four algorithms that leave the path: what the refusal must mention
@@ -23,15 +20,14 @@ EXPECTED_REFUSALS = {
 
 
 def shipped():
+    with open(GOLDEN) as f:
+        configs = json.load(f)
     out = []
-    for f in sorted(glob.glob(REF + '/**/*.yml', recursive=True)):
-        try:
-            c = yaml.safe_load(open(f))
-        except Exception:       # noqa: BLE001
-            continue
+    for rel in sorted(configs):
+        c = configs[rel]
         q = (c or {}).get('quant') or {}
         if isinstance(q, dict) and q.get('method') in ALGOS:
-            out.append((os.path.relpath(f, REF), c))
+            out.append((rel, c))
     return out
 
 

@@ -1,6 +1,5 @@
-"""The exporters' JSON against the REFERENCE's own exporters (llmc/utils/export_vllm.py, export_autoawq.py), run on the
-same configs when /root/reference is present (build container); schema-only checks otherwise. CPU."""
-import importlib.util
+"""The exporters' JSON against what the REFERENCE's own exporters (llmc/utils/export_vllm.py, export_autoawq.py) write for the
+same configs, recorded in tests/golden/export_config.json by oracle/make_golden_configs.py. CPU."""
 import json
 import os
 import sys
@@ -8,7 +7,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = '/root/reference'
+GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'export_config.json')
 
 
 class Cfg(dict):
@@ -45,11 +44,15 @@ CASES = {
 }
 
 
-def _load_ref(name):
-    spec = importlib.util.spec_from_file_location('ref_' + name, os.path.join(REF, 'llmc', 'utils', name + '.py'))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
+AUTOAWQ_CASES = (
+    {'bit': 4, 'symmetric': False, 'granularity': 'per_group', 'group_size': 128, 'pack_version': 'gemm_pack'},
+    {'bit': 4, 'symmetric': False, 'granularity': 'per_channel', 'pack_version': 'gemv_pack'},
+)
+
+
+def _reference():
+    with open(GOLDEN) as f:
+        return json.load(f)
 
 
 def _run(fn, tmp, *args):
@@ -71,20 +74,16 @@ def test_vllm_config_matches_reference(case, tmp_path):
         assert ours['quantization_config']['quant_method'] == 'fp8'
     else:
         assert ours['compression_config']['quant_method'] == 'compressed-tensors'
-    if not os.path.isdir(REF):
-        pytest.skip('reference tree not present: schema-only checks done')
-    ref = _run(_load_ref('export_vllm').update_vllm_quant_config, str(tmp_path / 'b'), Model(), config, str(tmp_path / 'b'))
-    assert ours == ref
+    assert ours == _reference()['vllm'][case]
 
 
 def test_autoawq_config_matches_reference(tmp_path):
     sys.path.insert(0, ROOT)
     from llmc_amd.utils import update_autoawq_quant_config
-    for w in ({'bit': 4, 'symmetric': False, 'granularity': 'per_group', 'group_size': 128, 'pack_version': 'gemm_pack'},
-              {'bit': 4, 'symmetric': False, 'granularity': 'per_channel', 'pack_version': 'gemv_pack'}):
+    refs = _reference()['autoawq']
+    assert len(refs) == len(AUTOAWQ_CASES)
+    for w, ref in zip(AUTOAWQ_CASES, refs):
         config = cfg({'quant': {'weight': w}})
         ours = _run(update_autoawq_quant_config, str(tmp_path / 'a'), config, str(tmp_path / 'a'))
         assert ours['quantization_config']['quant_method'] == 'awq' and 'stale' not in ours['quantization_config']
-        if os.path.isdir(REF):
-            ref = _run(_load_ref('export_autoawq').update_autoawq_quant_config, str(tmp_path / 'b'), config, str(tmp_path / 'b'))
-            assert ours == ref
+        assert ours == ref

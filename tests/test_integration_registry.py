@@ -1,6 +1,7 @@
 """INTEGRATION.md §1, executed: bind this repo's classes into the REFERENCE's own registry object
 (llmc/utils/registry_factory.py:9-23) and look them up the way llmc/__main__.py:43,62 does.
-Runs on CPU; needs the reference tree (present in the build container, absent on the GPU box -> skipped)."""
+Runs on CPU; reads the reference's registry module from oracle/_ref (built by __graft_entry__.build() where the reference tree
+exists; skipped without it)."""
 import os
 import subprocess
 import sys
@@ -8,7 +9,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = '/root/reference'
+REF = os.path.join(ROOT, 'oracle', '_ref')
 
 SCRIPT = r'''
 import sys
@@ -52,7 +53,7 @@ print('REGISTRY_OK')
 '''
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference tree not present')
+@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'llmc')), reason='oracle/_ref is built by __graft_entry__.build() where the reference tree exists')
 def test_register_into_reference_registry():
     code = SCRIPT % {'shims': os.path.join(ROOT, 'oracle', '_shims'), 'ref': REF, 'root': ROOT}
     r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=300)

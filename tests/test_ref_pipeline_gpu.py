@@ -2,7 +2,7 @@
 with its `MODEL_REGISTRY` adapters (`models/llama.py:52-91`, `models/opt.py:53-90`), `BaseDataset`, `collect_first_block_input`,
 `ALGO_REGISTRY[method](...)`, `run_block_loop()` (`compression/blockwise_optimization.py:53-61`), `deploy_all_modality` and
 `PerplexityEval` — runs twice in one process on a random-init checkpoint written by `save_pretrained`: once untouched
-(oracle/_ref_gpu = plain copy of the reference, on this GPU through PyTorch-ROCm) and once after the single line
+(oracle/_ref/plain = plain copy of the reference, on this GPU through PyTorch-ROCm) and once after the single line
 `llmc_amd.register_into(ALGO_REGISTRY)` of INTEGRATION.md section 1. Configurations are the reference's CI files
 (`ci_check/gptq_w_only.yml`: W4 asym g128, actorder, true_sequential, quant_out; `ci_check/awq_w4a16_fakequant_eval.yml`: trans v2
 + weight_clip) and BASELINE configs[0] (RTN W8A16 per-channel, OPT-125M widths). Compared: what every Linear ends with after
@@ -20,8 +20,8 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOOL = os.path.join(ROOT, 'tools', 'ref_pipeline.py')
 
-needs_ref = pytest.mark.skipif(not os.path.isdir(os.path.join(ROOT, 'oracle', '_ref_gpu', 'llmc')),
-                               reason='oracle/_ref_gpu (plain copy of the reference, made by __graft_entry__.build()) is absent')
+needs_ref = pytest.mark.skipif(not os.path.isdir(os.path.join(ROOT, 'oracle', '_ref', 'plain', 'llmc')),
+                               reason='oracle/_ref/plain (plain copy of the reference, made by __graft_entry__.build()) is absent')
 
 
 def run_arms(tmp_path, arch, methods):

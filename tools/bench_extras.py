@@ -1,6 +1,7 @@
 """Secondary workloads of bench.py (`--workload awq | fp8`): BASELINE.json configs[2] (AWQ W4A16 g128 scale search + fake-quant
 evaluation on Llama-3-8B shapes) and configs[4] (FP8 e4m3 per-tensor quantization on Mixtral-8x7B block shapes). Same JSON contract
-as bench.py; bench.py runs them as child processes and reports them under "extra"."""
+as bench.py (a plain run times the steps only; --full adds the CPU baseline, AutoClipper's time and the FP8 cast's own roofline);
+bench.py --full runs them as child processes and reports them under "extra"."""
 import json
 import os
 import subprocess
@@ -17,6 +18,20 @@ PEAK_MFMA_16BIT = 2.5e15  # dense bf16/f16 MFMA, /opt/skills/guides/MI355X_MICRO
 def _shared():
     import bench
     return bench.block_groups, bench.synth_acts, bench.synth_weight
+
+
+def _dump(args, arrays):
+    import bench
+    bench.dump_outputs(args.dump_outputs, arrays)
+
+
+def flatten_outputs(labels, outs):
+    """name -> tensor of a step's result list, entry i under labels[i]"""
+    import bench
+    arrays, seen = {}, set()
+    for label, o in zip(labels, outs):
+        bench.flatten_outputs(label, o, arrays, seen)
+    return arrays
 
 
 def cpu_baseline_reference_awq(groups, N):
@@ -94,32 +109,35 @@ def run_awq(args):
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step(True)
+        last = step(True)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        _dump(args, {f'{name}.best_scales': s for (name, _, _), s in zip(groups, last)})     # one [K] per subset, block order
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
     # weight_clip: True in awq_w_only.yml runs AutoClipper after the scale search (auto_clip.py:37-77: every Linear except q / k,
     # n_sample_token = calib seq_len = 512). Not part of configs[2]'s metric (scale search + fake-quant evaluation); timed once,
-    # outside the timed region, and reported beside it.
+    # outside the timed region, and reported beside it (--full).
     clip_ms = None
-    try:
-        step_tok = max(1, N // seq)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for name, K, layers in groups:
-            xs = acts[name][0::step_tok]
-            for (lname, R), w in zip(layers, weights[name]):
-                if lname in ('q_proj', 'k_proj'):
-                    continue
-                awq_ops.clip_search(w, xs, wq, True)
-        e1.record()
-        torch.cuda.synchronize()
-        clip_ms = e0.elapsed_time(e1)
-    except Exception:
-        clip_ms = None
+    if args.full:
+        try:
+            step_tok = max(1, N // seq)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for name, K, layers in groups:
+                xs = acts[name][0::step_tok]
+                for (lname, R), w in zip(layers, weights[name]):
+                    if lname in ('q_proj', 'k_proj'):
+                        continue
+                    awq_ops.clip_search(w, xs, wq, True)
+            e1.record()
+            torch.cuda.synchronize()
+            clip_ms = e0.elapsed_time(e1)
+        except Exception:
+            clip_ms = None
     n_layers = sum(len(ls) for _, _, ls in groups)
     fl_eval = sum(2.0 * N * sum(r for _, r in ls) * K for _, K, ls in groups)        # one evaluation of every subset
     fl = sum(f for _, _, f in gemm_ev)
@@ -135,7 +153,7 @@ def run_awq(args):
             except Exception:
                 pass
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 cpu = cpu_baseline_reference_awq(groups, N)
             except Exception as e:
@@ -219,25 +237,30 @@ def run_fp8(args):
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # per weight its real_quant_weight_dynamic result (codes, scales, ...), then the static scale of every input
+        labels = [name for name, _, _ in layers] + [k + '.act_scale' for k in acts]
+        _dump(args, flatten_outputs(labels, last))
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
-    # the dominant kernel alone: the cast of one 14336 x 4096 weight, HIP events on the current stream
+    # the dominant kernel alone (--full): the cast of one 14336 x 4096 weight, HIP events on the current stream
     w = weights[4]
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    reps = 10
-    wq.real_quant_weight_dynamic(w)
-    e0.record()
-    for _ in range(reps):
-        wq.real_quant_weight_dynamic(w)
-    e1.record()
-    torch.cuda.synchronize()
-    t_w = e0.elapsed_time(e1) * 1e-3 / reps
     wbytes = 5.0 * w.numel()          # 2 B min/max pass + 2 B cast pass + 1 B codes
+    reps, t_w = 10, None
+    if args.full:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        wq.real_quant_weight_dynamic(w)
+        e0.record()
+        for _ in range(reps):
+            wq.real_quant_weight_dynamic(w)
+        e1.record()
+        torch.cuda.synchronize()
+        t_w = e0.elapsed_time(e1) * 1e-3 / reps
     if rank == 0:
         elems = sum(R * K for _, R, K in layers)
         abytes = sum(2.0 * x.numel() for x in acts.values())
@@ -251,11 +274,11 @@ def run_fp8(args):
                                    'x 3) -> absmax, scale, codes; static per-tensor ranges of their 18 inputs (128 x 512 calibration '
                                    'tokens, experts a quarter each), 1 block per step per GPU',
                        'n_seq': n_seq, 'seq_len': seq, 'parallelism': f'block-sharded x{world}' if world > 1 else 'single GPU'},
-            'roofline': {'bound': 'hbm', 'achieved': wbytes / t_w / 1e9, 'peak': PEAK_HBM / 1e9, 'unit': 'GB/s',
-                         'frac': wbytes / t_w / PEAK_HBM, 'traffic': None,
+            'roofline': {'bound': 'hbm', 'achieved': wbytes / t_w / 1e9 if t_w else None, 'peak': PEAK_HBM / 1e9, 'unit': 'GB/s',
+                         'frac': wbytes / t_w / PEAK_HBM if t_w else None, 'traffic': None,
                          'kernel': 'k_minmax_partial + k_fp8_cast on a 14336 x 4096 weight (5 B per element: two 16-bit reads, one code '
                                    'written); the Python call, events on the launch stream',
-                         'launches': reps, 'algorithmic_bytes_per_launch': wbytes, 'avg_launch_ms': t_w * 1e3,
+                         'launches': reps if t_w else 0, 'algorithmic_bytes_per_launch': wbytes, 'avg_launch_ms': t_w * 1e3 if t_w else None,
                          'whole_step_gbps': (5.0 * elems + abytes) * args.steps / dt / 1e9},
             'cpu_baseline': None,
         }), flush=True)

@@ -1,6 +1,6 @@
 """Goldens for the reference's TRITON-only FP8 block-wise ops (llmc/compression/quantization/kernel.py:7-242: act_quant,
 weight_cast_to_fp8, weight_cast_to_bf16, fp8_gemm), produced by running the UNMODIFIED reference kernels on the MI355X
-(Triton on ROCm; oracle/_ref_gpu is a plain copy of the reference made by oracle/build_ref.py). They cannot run in the
+(Triton on ROCm; oracle/_ref/plain is a plain copy of the reference made by oracle/build_ref.py). They cannot run in the
 build container (no GPU), so this script runs on the GPU box:
 
     python tools/fp8_triton_golden.py gpurun_out/fp8_triton.npz
@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def load_kernel_module():
-    p = os.path.join(ROOT, 'oracle', '_ref_gpu', 'llmc', 'compression', 'quantization', 'kernel.py')
+    p = os.path.join(ROOT, 'oracle', '_ref', 'plain', 'llmc', 'compression', 'quantization', 'kernel.py')
     spec = importlib.util.spec_from_file_location('ref_kernel', p)
     m = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(m)

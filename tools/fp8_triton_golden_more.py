@@ -1,5 +1,5 @@
 """More goldens of the reference's Triton fp8_gemm (llmc/compression/quantization/kernel.py:146-242), run UNMODIFIED on the MI355X
-(oracle/_ref_gpu, see tools/fp8_triton_golden.py): more shapes — several 128-column blocks of b_s, up to 16 K blocks, M below
+(oracle/_ref/plain, see tools/fp8_triton_golden.py): more shapes — several 128-column blocks of b_s, up to 16 K blocks, M below
 one tile, ragged M / N — and the fp32 output (it shows the accumulation order without the bf16 rounding on top; the bf16 output is checked to be
 its rounding).
 Inputs are stored as the fp8 codes and fp32 scales the GEMM takes (act_quant / weight_cast_to_fp8 are pinned by

@@ -5,7 +5,8 @@
 # Jobs:
 #   smoke                 __graft_entry__.smoke()
 #   tests[:<pytest args>] python -m pytest tests -m gpu -q <args>  (default: everything; e.g. tests:tests/test_hessian_gpu.py)
-#   bench[:<flags>]       python bench.py <flags>  (default "--steps 20 --warmup 5": the driver's command) -> bench*.json + a summary line
+#   bench[:<flags>]       python bench.py <flags>  (default "--full --steps 20 --warmup 5": the headline and everything the summary
+#                         line prints; "--steps 20 --warmup 5" alone is the plain headline run) -> bench*.json + a summary line
 #   stats[:<flags>]       rocprofv3 --kernel-trace --stats over bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras <flags>
 #                         -> kernel_stats*.txt (tools/kernel_stats_csv.py)
 #   timeline[:<flags>]    the same trace -> step_timeline*.txt (tools/step_timeline.py: per-stream busy time of one step)
@@ -35,7 +36,7 @@ for job in "$@"; do
   case $kind in
     smoke) timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -2 $O/smoke.log ;;
     tests) timeout 1500 python -m pytest ${arg:-tests} -m gpu -q 2>&1 | tail -40 > $O/tests_$n.txt; tail -6 $O/tests_$n.txt ;;
-    bench) timeout 900 python bench.py ${arg:---steps 20 --warmup 5} > $O/bench_$n.json 2> $O/bench_$n.err || tail -5 $O/bench_$n.err; echo "[$arg]"; summ $O/bench_$n.json ;;
+    bench) timeout 900 python bench.py ${arg:---full --steps 20 --warmup 5} > $O/bench_$n.json 2> $O/bench_$n.err || tail -5 $O/bench_$n.err; echo "[$arg]"; summ $O/bench_$n.json ;;
     stats|timeline)
       timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -o ks -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras $arg > $O/ks.log 2>&1
       F=$(ls $O/ks/*/*kernel_trace.csv $O/ks/*kernel_trace.csv 2>/dev/null | head -1)

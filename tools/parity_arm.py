@@ -4,7 +4,7 @@ weights and calibration samples and write what the layer ends up with.
 Arms:
   ref_cpu   llmc's own GPTQ class methods (oracle/_ref = /root/reference after its own ci_check CPU rewrite) on the host
             cores, `--threads` MKL threads
-  ref_rocm  the UNMODIFIED reference (oracle/_ref_gpu = a plain copy of /root/reference/llmc) on the GPU through
+  ref_rocm  the UNMODIFIED reference (oracle/_ref/plain = a plain copy of the reference's llmc) on the GPU through
             PyTorch-ROCm (rocBLAS sgemm, hipSOLVER/MAGMA potrf)
   ours      llmc_amd: HessianAccumulator (per-sample hook calls) -> quantize_stacked
 Each arm runs the reference's call sequence (layer_init, add_batch per sample, layer_transform; gptq.py:97-196,
@@ -142,7 +142,7 @@ def main():
         sys.path.insert(0, os.path.join(ROOT, 'oracle', '_ref'))
     elif a.arm == 'ref_rocm':
         sys.path.insert(0, os.path.join(ROOT, 'oracle', '_shims'))
-        sys.path.insert(0, os.path.join(ROOT, 'oracle', '_ref_gpu'))
+        sys.path.insert(0, os.path.join(ROOT, 'oracle', '_ref', 'plain'))
     import numpy as np
     import torch
     if a.threads:

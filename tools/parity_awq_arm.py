@@ -1,7 +1,7 @@
 """One ARM of the AWQ scale-search parity check at the shapes BASELINE configs[2] is quoted on:
 `Awq.search_scale_subset` (awq.py:179-278; 20-point grid, one batch of N tokens, inspect = the subset's Linear layers)
 
-  ref_rocm  the UNMODIFIED reference class (oracle/_ref_gpu) on this GPU through PyTorch-ROCm
+  ref_rocm  the UNMODIFIED reference class (oracle/_ref/plain) on this GPU through PyTorch-ROCm
   ref_cpu   the reference after its own CI rewrite (oracle/_ref) on the host cores (small shapes only)
   ours      llmc_amd.compression.quantization.awq_pipeline.search_scale_stacked
 
@@ -118,7 +118,7 @@ def main():
         sys.path.insert(0, os.path.join(ROOT, 'oracle', '_ref'))
     elif a.arm == 'ref_rocm':
         sys.path.insert(0, os.path.join(ROOT, 'oracle', '_shims'))
-        sys.path.insert(0, os.path.join(ROOT, 'oracle', '_ref_gpu'))
+        sys.path.insert(0, os.path.join(ROOT, 'oracle', '_ref', 'plain'))
     import numpy as np
     import torch
     gpu = torch.cuda.is_available()

@@ -2,7 +2,7 @@
 models/opt.py:53-90), BaseDataset + wikitext2_gptq preproc, collect_first_block_input, ALGO_REGISTRY[method](...).run_block_loop()
 (compression/blockwise_optimization.py:53-61), PerplexityEval — on a random-init model saved with `save_pretrained`, twice:
 
-  --arm ref    the reference untouched (oracle/_ref on a CPU-only host, oracle/_ref_gpu = plain copy on a GPU box)
+  --arm ref    the reference untouched (oracle/_ref on a CPU-only host, oracle/_ref/plain = plain copy on a GPU box)
   --arm ours   the same process, the same reference code, with ONE extra line before main():
                    llmc_amd.register_into(ALGO_REGISTRY)            
 
@@ -399,9 +399,9 @@ def main():
     import torch
     import torch.distributed as dist
     gpu = torch.cuda.is_available()
-    ref_dir = os.path.join(ROOT, 'oracle', '_ref_gpu' if gpu else '_ref')
+    ref_dir = os.path.join(ROOT, 'oracle', '_ref', 'plain') if gpu else os.path.join(ROOT, 'oracle', '_ref')
     if not os.path.isdir(os.path.join(ref_dir, 'llmc')):
-        raise SystemExit(f'{ref_dir} missing (built by __graft_entry__.build() where /root/reference exists)')
+        raise SystemExit(f'{ref_dir} missing (built by __graft_entry__.build() where the reference tree exists)')
     arms, methods = a.arms.split(','), a.methods.split(',')
     if 'ours' in arms and not gpu:
         raise SystemExit('--arms ours needs an MI355X (llmc_amd has no CPU path)')

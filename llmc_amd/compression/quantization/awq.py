@@ -123,7 +123,7 @@ class Awq(BaseBlockwiseQuantization):
 
     @torch.no_grad()
     def get_act_scale(self, x):
-        return awq_ops.act_mean(x)
+        return self._act_scale_batched(x)
 
     @torch.no_grad()
     def get_scales(self, prev_op, x, w_max, is_gqa, ratio):
@@ -132,7 +132,7 @@ class Awq(BaseBlockwiseQuantization):
             # channel), always in the v2 form
             x = awq_ops.linear_auto(x, prev_op.weight.data, getattr(prev_op, 'bias', None))
             return awq_ops.awq_scales(self._act_scale_batched(x), None, ratio, 'v2')
-        return awq_ops.awq_scales(self.get_act_scale(x), w_max, ratio, self.trans_version)
+        return awq_ops.awq_scales(self._act_scale_batched(x), w_max, ratio, self.trans_version)
 
     # ---- the reference's helper surface (awq.py:110-145), used by the general route ---------------------------
     def inspect_module_forward(self, x, inspect_module, kwargs):

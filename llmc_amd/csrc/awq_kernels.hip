@@ -79,6 +79,75 @@ __global__ __launch_bounds__(AB) void k_wscale_partial(const T* __restrict__ W, 
     }
 }
 
+// Same partial sums for any group width (K % g == 0; per-channel g = K up to whole rows). One workgroup per slab of
+// WS_ROWS rows; the columns are walked in tiles of whole groups: first the tile's group maxima of the slab's rows into LDS
+// (LPR lanes per group, each lane looping over its part of the group, as the quantizer kernels do), then the per-column
+// sums over the slab's rows in row order: the summation order of k_wscale_partial, so both give the same bits.
+static constexpr int WS_ROWS = 16;
+static constexpr int WS_TILE_GROUPS = 256;   // groups per column tile: LDS of WS_ROWS x 256 floats
+
+template <typename T, int VEC>
+__device__ __forceinline__ void load_abs(const T* p, float (&a)[VEC]) {
+    T v[VEC];
+    if constexpr (VEC * sizeof(T) == 16) {
+        uint4 raw = *reinterpret_cast<const uint4*>(p);
+        __builtin_memcpy(v, &raw, 16);
+    } else {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) v[i] = p[i];
+    }
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) a[i] = fabsf(to_f32<T>(v[i]));
+}
+
+template <typename T, int VEC>  // VEC > 1 needs g % VEC == 0 and 16-B aligned rows: a vector never straddles two groups
+__global__ __launch_bounds__(AB) void k_wscale_partial_any(const T* __restrict__ W, int64_t R, int64_t K, int64_t g,
+                                                           int lpr, float* __restrict__ part) {
+    constexpr int DT = dt_of<T>::value;
+    __shared__ float gmax[WS_ROWS * WS_TILE_GROUPS];
+    const int64_t r0 = (int64_t)blockIdx.x * WS_ROWS;
+    const int nr = (int)(R - r0 < WS_ROWS ? R - r0 : WS_ROWS);
+    const int64_t ngr = K / g;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int gpw = 64 / lpr, sub = lane / lpr, sl = lane % lpr;   // groups per wave pass, this lane's group and slot
+    for (int64_t j0 = 0; j0 < ngr; j0 += WS_TILE_GROUPS) {
+        const int nj = (int)(ngr - j0 < WS_TILE_GROUPS ? ngr - j0 : WS_TILE_GROUPS);
+        const int items = nr * nj;                                  // (row, group) pairs of the tile, row-major
+        for (int base = wave * gpw; base < items; base += (AB / 64) * gpw) {
+            const int item = base + sub;
+            const int it = item < items ? item : items - 1;         // idle lanes repeat the last pair: the shuffle needs all
+            const T* p = W + (r0 + it / nj) * K + (j0 + it % nj) * g;
+            float m = 0.0f;
+            for (int64_t c = (int64_t)sl * VEC; c < g; c += (int64_t)lpr * VEC) {
+                float a[VEC];
+                load_abs<T, VEC>(p + c, a);
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) m = fmaxf(m, a[i]);
+            }
+            m = wave_max(m, lpr);
+            if (item < items && sl == 0) gmax[item] = m;
+        }
+        __syncthreads();
+        const int64_t c0t = j0 * g, c1t = (j0 + nj) * g;
+        for (int64_t c = c0t + (int64_t)threadIdx.x * VEC; c < c1t; c += (int64_t)AB * VEC) {
+            const int j = (int)((c - c0t) / g);
+            float acc[VEC];
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) acc[i] = 0.0f;
+            for (int r = 0; r < nr; ++r) {
+                float a[VEC];
+                load_abs<T, VEC>(W + (r0 + r) * K + c, a);
+                const float m = gmax[r * nj + j];
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) acc[i] += rndc<DT>(a[i] / m);
+            }
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) part[(int64_t)blockIdx.x * K + c + i] = acc[i];
+        }
+        __syncthreads();   // the next tile overwrites gmax
+    }
+}
+
 // ---- Awq.get_scales (awq.py:98-108), single workgroup
 template <typename T>
 __global__ __launch_bounds__(1024) void k_awq_scales(const T* __restrict__ xm, const T* __restrict__ wm, int64_t K,
@@ -235,18 +304,25 @@ extern "C" int llmc_awq_weight_mean(const void* W, int dt, int64_t R, int64_t K,
     LLMC_REQUIRE(dtype_ok(dt), "awq_weight_mean: bad dtype");
     LLMC_REQUIRE(W && out_dt && ws && R > 0 && K > 0, "awq_weight_mean: null/empty argument");
     if (g <= 0) g = K;
-    const int V = 16 / dtype_size(dt);
-    const int64_t lpr = g / V;
-    if (!(K % g == 0 && g % V == 0 && lpr >= 1 && lpr <= 64 && (lpr & (lpr - 1)) == 0 && K % ((int64_t)V) == 0 &&
-          ((uintptr_t)W & 15) == 0)) {
-        set_last_error_msg("awq_weight_mean: group size must be 16 B x (power of two <= 64) elements");
-        return LLMC_ENOTSUP;
-    }
+    LLMC_REQUIRE(K % g == 0, "awq_weight_mean: K must be a multiple of the group size");
     hipStream_t st = (hipStream_t)stream;
-    const int rpb = 16;
-    const int64_t nblk = ceil_div64(R, rpb);
-    DISPATCH_DT(dt, hipLaunchKernelGGL((k_wscale_partial<T>), dim3((unsigned)nblk), dim3(AB), 0, st, (const T*)W, R, K,
-                                       (int)g, rpb, (float*)ws));
+    const int V = 16 / dtype_size(dt);
+    const int64_t nblk = ceil_div64(R, WS_ROWS);
+    const bool vec = g % V == 0 && ((uintptr_t)W & 15) == 0;   // K % g == 0: whole rows of 16-B chunks too
+    const int64_t lpr = g / V;
+    if (vec && lpr <= 64 && (lpr & (lpr - 1)) == 0) {
+        // a group is a power of two <= 64 of 16-B chunks: one shuffle over the group's lanes per row, one pass over W
+        DISPATCH_DT(dt, hipLaunchKernelGGL((k_wscale_partial<T>), dim3((unsigned)nblk), dim3(AB), 0, st, (const T*)W, R,
+                                           K, (int)g, WS_ROWS, (float*)ws));
+    } else if (vec) {
+        const int l = pow2_ceil(lpr < 64 ? lpr : 64);
+        DISPATCH_DT(dt, hipLaunchKernelGGL((k_wscale_partial_any<T, 16 / sizeof(T)>), dim3((unsigned)nblk), dim3(AB), 0,
+                                           st, (const T*)W, R, K, g, l, (float*)ws));
+    } else {
+        const int l = pow2_ceil(g < 64 ? g : 64);
+        DISPATCH_DT(dt, hipLaunchKernelGGL((k_wscale_partial_any<T, 1>), dim3((unsigned)nblk), dim3(AB), 0, st,
+                                           (const T*)W, R, K, g, l, (float*)ws));
+    }
     LLMC_LAUNCH_CHECK();
     DISPATCH_DT(dt, hipLaunchKernelGGL((k_colsum_final<T>), dim3((unsigned)ceil_div64(K, AB)), dim3(AB), 0, st,
                                        (const float*)ws, nblk, K, (float)R, (T*)out_dt));

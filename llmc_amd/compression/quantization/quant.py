@@ -511,12 +511,16 @@ def pack_lsb(codes, bits):
     _ffi.require_gpu(codes)
     L = _ffi.lib()
     codes = codes.contiguous()
+    if codes.dtype == torch.uint8:
+        # 8-bit asymmetric codes (real_quant_weight_dynamic's uint8 container): the reference's (code + 2^(b-1)).to(uint8)
+        # wraps mod 256, so the same bytes read as int8 pack to the same words
+        codes = codes.view(torch.int8)
     if codes.dtype == torch.int32:
         kind = _ffi.OUT_I32
     elif codes.dtype == torch.int8:
         kind = _ffi.OUT_I8
     else:
-        raise ValueError(f'pack_lsb: codes must be int32 or int8, got {codes.dtype}')
+        raise ValueError(f'pack_lsb: codes must be int32, int8 or uint8, got {codes.dtype}')
     R, K = codes.shape
     pf = 32 // bits
     packed = torch.empty((R, (K + pf - 1) // pf), dtype=torch.int32, device=codes.device)

@@ -137,6 +137,14 @@ int llmc_histc(const void* x, int dt, int64_t n, int bins, float min, float max,
 int llmc_mse_qparams(const void* W, int dt, int64_t G, int64_t g, int sym, int round_zp, float qmin, float qmax,
                      int nsteps, int grid, float norm, float* scales, float* zeros, float* min_out, float* max_out,
                      llmc_stream_t stream);
+/* The same search on the groups of a strided fp32 panel, in place: W[r, c0 : c0 + width] for r < R, row stride ld
+ * (elements, ld >= c0 + width). Group j covers panel columns [j * group_size, min((j + 1) * group_size, width)): the last
+ * group may be ragged. Each (row, group) gives bit for bit what llmc_mse_qparams gives on a contiguous fp32 copy of that
+ * group. Results: scales / zeros fp32 [R, ng] at [r * ng + g0 + j] (zeros may be NULL when sym; ng >= g0 + groups).
+ * group_size in {16, 32, 64, 128}, others LLMC_ENOTSUP. GPTQ's column loop with calib_algo 'mse' runs it per block. */
+int llmc_mse_qparams_panel(const float* W, int64_t R, int64_t ld, int64_t c0, int64_t width, int64_t group_size, int sym,
+                           int round_zp, float qmin, float qmax, int nsteps, int grid, float norm, float* scales,
+                           float* zeros, int64_t ng, int64_t g0, llmc_stream_t stream);
 
 /* IntegerQuantizer.quant / quant_dequant with given qparams (quant.py:699-717), i.e. the arithmetic of
  * fake_quant_weight_static (quant.py:785-831) and real_quant_weight_static (quant.py:871-914).
@@ -321,6 +329,18 @@ int llmc_gptq_quantize_cols(float* W, const float* Hinv, int64_t R, int64_t K, i
                        float qmax, int64_t group_size, int static_groups, const int32_t* col_group,
                        float* scales, float* zeros, float* Wout, float* losses, int blocksize,
                        void* ws, llmc_stream_t stream);
+/* The same loop (n_quant as in llmc_gptq_quantize_cols) with calib_algo 'mse' dynamic groups: the qparams of a group
+ * are searched (get_mse_range, as llmc_mse_qparams_panel) on W[:, i : min(i + group_size, n_quant)] as it stands when
+ * the 128-column block holding column i begins, the values the reference's search sees (gptq.py:216-221). Once per
+ * block, on `stream`, the groups starting in the block are searched, then the block runs with those qparams.
+ * Outputs as for static_groups = 0: scales / zeros [R, ceil(K / group_size)] fp32 in processing order; groups the loop
+ * never visits (n_quant < K) keep their input values. zeros may be NULL when sym. group_size in {16, 32, 64, 128}
+ * (others LLMC_ENOTSUP); nsteps = int(maxshrink * mse_grid), grid = mse_grid, norm = 2.4 in the reference.
+ * ws: llmc_gptq_quantize_mse_ws_bytes(R, K) bytes, 256-B aligned. */
+size_t llmc_gptq_quantize_mse_ws_bytes(int64_t R, int64_t K);
+int llmc_gptq_quantize_mse(float* W, const float* Hinv, int64_t R, int64_t K, int64_t n_quant, int sym, float qmin,
+                           float qmax, int64_t group_size, int round_zp, int nsteps, int grid, float norm, float* scales,
+                           float* zeros, float* Wout, float* losses, int blocksize, void* ws, llmc_stream_t stream);
 
 /* SpQR.weight_transform (spqr.py:185-254) for asymmetric per-group weights (a symmetric weight quantizer crashes in the
  * reference's get_group_qparams): the blocked column loop with

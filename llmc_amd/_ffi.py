@@ -37,6 +37,8 @@ SIGNATURES = {
     'llmc_histc_ws_bytes': (_sz, [_i32]),
     'llmc_histc': (_i32, [_vp, _i32, _i64, _i32, _f32, _f32, _vp, _vp, _vp]),
     'llmc_mse_qparams': (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _f32, _f32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    'llmc_mse_qparams_panel': (_i32, [_vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _f32, _f32, _i32, _i32, _f32, _vp,
+                                      _vp, _i64, _i64, _vp]),
     'llmc_quant_static': (_i32, [_vp, _i32, _i64, _i64, _vp, _i32, _vp, _i32, _f32, _f32, _i32, _vp, _vp]),
     'llmc_quant_dynamic_ws_bytes': (_sz, [_i64, _i64]),
     'llmc_quant_dynamic': (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -68,6 +70,9 @@ SIGNATURES = {
                                   _i32, _vp, _vp]),
     'llmc_gptq_quantize_cols': (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _f32, _f32, _i64, _i32, _vp, _vp, _vp, _vp, _vp,
                                        _i32, _vp, _vp]),
+    'llmc_gptq_quantize_mse_ws_bytes': (_sz, [_i64, _i64]),
+    'llmc_gptq_quantize_mse': (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _f32, _f32, _i64, _i32, _i32, _i32, _f32, _vp, _vp,
+                                      _vp, _vp, _i32, _vp, _vp]),
     'llmc_spqr_quantize_ws_bytes': (_sz, [_i64, _i64]),
     'llmc_spqr_quantize': (_i32, [_vp, _vp, _i64, _i64, _f32, _f32, _i64, _f32, _i32, _f32, _f32, _f32, _f32, _vp, _vp,
                                   _vp, _vp, _vp, _i32, _vp, _vp]),

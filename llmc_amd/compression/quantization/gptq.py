@@ -57,16 +57,32 @@ class GPTQ(BaseBlockwiseQuantization):
             self.n_outs = special['n_outs']
             self.static_groups = False
             self.actorder = False
-        if self.wquantizer.calib_algo == 'mse' and not self.static_groups and self.wquantizer.granularity == 'per_group':
-            # the column loop's kernel takes the qparams of a group from min/max of the current weights; searched
-            # ranges inside the loop are not on the accelerated path (static_groups / per-channel use the quantizer)
-            raise NotImplementedError('GPTQ with calib_algo=mse needs static_groups (or per_channel weights)')
+        mse = None
+        wq = self.wquantizer
+        if wq.calib_algo == 'mse' and not self.static_groups and wq.granularity == 'per_group':
+            # dynamic groups: get_mse_range at every group start (gptq.py:216-221), searched once per 128-column block
+            # on the block-start weights (llmc_gptq_quantize_mse). static_groups / per_channel take the quantizer's
+            # qparams of the original weights like every other calib_algo.
+            if int(wq.group_size) not in (16, 32, 64, 128):
+                raise NotImplementedError(f'GPTQ with calib_algo=mse and dynamic groups: group_size {wq.group_size} is '
+                                          'not supported (the per-block search covers group sizes 16, 32, 64 and 128, '
+                                          'which divide the 128-column block)')
+            if not wq.round_zp:
+                raise NotImplementedError('GPTQ with calib_algo=mse and dynamic groups needs round_zp=True: the column '
+                                          'loop quantizes with round(w / s) + z, not round(w / s + z)')
+            mse = (bool(wq.round_zp), int(wq.maxshrink * wq.mse_grid), int(wq.mse_grid), 2.4)
         self.need_perm = (self.wquantizer.granularity == 'per_group' and not self.static_groups
                           and self.actorder) or self.owq
         gs = self.wquantizer.group_size if self.wquantizer.granularity == 'per_group' else 0
         self.gcfg = GptqConfig(bit=self.wquantizer.bit, symmetric=self.wquantizer.sym, group_size=gs,
                                actorder=self.actorder, static_groups=self.static_groups, percdamp=self.percdamp,
-                               blocksize=self.blocksize)
+                               blocksize=self.blocksize, mse=mse)
+
+    def _check_mse_rows(self, R):
+        """get_mse_range's assertion (quant.py:147-150) on one layer's [R, g] group tensor: mse_b_num must divide R."""
+        if self.gcfg.mse is not None:
+            b = self.wquantizer.mse_b_num
+            assert b >= 1 and R % b == 0, 'Batch number must be divisible by tensor.shape[0],'
 
     # ---- calibration: Hessian accumulation ---------------------------------------------------------
     @torch.no_grad()
@@ -270,6 +286,8 @@ class GPTQ(BaseBlockwiseQuantization):
         still shared by layers that see the same input)."""
         H = self._groups[gid]['acc'].H
         self.last_losses = {}
+        for l in layers:
+            self._check_mse_rows(l.weight.shape[0])
         for l, n in zip(layers, names):
             n_out = int(self.n_out_dict[n])
             z = l.buf_zeros if (torch.is_tensor(l.buf_zeros) and l.buf_zeros.dim() > 0) else None
@@ -293,6 +311,8 @@ class GPTQ(BaseBlockwiseQuantization):
     def _transform_group(self, gid, layers, names):
         if self.owq:
             return self._transform_owq(gid, layers, names)
+        for l in layers:
+            self._check_mse_rows(l.weight.shape[0])
         H = self._groups[gid]['acc'].H
         static = None
         if self.gcfg.static_groups or not self.gcfg.group_size:
@@ -448,9 +468,13 @@ class GPTQ(BaseBlockwiseQuantization):
                 zeros = self.qparams['zero'].reshape(R, 1).float()
         if not W.is_contiguous():
             raise ValueError('GPTQ.weight_transform: W must be contiguous (it is updated in place)')
+        mse = getattr(getattr(self, 'gcfg', None), 'mse', None) if dynamic else None
+        if mse is not None:
+            self._check_mse_rows(R)
         t, l, s, z = gptq_ops.gptq_quantize(W, Hinv.contiguous(), wq.sym, qmin, qmax, gs, self.static_groups, col_group, scales,
                                             zeros, want_losses=True, blocksize=self.blocksize,
-                                            n_quant=n_nonout if n_nonout < K else None, init_scales=init_s, init_zeros=init_z)
+                                            n_quant=n_nonout if n_nonout < K else None, init_scales=init_s, init_zeros=init_z,
+                                            mse=mse)
         tmp.copy_(t)
         Losses.copy_(l)
         if dynamic:

@@ -121,18 +121,22 @@ def release_workspaces():
 
 
 def gptq_quantize(W, Hinv, sym, qmin, qmax, group_size, static_groups=False, col_group=None, scales=None,
-                  zeros=None, want_losses=True, blocksize=128, n_quant=None, init_scales=None, init_zeros=None):
+                  zeros=None, want_losses=True, blocksize=128, n_quant=None, init_scales=None, init_zeros=None, mse=None):
     """gptq.py:199-244. W [R,K] fp32 (overwritten with the running weights), Hinv [K,K] fp32 upper.
     Returns (tmp [R,K], losses [R,K] | None, scales [R,ng], zeros [R,ng] | None).
     n_quant < K (OWQ): only the first n_quant columns are quantized, the rest keep receiving the error feedback and
     are left in W; tmp / losses are zero there and dynamic-group qparams of never-visited groups keep
-    init_scales / init_zeros (the reference's `self.groups` starts from the layer's RTN qparams, gptq.py:380-395)."""
+    init_scales / init_zeros (the reference's `self.groups` starts from the layer's RTN qparams, gptq.py:380-395).
+    mse = (round_zp, nsteps, grid, norm): calib_algo 'mse' dynamic groups (llmc_gptq_quantize_mse), the qparams of each
+    group searched on the block-start weights; nsteps = int(maxshrink * mse_grid), grid = mse_grid, norm = 2.4."""
     _ffi.require_gpu(W, Hinv)
     L = _ffi.lib()
     R, K = W.shape
     per_channel = not group_size
     ng = 1 if per_channel else (K + group_size - 1) // group_size
     static_mode = static_groups or per_channel
+    if mse is not None and static_mode:
+        raise ValueError('gptq_quantize: mse searches dynamic group qparams (per_group without static_groups)')
     dev = W.device
     if static_mode:
         scales = scales.to(device=dev, dtype=torch.float32).reshape(R, ng).contiguous()
@@ -154,6 +158,14 @@ def gptq_quantize(W, Hinv, sym, qmin, qmax, group_size, static_groups=False, col
     partial = nq < K
     tmp = torch.zeros_like(W) if partial else torch.empty_like(W)
     losses = (torch.zeros_like(W) if partial else torch.empty_like(W)) if want_losses else None
+    if mse is not None:
+        round_zp, nsteps, grid, norm = mse
+        ws = _ffi.workspace(L.llmc_gptq_quantize_mse_ws_bytes(R, K), dev)
+        _ffi.check(L.llmc_gptq_quantize_mse(
+            _ffi.ptr(W), _ffi.ptr(Hinv), R, K, nq, int(bool(sym)), float(qmin), float(qmax), int(group_size),
+            int(bool(round_zp)), int(nsteps), int(grid), float(norm), _ffi.ptr(scales), _ffi.ptr(zeros), _ffi.ptr(tmp),
+            _ffi.ptr(losses), int(blocksize), _ffi.ptr(ws), _ffi.stream()), 'llmc_gptq_quantize_mse')
+        return tmp, losses, scales, zeros
     ws = _ffi.workspace(L.llmc_gptq_quantize_ws_bytes(R, K), dev)
     _ffi.check(L.llmc_gptq_quantize_cols(
         _ffi.ptr(W), _ffi.ptr(Hinv), R, K, nq, int(bool(sym)), float(qmin), float(qmax), int(group_size or 0),

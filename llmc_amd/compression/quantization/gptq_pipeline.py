@@ -24,6 +24,9 @@ class GptqConfig:
     static_groups: bool = False
     percdamp: float = 0.01
     blocksize: int = 128
+    # calib_algo 'mse' with dynamic groups (get_mse_range at every group start): None = min/max qparams, else
+    # (round_zp, nsteps = int(maxshrink * mse_grid), grid = mse_grid, norm = 2.4) as gptq_ops.gptq_quantize takes it
+    mse: tuple = None
 
     @property
     def qrange(self):
@@ -111,7 +114,8 @@ def quantize_stacked(W_list, H, cfg, static_qparams=None, h_work=None, want_loss
             col_group = (idx // cfg.group_size).to(torch.int32)    # gptq.py:225-227
     tmp, losses, s, z = gptq_ops.gptq_quantize(Wp, U, cfg.symmetric, qmin, qmax, cfg.group_size,
                                                cfg.static_groups, col_group, scales, zeros,
-                                               want_losses=want_losses, blocksize=cfg.blocksize)
+                                               want_losses=want_losses, blocksize=cfg.blocksize,
+                                               mse=None if static_mode else cfg.mse)
     if perm is not None:
         invperm = _inverse_permutation(perm)
         K4 = tmp.shape[1]
@@ -153,7 +157,8 @@ def quantize_owq(W, H, cfg, n_out, wquantizer, rtn_scales=None, rtn_zeros=None, 
         init_s = rtn_scales.reshape(R, ng) if rtn_scales is not None else None
         init_z = rtn_zeros.reshape(R, ng) if (rtn_zeros is not None and rtn_zeros.dim() > 0) else None
         tmp, losses, s, z = gptq_ops.gptq_quantize(Wp, U, cfg.symmetric, qmin, qmax, cfg.group_size, n_quant=n_nonout,
-                                                   init_scales=init_s, init_zeros=init_z, blocksize=cfg.blocksize)
+                                                   init_scales=init_s, init_zeros=init_z, blocksize=cfg.blocksize,
+                                                   mse=cfg.mse)
     else:
         # per_channel: qparams of the permuted, dead-zeroed non-outlier columns in fp32 (gptq.py:157-164)
         _, s, z, _, _ = wquantizer.get_tensor_qparams(Wp[:, :n_nonout].contiguous())

@@ -37,7 +37,8 @@ struct GptqBlockArgs {
     int err_kmajor;
     float* scales;        // [R, ng]
     float* zeros;         // [R, ng] or null (sym static)
-    const int32_t* col_group;  // [K] group of processed column (static mode)
+    const int32_t* col_group;  // [K] group of processed column (static mode), or null: group (i1 + c) / col_gsz
+    int col_gsz;          // static mode without col_group: processing-order groups (per_channel: 1 << 30, group 0)
     int64_t R;
     int K;
     int i1;
@@ -238,7 +239,7 @@ __device__ __forceinline__ bool block_fast(const GptqBlockArgs& a, const float* 
         zr[e] = 0.0f;
         ys[e] = 1.0f;
         if (STATIC) {
-            const int g = a.col_group ? a.col_group[a.i1 + c] : 0;
+            const int g = a.col_group ? a.col_group[a.i1 + c] : (a.i1 + c) / a.col_gsz;
             sc[e] = a.scales[rr * a.ng + g];
             zr[e] = a.zeros ? a.zeros[rr * a.ng + g] : 0.0f;
             ys[e] = rcp_refined(sc[e]);
@@ -380,7 +381,7 @@ __global__ __launch_bounds__(NT) void k_gptq_block(GptqBlockArgs a) {
         sc[e] = 1.0f;
         zr[e] = 0.0f;
         if (a.static_mode && c < a.count) {
-            const int g = a.col_group ? a.col_group[a.i1 + c] : 0;
+            const int g = a.col_group ? a.col_group[a.i1 + c] : (a.i1 + c) / a.col_gsz;
             sc[e] = a.scales[rr * a.ng + g];
             zr[e] = a.zeros ? a.zeros[rr * a.ng + g] : 0.0f;
         }
@@ -448,10 +449,49 @@ extern "C" int llmc_gptq_quantize(float* W, const float* Hinv, int64_t R, int64_
 // loop; the trailing K - n_quant columns (the outlier columns OWQ keeps in floating point) still receive every
 // block's error feedback `W[:, i2:] -= Err1 @ Hinv[i1:i2, i2:]`. Groups are clipped at n_quant like the reference's
 // `min(i + group_size, columns - n_out)`.
+// calib_algo = 'mse' with dynamic groups: the searched qparams of every group that starts in a block (gptq.py:216-221 ->
+// get_mse_range). The reference searches W[:, i:i+g], which inside a block still holds the values the block started
+// with, so each block's groups are searched on the running panel right before its in-block kernel, on the same stream.
+struct MseSearch {
+    int round_zp;
+    int nsteps;
+    int grid;
+    float norm;
+};
+
+static int gptq_cols_impl(float* W, const float* Hinv, int64_t R, int64_t K, int64_t n_quant, int sym, float qmin,
+                          float qmax, int64_t group_size, int static_groups, const int32_t* col_group, float* scales,
+                          float* zeros, float* Wout, float* losses, int blocksize, void* ws, llmc_stream_t stream,
+                          const MseSearch* mse);
+
 extern "C" int llmc_gptq_quantize_cols(float* W, const float* Hinv, int64_t R, int64_t K, int64_t n_quant, int sym,
                                        float qmin, float qmax, int64_t group_size, int static_groups,
                                        const int32_t* col_group, float* scales, float* zeros, float* Wout,
                                        float* losses, int blocksize, void* ws, llmc_stream_t stream) {
+    return gptq_cols_impl(W, Hinv, R, K, n_quant, sym, qmin, qmax, group_size, static_groups, col_group, scales, zeros,
+                          Wout, losses, blocksize, ws, stream, nullptr);
+}
+
+extern "C" size_t llmc_gptq_quantize_mse_ws_bytes(int64_t R, int64_t K) { return llmc_gptq_quantize_ws_bytes(R, K); }
+
+extern "C" int llmc_gptq_quantize_mse(float* W, const float* Hinv, int64_t R, int64_t K, int64_t n_quant, int sym,
+                                      float qmin, float qmax, int64_t group_size, int round_zp, int nsteps, int grid,
+                                      float norm, float* scales, float* zeros, float* Wout, float* losses,
+                                      int blocksize, void* ws, llmc_stream_t stream) {
+    LLMC_REQUIRE(nsteps >= 1 && grid >= 1, "gptq_quantize_mse: nsteps and grid must be positive");
+    if (!(group_size == 16 || group_size == 32 || group_size == 64 || group_size == 128)) {
+        set_last_error_msg("gptq_quantize_mse: the searched group qparams need group_size in {16,32,64,128}");
+        return LLMC_ENOTSUP;
+    }
+    const MseSearch m{round_zp, nsteps, grid, norm};
+    return gptq_cols_impl(W, Hinv, R, K, n_quant, sym, qmin, qmax, group_size, 0, nullptr, scales, zeros, Wout, losses,
+                          blocksize, ws, stream, &m);
+}
+
+static int gptq_cols_impl(float* W, const float* Hinv, int64_t R, int64_t K, int64_t n_quant, int sym, float qmin,
+                          float qmax, int64_t group_size, int static_groups, const int32_t* col_group, float* scales,
+                          float* zeros, float* Wout, float* losses, int blocksize, void* ws, llmc_stream_t stream,
+                          const MseSearch* mse) {
     LLMC_REQUIRE(W && Hinv && Wout && scales && ws && R > 0 && K > 0, "gptq_quantize: null/empty argument");
     LLMC_REQUIRE(n_quant > 0 && n_quant <= K, "gptq_quantize: n_quant must be in (0, K]");
     const int64_t NQ = n_quant;
@@ -459,10 +499,11 @@ extern "C" int llmc_gptq_quantize_cols(float* W, const float* Hinv, int64_t R, i
     LLMC_REQUIRE(K % 4 == 0 && K < (1 << 30), "gptq_quantize: K must be a multiple of 4");
     LLMC_REQUIRE(sym || zeros, "gptq_quantize: zeros required for asymmetric");
     const bool per_channel = group_size <= 0;
-    int static_mode = static_groups || per_channel;
+    // mse: qparams searched per block into scales / zeros, then read like static groups in processing order
+    int static_mode = static_groups || per_channel || mse != nullptr;
     int gsz = (int)group_size;
     int ng = per_channel ? 1 : (int)ceil_div64(K, group_size);
-    if (!static_mode) {
+    if (!static_mode || mse) {
         if (!(gsz == 16 || gsz == 32 || gsz == 64 || gsz == 128)) {
             set_last_error_msg("gptq_quantize: dynamic group qparams need group_size in {16,32,64,128}");
             return LLMC_ENOTSUP;
@@ -529,7 +570,8 @@ extern "C" int llmc_gptq_quantize_cols(float* W, const float* Hinv, int64_t R, i
             GptqBlockArgs a;
             a.W = W; a.U = Hinv; a.Wout = Wout; a.losses = losses;
             a.Err = Err + (ekm ? (i1 - g0) * Rp : (i1 - g0)); a.err_ld = (int)err_ld; a.err_kmajor = ekm ? 1 : 0;
-            a.scales = scales; a.zeros = zeros; a.col_group = per_channel ? nullptr : col_group;
+            a.scales = scales; a.zeros = zeros; a.col_group = (per_channel || mse) ? nullptr : col_group;
+            a.col_gsz = mse ? gsz : 1 << 30;
             a.R = R; a.K = (int)K; a.i1 = (int)i1; a.count = count; a.ng = ng; a.gsz = static_mode ? BS : gsz;
             a.static_mode = static_mode; a.sym = sym; a.qmin = qmin; a.qmax = qmax;
             // 64 KB of LDS per workgroup = 2 workgroups per CU: tall weights use 1024-thread workgroups so that the
@@ -539,6 +581,13 @@ extern "C" int llmc_gptq_quantize_cols(float* W, const float* Hinv, int64_t R, i
             // group sizes 16/32/64 with qparams taken mid-block stay on the generic path (their fast variants
             // spill: the qparams change inside the unrolled loop)
             const int variant = (count != BS || force_generic) ? 0 : static_mode ? 1 : gsz == BS ? BS : 0;
+            if (mse) {
+                // every group starting in [i1, i1 + count) from the block-start panel (gsz divides 128, so groups start
+                // at i1 + k * gsz; the last one is clipped at n_quant like the reference's min(i + g, columns - n_out))
+                int rc = llmc_mse_qparams_panel(W, R, K, i1, count, gsz, sym, mse->round_zp, qmin, qmax, mse->nsteps,
+                                                mse->grid, mse->norm, scales, zeros, ng, i1 / gsz, (llmc_stream_t)st);
+                if (rc) return rc;
+            }
             switch (variant) {
 #define LLMC_GB(V)                                                                                   \
     case V:                                                                                          \

@@ -486,9 +486,49 @@ extern "C" int llmc_minmax_qparams(const void* W, int dt, int64_t G, int64_t g, 
 
 
 // calib_algo = 'mse' (BaseQuantizer.get_mse_range, quant.py:145-203) + get_qparams on the searched range.
-// One wave per row of the [G, g] view. The reference works on tensor.float(): ranges, qparams and the fake-quant are
+// One wave per row of g elements. The reference works on tensor.float(): ranges, qparams and the fake-quant are
 // fp32. Its candidate ranges COMPOUND: best_min_val aliases _min_val, so after an improvement at step i the next
 // candidate is p_{i+1} times the already shrunk range (oracle/quant_ref.py:mse_range pins this against the goldens).
+// Every caller of the search (k_mse_qparams, k_mse_panel) runs this one function, so a row gives the same bits
+// whichever kernel searched it. Returns the searched (min, max) and their qparams, valid in every lane.
+template <typename T>
+__device__ __forceinline__ QParams mse_search_row(const T* __restrict__ w, int g, int lane, int sym, int round_zp,
+                                                  float qmin, float qmax, int nsteps, int grid, float norm,
+                                                  float& min_out, float& max_out) {
+    float mn = INFINITY, mx = -INFINITY;
+    for (int c = lane; c < g; c += 64) {
+        const float x = to_f32<T>(w[c]);
+        mn = fminf(mn, x);
+        mx = fmaxf(mx, x);
+    }
+    float cur_min = wave_min(mn, 64), cur_max = wave_max(mx, 64);
+    const float row_absmax = fmaxf(fabsf(cur_min), fabsf(cur_max));
+    float best = INFINITY;
+    for (int i = 0; i < nsteps; ++i) {
+        const float p = (float)(1.0 - (double)i / (double)grid);   // python float -> fp32 scalar operand
+        const float xmin = p * cur_min, xmax = p * cur_max;
+        const QParams q = qparams_from_minmax(xmin, xmax, LLMC_F32, sym, round_zp, qmin, qmax);
+        const Divisor dv = make_divisor(q.s, row_absmax);
+        float acc = 0.0f;
+        for (int c = lane; c < g; c += 64) {
+            const float x = to_f32<T>(w[c]);
+            const float code = quant_code(x, dv, q.z, LLMC_F32, LLMC_F32, qmin, qmax);
+            const float d = fabsf(dequant_code(code, q.s, q.z, LLMC_F32) - x);
+            acc += powf(d, norm);
+        }
+        const float err = wave_sum(acc, 64);
+        if (err < best) {
+            best = err;
+            cur_min = xmin;
+            cur_max = xmax;
+        }
+    }
+    min_out = cur_min;
+    max_out = cur_max;
+    return qparams_from_minmax(cur_min, cur_max, LLMC_F32, sym, round_zp, qmin, qmax);
+}
+
+// One wave per row of the contiguous [G, g] view.
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_mse_qparams(const T* __restrict__ W, int64_t G, int g, int sym,
                                                         int round_zp, float qmin, float qmax, int nsteps, int grid,
@@ -499,41 +539,41 @@ __global__ __launch_bounds__(kBlock) void k_mse_qparams(const T* __restrict__ W,
     const int64_t wave = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
     const int64_t nwaves = (int64_t)gridDim.x * (kBlock / 64);
     for (int64_t row = wave; row < G; row += nwaves) {
-        const T* w = W + row * g;
-        float mn = INFINITY, mx = -INFINITY;
-        for (int c = lane; c < g; c += 64) {
-            const float x = to_f32<T>(w[c]);
-            mn = fminf(mn, x);
-            mx = fmaxf(mx, x);
-        }
-        float cur_min = wave_min(mn, 64), cur_max = wave_max(mx, 64);
-        const float row_absmax = fmaxf(fabsf(cur_min), fabsf(cur_max));
-        float best = INFINITY;
-        for (int i = 0; i < nsteps; ++i) {
-            const float p = (float)(1.0 - (double)i / (double)grid);   // python float -> fp32 scalar operand
-            const float xmin = p * cur_min, xmax = p * cur_max;
-            const QParams q = qparams_from_minmax(xmin, xmax, LLMC_F32, sym, round_zp, qmin, qmax);
-            const Divisor dv = make_divisor(q.s, row_absmax);
-            float acc = 0.0f;
-            for (int c = lane; c < g; c += 64) {
-                const float x = to_f32<T>(w[c]);
-                const float code = quant_code(x, dv, q.z, LLMC_F32, LLMC_F32, qmin, qmax);
-                const float d = fabsf(dequant_code(code, q.s, q.z, LLMC_F32) - x);
-                acc += powf(d, norm);
-            }
-            const float err = wave_sum(acc, 64);
-            if (err < best) {
-                best = err;
-                cur_min = xmin;
-                cur_max = xmax;
-            }
-        }
+        float cur_min, cur_max;
+        const QParams q = mse_search_row<T>(W + row * g, g, lane, sym, round_zp, qmin, qmax, nsteps, grid, norm,
+                                            cur_min, cur_max);
         if (lane == 0) {
-            const QParams q = qparams_from_minmax(cur_min, cur_max, LLMC_F32, sym, round_zp, qmin, qmax);
             scales[row] = q.s;
             if (zeros) zeros[row] = q.z;
             if (min_out) min_out[row] = cur_min;
             if (max_out) max_out[row] = cur_max;
+        }
+    }
+}
+
+// The same search over the groups of a strided fp32 panel W[r, c0 : c0 + width] (row stride ld), in place: one wave
+// per (row, group), group j covers columns c0 + j*gsz .. min(c0 + (j+1)*gsz, c0 + width). GPTQ's column loop runs it
+// on the running weights at each block start (gptq_loop.hip). Results go to scales / zeros [r * ng + g0 + j].
+__global__ __launch_bounds__(kBlock) void k_mse_panel(const float* __restrict__ W, int64_t R, int64_t ld, int64_t c0,
+                                                      int width, int gsz, int sym, int round_zp, float qmin,
+                                                      float qmax, int nsteps, int grid, float norm,
+                                                      float* __restrict__ scales, float* __restrict__ zeros, int ng,
+                                                      int g0) {
+    const int lane = threadIdx.x & 63;
+    const int nb = (width + gsz - 1) / gsz;
+    const int64_t G = R * nb;
+    const int64_t wave = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    const int64_t nwaves = (int64_t)gridDim.x * (kBlock / 64);
+    for (int64_t t = wave; t < G; t += nwaves) {
+        const int64_t row = t / nb;
+        const int j = (int)(t - row * nb);
+        const int gw = min(gsz, width - j * gsz);
+        float cur_min, cur_max;
+        const QParams q = mse_search_row<float>(W + row * ld + c0 + (int64_t)j * gsz, gw, lane, sym, round_zp, qmin,
+                                                qmax, nsteps, grid, norm, cur_min, cur_max);
+        if (lane == 0) {
+            scales[row * ng + g0 + j] = q.s;
+            if (zeros) zeros[row * ng + g0 + j] = q.z;
         }
     }
 }
@@ -560,6 +600,29 @@ extern "C" int llmc_mse_qparams(const void* W, int dt, int64_t G, int64_t g, int
             hipLaunchKernelGGL((k_mse_qparams<float>), dim3(nblk), dim3(kBlock), 0, st, (const float*)W, G, (int)g, sym,
                                round_zp, qmin, qmax, nsteps, grid, norm, scales, zeros, min_out, max_out);
     }
+    LLMC_LAUNCH_CHECK();
+    return LLMC_OK;
+}
+
+extern "C" int llmc_mse_qparams_panel(const float* W, int64_t R, int64_t ld, int64_t c0, int64_t width,
+                                      int64_t group_size, int sym, int round_zp, float qmin, float qmax, int nsteps,
+                                      int grid, float norm, float* scales, float* zeros, int64_t ng, int64_t g0,
+                                      llmc_stream_t stream) {
+    LLMC_REQUIRE(W && scales && R > 0 && width > 0 && c0 >= 0 && width <= ld - c0,
+                 "mse_qparams_panel: null/empty argument or panel outside the row");
+    LLMC_REQUIRE(sym || zeros, "mse_qparams_panel: zeros required for asymmetric");
+    LLMC_REQUIRE(nsteps >= 1 && grid >= 1, "mse_qparams_panel: nsteps and grid must be positive");
+    if (!(group_size == 16 || group_size == 32 || group_size == 64 || group_size == 128)) {
+        set_last_error_msg("mse_qparams_panel: group_size must be 16, 32, 64 or 128");
+        return LLMC_ENOTSUP;
+    }
+    LLMC_REQUIRE(width < (1ll << 31), "mse_qparams_panel: panel too wide");
+    const int64_t nb = ceil_div64(width, group_size);
+    LLMC_REQUIRE(g0 >= 0 && ng >= g0 + nb && ng < (1ll << 31), "mse_qparams_panel: groups outside scales' row");
+    hipStream_t st = (hipStream_t)stream;
+    const int nblk = grid_for(R * nb, kBlock / 64);
+    hipLaunchKernelGGL(k_mse_panel, dim3(nblk), dim3(kBlock), 0, st, W, R, ld, c0, (int)width, (int)group_size, sym,
+                       round_zp, qmin, qmax, nsteps, grid, norm, scales, zeros, (int)ng, (int)g0);
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;
 }

@@ -146,6 +146,26 @@ int llmc_mse_qparams_panel(const float* W, int64_t R, int64_t ld, int64_t c0, in
                            int round_zp, float qmin, float qmax, int nsteps, int grid, float norm, float* scales,
                            float* zeros, int64_t ng, int64_t g0, llmc_stream_t stream);
 
+/* calib_algo 'hqq' / method HQQ: optimize_weights_proximal (quant.py:588-610, hqq.py:36-60) after get_tensor_qparams
+ * (quant.py:680-697) on the weight W [R, K] (row stride ld >= K elements, dtype dt), in place: no transposed copy.
+ * axis 1 groups g consecutive elements of a row (group r * (K / g) + k / g); axis 0 groups g consecutive rows of one column
+ * (the reference's W.T reshaped: group k * (R / g) + r / g). g = group_size in {16, 32, 64, 128} dividing the grouped
+ * dimension, anything else LLMC_ENOTSUP. The start is get_qparams of the group's min / max in fp32 (bit for bit
+ * llmc_minmax_qparams on W.float()), or the given s_in / z_in (fp32 [G], group order; z_in NULL = 0) when s_in is not NULL.
+ * Each iteration, in fp32 with one rounding per op: q = clamp(round(W * inv + z)), W_r = (q - z) / inv (inv = 1 / s; quant.py:593-598), the shrink
+ * sign(d) * relu(|d| - c * |d|^p1) (lp_norm_one: relu(|d| - c)), c = fp32(1 / beta) computed in double, p1 = fp32(lp_norm - 1),
+ * pow evaluated in fp64 and rounded once; the new zero is the group mean in ATen's CPU inner-sum order. The error of an
+ * iteration is mean |W - W_r| over the tensor, summed in fp64 in a fixed order and rounded to fp32; the first iteration
+ * whose error is not below the best stops the loop and its zeros are returned (beta's decay by kappa has no effect in the
+ * reference: its shrink reads self.beta). Outputs: scales = 1 / (1 / s), zeros, fp32 [G] in group order; errs (optional,
+ * fp64 [iters]) the per-iteration mean errors up to the stop; t_out (optional, int32 [1]) the stop iteration (iters - 1
+ * when the loop runs out, -1 when iters == 0). Stream-ordered, no host synchronisation. ws: llmc_hqq_ws_bytes. */
+size_t llmc_hqq_ws_bytes(int64_t R, int64_t K, int axis, int64_t group_size, int iters);
+int llmc_hqq_optimize(const void* W, int dt, int64_t R, int64_t K, int64_t ld, int axis, int64_t group_size, int sym,
+                      int round_zp, float qmin, float qmax, const float* s_in, const float* z_in, float c, float p1,
+                      int lp_norm_one, int iters, float* scales, float* zeros, double* errs, int* t_out, void* ws,
+                      llmc_stream_t stream);
+
 /* IntegerQuantizer.quant / quant_dequant with given qparams (quant.py:699-717), i.e. the arithmetic of
  * fake_quant_weight_static (quant.py:785-831) and real_quant_weight_static (quant.py:871-914).
  * W: [G, g] dtype wdt. scales [G] dtype sdt. zeros [G] dtype zdt, or NULL (== 0, the symmetric case).

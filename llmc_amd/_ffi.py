@@ -39,6 +39,9 @@ SIGNATURES = {
     'llmc_mse_qparams': (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _f32, _f32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
     'llmc_mse_qparams_panel': (_i32, [_vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _f32, _f32, _i32, _i32, _f32, _vp,
                                       _vp, _i64, _i64, _vp]),
+    'llmc_hqq_ws_bytes': (_sz, [_i64, _i64, _i32, _i64, _i32]),
+    'llmc_hqq_optimize': (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _i64, _i32, _i32, _f32, _f32, _vp, _vp, _f32, _f32,
+                                 _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     'llmc_quant_static': (_i32, [_vp, _i32, _i64, _i64, _vp, _i32, _vp, _i32, _f32, _f32, _i32, _vp, _vp]),
     'llmc_quant_dynamic_ws_bytes': (_sz, [_i64, _i64]),
     'llmc_quant_dynamic': (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),

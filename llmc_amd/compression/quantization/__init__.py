@@ -8,3 +8,4 @@ from .rtn import RTN  # noqa: F401
 from .gptq import GPTQ  # noqa: F401
 from .awq import Awq  # noqa: F401
 from .spqr import SpQR  # noqa: F401
+from .hqq import HQQ  # noqa: F401

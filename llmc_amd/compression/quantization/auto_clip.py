@@ -20,6 +20,9 @@ class AutoClipper:
                  external_ranges=False):
         if clip_version not in ('v1', 'v2'):
             raise Exception('Not support other clip version')
+        if getattr(wquantizer, 'calib_algo', None) == 'hqq':
+            raise NotImplementedError('AutoClipper with calib_algo=hqq: the solver would run for every clip candidate; '
+                                      'not built')
         if clip_version == 'v2' and not external_ranges and getattr(wquantizer, 'granularity', None) == 'per_group':
             # fail where the configuration is read, not after block 0's calibration forward: with per_group
             # weights the reference's v2 search raises inside its own quantizer (the [oc, 1, ng, 1] scales do not broadcast

@@ -60,6 +60,9 @@ class Awq(BaseBlockwiseQuantization):
     def __init__(self, model, quant_config, input, padding_mask, config):
         super().__init__(model, quant_config, input, padding_mask, config)
         special = self.quant_config.get('special', {}) or {}
+        if self.wquantizer.calib_algo == 'hqq':
+            raise NotImplementedError('Awq with calib_algo=hqq: the solver would run for every grid point of the scale '
+                                      'search; not built. method: HQQ quantizes weights with it.')
         self.trans = special.get('trans', True)
         self.trans_version = special.get('trans_version', 'v2')
         self.save_scale = special.get('save_scale', False)

@@ -40,6 +40,9 @@ class GPTQ(BaseBlockwiseQuantization):
     @torch.no_grad()
     def add_quant_config(self):
         special = self.quant_config['special']
+        if self.wquantizer.calib_algo == 'hqq':
+            raise NotImplementedError('GPTQ with calib_algo=hqq: the solver would run per group inside the column loop '
+                                      '(gptq.py:216-221); not built. method: HQQ quantizes weights with it.')
         self.true_sequential = special['true_sequential']
         self.static_groups = special['static_groups']
         self.actorder = special['actorder']

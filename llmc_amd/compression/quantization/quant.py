@@ -7,7 +7,11 @@ named in BASELINE.json); granularity per_group / per_channel / per_token / per_t
 FloatQuantizer e4m3 / e5m2 with qtorch.float_quantize restated (fp8_semantics='cast': torch's dtype cast).
 Also in scope: calib_algo 'mse' (get_mse_range, quant.py:145-203).
 Also in scope: calib_algo 'learnable' (get_learnable_range, quant.py:205-224: the range AutoClipper's clip v2 factors scale).
-Out of scope (raise NotImplementedError): hqq range search, W48.
+Also in scope: calib_algo 'hqq' on IntegerQuantizer per_group weights with group sizes 16 / 32 / 64 / 128 (get_hqq_qparams,
+optimize_weights_proximal, quant.py:588-610, 680-697: the half-quadratic zero-point solver, llmc_hqq_optimize); the method
+HQQ (hqq.py) runs the same solver. FloatQuantizer refuses hqq: the reference's solver rounds to an integer grid.
+Out of scope (raise NotImplementedError): W48; calib_algo 'hqq' inside GPTQ's column loop, AWQ's search, AutoClipper and
+SpQR (the algorithms refuse it).
 
 Tensors must live on the GPU; there is no CPU fallback (see llmc_amd/_ffi.py).
 """
@@ -30,8 +34,9 @@ class BaseQuantizer(object):
         self.kwargs = kwargs
 
         self.calib_algo = self.kwargs.get('calib_algo', 'minmax')
-        if self.calib_algo not in ('minmax', 'static_minmax', 'static_moving_minmax', 'static_hist', 'mse', 'learnable'):
-            raise NotImplementedError(f'calib_algo={self.calib_algo}: hqq ranges are outside the hot path')
+        if self.calib_algo not in ('minmax', 'static_minmax', 'static_moving_minmax', 'static_hist', 'mse', 'learnable',
+                                   'hqq'):
+            raise NotImplementedError(f'calib_algo={self.calib_algo} is outside the hot path')
         # hist config (quant.py:81-86)
         self.bins = self.kwargs.get('bins', 2048)
         self.upsample_rate = self.kwargs.get('upsample_rate', 16)
@@ -39,6 +44,12 @@ class BaseQuantizer(object):
         self.mse_b_num = self.kwargs.get('mse_b_num', 1)
         self.maxshrink = self.kwargs.get('maxshrink', 0.8)
         self.mse_grid = self.kwargs.get('mse_grid', 100)
+        # hqq config (quant.py:87-101). The reference's shrink reads self.beta, not the beta its loop decays by kappa, so
+        # kappa has no effect on the result; it is kept for the surface.
+        self.lp_norm = self.kwargs.get('lp_norm', 0.7)
+        self.beta = self.kwargs.get('beta', 10)
+        self.kappa = self.kwargs.get('kappa', 1.01)
+        self.iters = self.kwargs.get('iters', 20)
 
         if self.granularity == 'per_group':
             self.group_size = self.kwargs['group_size']
@@ -310,9 +321,78 @@ class IntegerQuantizer(BaseQuantizer):
         self.qmax = torch.tensor(self.qmax)
         self.dst_nbins = 2 ** bit
 
+    # ---- calib_algo 'hqq' (quant.py:588-610, 680-689) ------------------------------------------------
+    def hqq_solve(self, weight, axis=1, scales=None, zeros=None, lp_norm=None, beta=None, iters=None):
+        """The half-quadratic solver on a 2-D weight in place (llmc_hqq_optimize). axis 1: groups along the rows of
+        `weight` (reshape_tensor of weight); axis 0: groups along its columns (reshape_tensor of weight.T), without a
+        transposed copy. Starts from get_qparams of the groups' fp32 min / max, or from the given fp32 scales / zeros
+        (one per group, group order). -> (scales [G, 1], zeros [G, 1] (0-dim 0.0 for a symmetric quantizer and no
+        iteration), T, per-iteration fp64 errors): the reference's return values, its stop iteration and the errors it
+        logs (hqq.py:51; entries after T are NaN)."""
+        _ffi.require_gpu(weight, scales)
+        if self.granularity != 'per_group':
+            raise NotImplementedError(f'calib_algo=hqq with granularity {self.granularity}: only per_group is built')
+        if weight.dim() != 2:
+            raise ValueError('hqq_solve takes a 2-D weight')
+        lp_norm = self.lp_norm if lp_norm is None else lp_norm
+        beta = self.beta if beta is None else beta
+        iters = int(self.iters if iters is None else iters)
+        R, K = weight.shape
+        w = weight if weight.stride(-1) == 1 and weight.stride(0) >= K else weight.contiguous()
+        n = R if axis == 0 else K
+        g = int(self.group_size) if n >= int(self.group_size) else n        # reshape_tensor keeps a short last dim whole
+        if n % g:
+            raise ValueError(f'Dimension {n} not divisible by group size {g}')
+        G = R * K // g
+        L = _ffi.lib()
+        dev = w.device
+        s_out = torch.empty(G, dtype=torch.float32, device=dev)
+        z_out = torch.empty(G, dtype=torch.float32, device=dev)
+        errs = torch.full((max(iters, 1),), float('nan'), dtype=torch.float64, device=dev)
+        t_out = torch.empty(1, dtype=torch.int32, device=dev)
+        s_in = z_in = None
+        if scales is not None:
+            s_in = scales.reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
+            if s_in.numel() != G:
+                raise ValueError(f'{s_in.numel()} scales for {G} groups')
+            if torch.is_tensor(zeros) and zeros.dim() > 0:
+                z_in = zeros.reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
+            elif zeros is not None and float(zeros) != 0.0:
+                z_in = torch.full((G,), float(zeros), dtype=torch.float32, device=dev)
+        # the reference's scalars as ATen meets them: (1.0 / beta) in double, then cast to the fp32 tensor's opmath; the
+        # pow exponent (lp_norm - 1) cast to fp32 (pow_tensor_scalar)
+        c = float(torch.tensor(1.0 / beta, dtype=torch.float32))
+        p1 = float(torch.tensor(lp_norm - 1, dtype=torch.float32))
+        ws = _ffi.workspace(L.llmc_hqq_ws_bytes(R, K, int(axis), g, iters), dev)
+        _ffi.check(L.llmc_hqq_optimize(
+            _ffi.ptr(w), _ffi.dt(w), R, K, w.stride(0), int(axis), g, int(self.sym), int(self.round_zp), float(self.qmin),
+            float(self.qmax), _ffi.ptr(s_in), _ffi.ptr(z_in), c, p1, int(lp_norm == 1), iters, _ffi.ptr(s_out),
+            _ffi.ptr(z_out), _ffi.ptr(errs), _ffi.ptr(t_out), _ffi.ptr(ws), _ffi.stream()), 'llmc_hqq_optimize')
+        zeros_out = z_out.reshape(G, 1)
+        if iters == 0 and self.sym and z_in is None:
+            zeros_out = torch.tensor(0.0)
+        return s_out.reshape(G, 1), zeros_out, t_out, errs[:iters]
+
+    def get_hqq_qparams(self, tensor, args={}):
+        """quant.py:680-689 -> (tensor.float() reshaped, scales, zeros, qmax, qmin); min / max, get_qparams and the solver
+        run in one kernel chain on the tensor as it is."""
+        t2 = self.reshape_tensor(tensor)
+        scales, zeros, _, _ = self.hqq_solve(t2, axis=1)
+        return t2.float(), scales, zeros, self.qmax.to(tensor.device), self.qmin.to(tensor.device)
+
+    def optimize_weights_proximal(self, tensor, scales, zeros, qmax, qmin):
+        """quant.py:588-610 on a [G, g] tensor from given qparams, with this quantizer's lp_norm / beta / iters.
+        qmax / qmin must be this quantizer's."""
+        if float(qmax) != float(self.qmax) or float(qmin) != float(self.qmin):
+            raise NotImplementedError('optimize_weights_proximal: qmin / qmax other than the quantizer\'s')
+        s, z, _, _ = self.hqq_solve(self.reshape_tensor(tensor), axis=1, scales=scales, zeros=zeros)
+        return s, z
+
     # ---- qparams ---------------------------------------------------------------------------------
     def get_tensor_qparams(self, tensor, args={}):
         """quant.py:690-697 -> (reshaped tensor, scales, zeros, qmax, qmin)."""
+        if self.calib_algo == 'hqq':
+            return self.get_hqq_qparams(tensor, args)
         tensor = self.reshape_tensor(tensor)
         if self.calib_algo == 'learnable' and (args.get('upbound_factor') is not None):
             scales, zeros, qmax, qmin = self.get_qparams(self.get_tensor_range(tensor, args), tensor.device)
@@ -429,6 +509,10 @@ class IntegerQuantizer(BaseQuantizer):
             # quant.py:833-869 with the learnable range: qparams from the factor-scaled range, static arithmetic
             q_weight, scales, zeros, qmax, qmin = self.get_tensor_qparams(q_weight, args)
             q_weight = self.quant_dequant(q_weight.contiguous(), scales, zeros, qmax, qmin)
+        elif self.calib_algo == 'hqq':
+            # quant.py:833-869 with get_hqq_qparams: fp32 weight and qparams, static arithmetic, cast back
+            q_weight, scales, zeros, qmax, qmin = self.get_tensor_qparams(q_weight, args)
+            q_weight = self.quant_dequant(q_weight.contiguous(), scales, zeros, qmax, qmin).to(weight.dtype)
         else:
             q_weight = self.reshape_tensor(q_weight)
             q_weight, _, _ = self._dynamic(q_weight, _ffi.OUT_FAKE, False)
@@ -493,6 +577,10 @@ class IntegerQuantizer(BaseQuantizer):
     def real_quant_weight_dynamic(self, weight, args={}):
         """quant.py:916-953"""
         org_w_shape = weight.shape
+        if self.calib_algo == 'hqq':      # codes of the fp32 weight with its hqq qparams (fractional zeros)
+            w, scales, zeros, qmax, qmin = self.get_tensor_qparams(weight, args)
+            codes = self.restore_tensor(self._static(w, scales, zeros, qmax, qmin, self._code_kind()), org_w_shape)
+            return self._finish_real(codes, scales, torch.tensor(0.0) if self.sym else zeros)
         w = self.reshape_tensor(weight)
         codes, scales, zeros = self._dynamic(w, self._code_kind(), True)
         codes = self.restore_tensor(codes, org_w_shape)
@@ -550,6 +638,9 @@ class FloatQuantizer(BaseQuantizer):
                                       '(e3m2 / e4m7 / e2m1 of quant.py:988-990 are not 8-bit storage formats)')
         if self.granularity not in ('per_tensor', 'per_channel', 'per_token', 'per_group', 'per_block'):
             raise NotImplementedError(f'FloatQuantizer granularity={self.granularity}')
+        if self.calib_algo == 'hqq':
+            raise NotImplementedError('FloatQuantizer with calib_algo=hqq: the half-quadratic solver rounds to an integer '
+                                      'grid (torch.round, quant.py:593); the reference has no FP8 form of it')
         self._fmt, self.e_bits, self.m_bits, self._tdtype = self._FMT[self.bit]
         if self.granularity == 'per_block' and self.bit != 'e4m3':
             raise NotImplementedError('FloatQuantizer per_block: e4m3 only (the DeepSeek-V3 checkpoint format)')

@@ -130,6 +130,9 @@ class SpQR(GPTQ):
     @torch.no_grad()
     def add_quant_config(self):
         special = self.quant_config['special']
+        if self.wquantizer.calib_algo == 'hqq':
+            raise NotImplementedError('SpQR with calib_algo=hqq: the solver would run per group inside the column loop; '
+                                      'not built. method: HQQ quantizes weights with it.')
         self.true_sequential = special['true_sequential']
         self.actorder = special['actorder']
         self.percdamp = special['percdamp']

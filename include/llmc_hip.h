@@ -507,6 +507,34 @@ int llmc_fp8_act_quant(const void* X, int dt, int64_t n_elem, int block, void* o
 int llmc_fp8_block_gemm(const void* A8, const float* a_s, const void* B8, const float* b_s, int64_t M, int64_t N,
                         int64_t K, int out_dt, const void* bias, void* C, llmc_stream_t stream);
 
+/* ---- SmoothQuant / OS+ (smoothquant.py:39-59, osplus.py:61-170) ------------------------------------------------------------
+ * Column statistics of X [N, K] dt (N up to 2^31 rows): run[0:K] = max, run[K:2K] = min, run[2K:3K] = max |x| per column, fp32
+ * (exact: they are values of dt). init != 0: the buffers are written; else the batch is folded into them (running max / min
+ * over calibration batches; over the layers of a subset for |W|.max(dim=0)). NaN propagates like torch.amax. glob (optional,
+ * fp32 [2]): max(0, max_k run_max), min(0, min_k run_min) — OS+'s amx / amn. Two stages without atomics: bit-exact whatever
+ * the launch geometry. ws: llmc_col_stats_ws_bytes. */
+size_t llmc_col_stats_ws_bytes(int64_t N, int64_t K);
+int llmc_col_stats(const void* X, int dt, int64_t N, int64_t K, int init, float* run, float* glob, void* ws,
+                   llmc_stream_t stream);
+/* SmoothQuant.search_scale_subset: out[k] = (x^alpha / max(w, 1e-5)^(1 - alpha)).clamp(min=1e-5) in dt, every op rounded to
+ * dt; x_absmax / w_absmax fp32 [K] (llmc_col_stats), x is cast to dt first. Exponents are cast to dt; 0.5 is a square
+ * root, like ATen's pow. */
+int llmc_smooth_scales(const float* x_absmax, const float* w_absmax, int dt, int64_t K, double alpha, double one_minus_alpha,
+                       void* out, llmc_stream_t stream);
+/* OS+ cur_scale of grid point `index` (osplus.py:118-131): st = thresholds[index] (dt, rounded on the host);
+ * out[k] = max(cmx[k] > st ? cmx[k] / st : 1, cmn[k] < -st ? cmn[k] / -st : 1) in dt. cmx / cmn fp32 [K]. */
+int llmc_osplus_scale(const float* cmx, const float* cmn, const void* thresholds, int64_t index, int dt, int64_t K, void* out,
+                      llmc_stream_t stream);
+/* out = fake_quant_act_dynamic(X / s[None, :]) per token (osplus.py:156-157) in one pass over X [N, K] dt: the same bits as
+ * llmc_div_cols followed by llmc_quant_dynamic (kind 0: integer, sym / qmin / qmax as there, round_zp) or by llmc_fp8_quant
+ * with dynamic per-row scales of dt (kind 1: fp8_mode = its `fake` argument's format and semantics bits). Takes rows of whole
+ * 16-byte vectors up to 14 per thread of a 256-thread workgroup (K <= 28672 for 16-bit dt, 14336 for fp32) and 16-byte
+ * aligned buffers; anything else LLMC_ENOTSUP (callers run the two kernels). llmc_osplus_act_step_tier: the vectors-per-thread
+ * tier (2 / 4 / 8 / 14) a width is compiled for, 0 when the kernel does not take it; a pure host call. */
+int llmc_osplus_act_step_tier(int dt, int64_t K);
+int llmc_osplus_act_step(const void* X, const void* s, int dt, int64_t N, int64_t K, int kind, int sym, float qmin, float qmax,
+                         int fp8_mode, void* out, llmc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

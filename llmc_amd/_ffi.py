@@ -106,6 +106,12 @@ SIGNATURES = {
     'llmc_fp8_act_quant': (_i32, [_vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     'llmc_fp8_block_gemm': (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
     'llmc_pack_awq_gemm': (_i32, [_vp, _i32, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    'llmc_col_stats_ws_bytes': (_sz, [_i64, _i64]),
+    'llmc_col_stats': (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
+    'llmc_smooth_scales': (_i32, [_vp, _vp, _i32, _i64, _f64, _f64, _vp, _vp]),
+    'llmc_osplus_scale': (_i32, [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp]),
+    'llmc_osplus_act_step_tier': (_i32, [_i32, _i64]),
+    'llmc_osplus_act_step': (_i32, [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _f32, _f32, _i32, _vp, _vp]),
     'llmc_test_sgemm': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                _i32, _i32, _vp]),
     'llmc_test_sgemm_phased': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),

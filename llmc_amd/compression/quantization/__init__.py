@@ -9,3 +9,5 @@ from .gptq import GPTQ  # noqa: F401
 from .awq import Awq  # noqa: F401
 from .spqr import SpQR  # noqa: F401
 from .hqq import HQQ  # noqa: F401
+from .smoothquant import SmoothQuant  # noqa: F401
+from .osplus import OsPlus  # noqa: F401

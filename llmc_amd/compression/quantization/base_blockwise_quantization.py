@@ -33,6 +33,16 @@ def _get(cfg, key, default=None):
     return getattr(cfg, key, default)
 
 
+def is_norm_module(m):
+    """A norm in the sense of the reference's `isinstance(prev_op[0], tuple(_LLMC_LN_TYPES_ + _TRANSFORMERS_LN_TYPES_))`
+    (smoothquant.py:22, osplus.py:37). transformers stopped listing the models' own RMSNorm classes in ALL_LAYERNORM_LAYERS
+    (LlamaRMSNorm is no longer in it), so a module whose class is named *Norm and that carries a 1-D `weight` counts too."""
+    if isinstance(m, tuple(_LLMC_LN_TYPES_ + _TRANSFORMERS_LN_TYPES_)):
+        return True
+    w = getattr(m, 'weight', None)
+    return type(m).__name__.endswith('Norm') and torch.is_tensor(w) and w.dim() == 1
+
+
 def _world():
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 
@@ -325,10 +335,61 @@ class BaseBlockwiseQuantization(BlockwiseOpt):
         else:
             raise NotImplementedError(f'prev_op {type(prev_op[0])} not supported yet!')
 
+    # ---- shift folding (base_…:613-629, 702-747): OS+ moves the channel-wise shift of a subset's input into the biases ----
+    @torch.no_grad()
+    def apply_shift(self, shifts, prev_op, layers):
+        if shifts is None:
+            return
+        assert len(prev_op) == 1, 'Only support single prev_op. If multi prev_ops, code need to be updated.'
+        if isinstance(prev_op[0], tuple(_LLMC_LINEAR_TYPES_ + _TRANSFORMERS_LINEAR_TYPES_)):
+            assert len(layers) == 1
+            self.shift_fc_fc(prev_op[0], layers[0], shifts)
+        elif isinstance(prev_op[0], tuple(_LLMC_LN_TYPES_ + _TRANSFORMERS_LN_TYPES_)):
+            self.shift_ln_fcs(prev_op[0], layers, shifts)
+        else:
+            raise NotImplementedError(f'prev_op {type(prev_op[0])} not supported yet!')
+
+    @torch.no_grad()
+    def shift_fc_fc(self, fc1, fc2, shifts):
+        """base_…:702-725: fc1.bias -= shifts (the value third of a fused qkv: bias viewed [n_head, 3, head_dim]),
+        fc2.bias += fc2.weight @ shifts; a bias-free fc2 gets the product as a `bias` buffer under `use_shift`."""
+        if fc1.out_features == fc2.in_features * 3:
+            num_heads = self.model.get_model_config().to_dict().get('n_head', None)
+            if getattr(fc1, 'bias', None) is not None:
+                fc1.bias.data = fc1.bias.data.reshape(num_heads, 3, -1)
+                value = fc1.bias.data[:, 2, :].reshape(-1)
+                fc1.bias.data[:, 2, :] = (value - shifts).reshape(fc1.bias[:, 2, :].shape)
+                fc1.bias.data = fc1.bias.data.reshape(-1)
+        else:
+            assert fc1.out_features == fc2.in_features
+            if getattr(fc1, 'bias', None) is not None:
+                fc1.bias.sub_(shifts)
+        if getattr(fc2, 'bias', None) is not None:
+            fc2.bias.add_(fc2.weight @ shifts)
+        elif getattr(self, 'use_shift', False):
+            del fc2.bias
+            fc2.register_buffer('bias', fc2.weight @ shifts)
+
+    @torch.no_grad()
+    def shift_ln_fcs(self, ln, fcs, shifts):
+        """base_…:727-747: ln.bias -= shifts, fc.bias += fc.weight @ shifts for a model with biases."""
+        if not isinstance(fcs, list):
+            fcs = [fcs]
+        if self.model.has_bias():
+            ln.bias.sub_(shifts)
+        for fc in fcs:
+            if self.model.has_bias():
+                fc.bias.add_(fc.weight @ shifts)
+            elif getattr(self, 'use_shift', False):
+                del fc.bias
+                fc.register_buffer('bias', fc.weight @ shifts)
+        for p in list(ln.parameters()) + [q for fc in fcs for q in fc.parameters()]:
+            assert torch.isnan(p).sum() == 0
+
     @torch.no_grad()
     def scale_fc_fc(self, fc1, fc2, scales):
         scales = scales.to(fc1.weight.device)
-        if fc1.out_features == fc2.in_features * 2:                    # fused gate|up: scale the second half
+        if fc1.out_features == fc2.in_features * 2:                   # fused gate|up: scale the second half
             half = fc1.weight.shape[0] // 2
             fc1.weight.data[half:].div_(scales.view(-1, 1))
             if getattr(fc1, 'bias', None) is not None:

@@ -1,0 +1,167 @@
+"""OsPlus (Outlier Suppression+) with llmc's operator surface (llmc/compression/quantization/osplus.py:29-235); the
+threshold search stays on the device.
+
+For a subset behind a norm the reference walks a grid of 100 to several hundred clipping thresholds `st`
+(num = max(100, int(amx / 0.5)), osplus.py:104-117): cur_scale = max(cmx / st, cmn / -st, 1) per channel, every weight of the
+subset scaled and fake-quantized, the (shifted) input divided, fake-quantized per token and sent through the inspected module,
+loss = (org_out - out).pow(2).sum(-1).mean() in the model dtype; the first smallest loss wins (strict `>`, osplus.py:165).
+Here:
+  * column max / min and the global amx / amn come from llmc_col_stats; amx / amn are read once on the host to build the
+    threshold list exactly as the reference does (`st -= step` in Python floats) — the subset's one host sync besides the
+    final finite-loss check; the list is rounded to the activation dtype and uploaded once;
+  * cur_scale of grid point g is llmc_osplus_scale on the device array;
+  * weights are fake-quantized from device copies (awq_ops.scale_fakequant, or mul_cols_ + fake_quant_weight_dynamic for
+    the quantizers it does not fuse) and restored by pointer, no state-dict reload;
+  * x_shift / cur_scale and the per-token fake-quant are one kernel (llmc_osplus_act_step; the two parent kernels for the
+    widths it does not take);
+  * the subset's Linears run on the HIP GEMMs (_hip_linear_forward) for org_out and for every grid point;
+  * the running best (loss, scale) and the loss curve stay on the device.
+Only input_feats[0] is searched: the reference returns from inside its batch loop (osplus.py:196). For models with bias
+(`model.has_bias()`), shift = (cmx + cmn) / 2 and every layer's bias is bias + shift @ W.T during the search
+(osplus.py:134-135: formed from the restored weights at every grid point, so it is the same at each and is formed once)."""
+import torch
+
+from llmc_amd.utils.registry_factory import ALGO_REGISTRY
+
+from . import awq_ops, smooth_ops
+from .awq import _hip_linear_forward
+from .base_blockwise_quantization import BaseBlockwiseQuantization, is_norm_module
+from .module_utils import _LLMC_LINEAR_TYPES_, _TRANSFORMERS_LINEAR_TYPES_
+from .quant import IntegerQuantizer
+
+
+@ALGO_REGISTRY
+class OsPlus(BaseBlockwiseQuantization):
+    def __init__(self, model, quant_config, input, padding_mask, config):
+        torch.set_grad_enabled(False)
+        super().__init__(model, quant_config, input, padding_mask, config)
+        if self.w_only:
+            raise NotImplementedError('OsPlus searches with the activation quantizer (osplus.py:157); the config has no '
+                                      '`act` section')
+        if self.act_static:
+            raise NotImplementedError('OsPlus with static activation quantization: the reference calls update_input_feat '
+                                      'without its is_gqa argument there (osplus.py:235) and raises TypeError')
+        if self.wquantizer.calib_algo == 'hqq':
+            raise NotImplementedError('OsPlus with calib_algo=hqq: the solver would run for every point of the threshold '
+                                      'grid; not built')
+        self.last_search = None
+
+    @torch.no_grad()
+    def filter_subset(self, prev_op):
+        """osplus.py:35-40; see is_norm_module"""
+        return is_norm_module(prev_op[0])
+
+    @torch.no_grad()
+    def get_original_out(self, x, inspect_module, subset_kwargs):
+        """osplus.py:42-48"""
+        org_out = inspect_module(x, **subset_kwargs)
+        if isinstance(org_out, tuple):
+            org_out = org_out[0]
+        return org_out
+
+    def _fake_quantize_weight(self, w0, cols, s0=None):
+        """osplus.py:137-154 for one layer from its original weight (not modified): the scaled, fake-quantized weight;
+        a block-wise FP8 checkpoint weight (s0 = its weight_scale_inv) is de-blocked, scaled, fake-quantized and re-blocked
+        -> (fp8 weight, new weight_scale_inv)."""
+        wq = self.wquantizer
+        if w0.dtype == torch.float8_e4m3fn:
+            tmp = self._fp8_to_bf16(w0, s0)
+            tmp = wq.fake_quant_weight_dynamic(awq_ops.mul_cols_(tmp, cols.to(tmp.dtype)))
+            return self._bf16_to_fp8(tmp)
+        if (isinstance(wq, IntegerQuantizer) and wq.granularity in ('per_group', 'per_channel')
+                and wq.calib_algo == 'minmax' and wq.round_zp):
+            return awq_ops.scale_fakequant(w0, cols, wq)
+        return wq.fake_quant_weight_dynamic(awq_ops.mul_cols_(w0.clone(), cols))
+
+    @torch.no_grad()
+    def search_scale_shift_subset(self, layers, input_feats, inspect_module, subset_kwargs):
+        """osplus.py:50-196 -> (best_scale, shift | None)."""
+        dev = next(inspect_module.parameters()).device
+        x = input_feats[0] = input_feats[0].to(dev)
+        if x.dim() not in (2, 3):
+            raise NotImplementedError(f'OsPlus: {x.dim()}-D input (the reference defines cmx / cmn for 2-D and 3-D inputs)')
+        kwargs = subset_kwargs[0] if isinstance(subset_kwargs, list) else (subset_kwargs or {})
+        has_bias = bool(self.model.has_bias())
+        if has_bias:
+            if any(self._is_fp8(fc) for fc in layers):
+                raise NotImplementedError('OsPlus: a model with bias and a block-wise FP8 checkpoint (the reference forms '
+                                          'shift @ W.T on the float8 weight, which has no matmul)')
+            st = smooth_ops.col_stats(x)
+            shift = (st.max.to(x.dtype) + st.min.to(x.dtype)) / 2                    # osplus.py:61-68
+            x_shift = x - shift
+        else:
+            shift, x_shift = None, x
+        st = smooth_ops.col_stats(x_shift)                                           # osplus.py:91-102
+        cmx, cmn = st.max, st.min
+        amx, amn = (float(v) for v in st.glob.tolist())                              # the host sync of the grid
+        thr_host = smooth_ops.osplus_thresholds(amx, amn)
+        thr = torch.tensor(thr_host, dtype=x.dtype).to(dev)
+        n_pts = len(thr_host)
+        if n_pts == 0:
+            raise NotImplementedError(f'OsPlus: no threshold to search (amx = {amx}, amn = {amn}: the grid starts at '
+                                      'max(-amn, amx) and stops at 1.0); the reference then scales by a bound below 1')
+
+        org_w = [fc.weight.data for fc in layers]
+        org_s = [fc.weight_scale_inv.data if self._is_fp8(fc) else None for fc in layers]
+        org_b = [fc.bias.data if has_bias else None for fc in layers]
+        losses = None
+        with _hip_linear_forward(layers):
+            org_out = self.get_original_out(x, inspect_module, kwargs)
+            if has_bias:
+                for fc in layers:                                                    # osplus.py:134-135
+                    fc.bias.data = fc.bias.data + shift @ fc.weight.data.T
+            try:
+                for g in range(n_pts):
+                    cur_scale = smooth_ops.osplus_scale(cmx, cmn, thr, g)
+                    for fc, w0, s0 in zip(layers, org_w, org_s):
+                        if s0 is not None:
+                            fc.weight.data, fc.weight_scale_inv.data = self._fake_quantize_weight(w0, cur_scale, s0)
+                        else:
+                            fc.weight.data = self._fake_quantize_weight(w0, cur_scale)
+                    q_x = smooth_ops.act_step(x_shift, cur_scale, self.aquantizer)   # osplus.py:156-157
+                    out = inspect_module(q_x, **kwargs)
+                    if isinstance(out, tuple):
+                        out = out[0]
+                    loss = (org_out - out).pow(2).sum(-1).mean().reshape(1)          # model dtype, osplus.py:163
+                    if losses is None:
+                        losses = torch.empty(n_pts, dtype=loss.dtype, device=dev)
+                        best_loss, best_scale = loss, cur_scale
+                        best_idx = torch.zeros(1, dtype=torch.int64, device=dev)
+                    else:
+                        better = best_loss > loss                                    # strict: the first minimum stays
+                        best_scale = torch.where(better, cur_scale, best_scale)
+                        best_idx = torch.where(better, torch.full_like(best_idx, g), best_idx)
+                        best_loss = torch.where(better, loss, best_loss)
+                    losses[g:g + 1] = loss
+            finally:
+                for fc, w0, s0, b0 in zip(layers, org_w, org_s, org_b):              # inspect_module.load_state_dict(org_sd)
+                    fc.weight.data = w0
+                    if s0 is not None:
+                        fc.weight_scale_inv.data = s0
+                    if b0 is not None:
+                        fc.bias.data = b0
+        self.last_search = {'losses': losses, 'index': best_idx, 'thresholds': thr_host, 'amx': amx, 'amn': amn,
+                            'cmx': cmx, 'cmn': cmn}
+        if not bool(torch.isfinite(best_loss).all()):
+            raise RuntimeError('OsPlus threshold search: the winning loss is not finite (the reference would return the scale '
+                               'of the first threshold here)')
+        return best_scale, shift
+
+    @torch.no_grad()
+    def subset_transform(self, subset, input_feat, subset_kwargs):
+        """osplus.py:198-235"""
+        layers_dict = subset['layers']
+        prev_op = subset['prev_op']
+        input_name = subset['input'][0]
+        inspect_module = subset['inspect']
+        assert len(prev_op) == 1, 'Only support single prev_op. If multi prev_ops, code need to be updated.'
+        layers = list(layers_dict.values())
+        if (isinstance(prev_op[0], tuple(_LLMC_LINEAR_TYPES_ + _TRANSFORMERS_LINEAR_TYPES_))
+                and prev_op[0].out_features != layers[0].in_features * 3
+                and prev_op[0].out_features != layers[0].in_features):
+            return
+        if not self.filter_subset(prev_op):
+            return
+        scale, shift = self.search_scale_shift_subset(layers, input_feat[input_name], inspect_module, subset_kwargs)
+        self.apply_shift(shift, prev_op, layers)
+        self.apply_scale(scale, prev_op, layers)

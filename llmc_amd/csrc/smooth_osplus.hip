@@ -1,0 +1,424 @@
+// smooth_osplus.hip — the device side of SmoothQuant (smoothquant.py:39-59) and OS+ (osplus.py:61-170).
+//   llmc_col_stats         per-column max / min / max|x| of [N, K], folded into running fp32 [3, K] buffers; two stages, no
+//                          atomics: max and min do not depend on the order, so the result is bit-exact by construction.
+//   llmc_smooth_scales     (x_max^a / w_max^(1-a)).clamp(1e-5), every op rounded to the weight dtype.
+//   llmc_osplus_scale      cur_scale of one threshold of the OS+ grid, from a device array of thresholds.
+//   llmc_osplus_act_step   fake_quant_act_dynamic(x / cur_scale) per token in one pass: the row's quotients stay in
+//                          registers between the range reduction and the quantize. Same bits as llmc_div_cols followed by
+//                          llmc_quant_dynamic (integer) or llmc_fp8_quant (FP8, dynamic per-row scales).
+// All three data passes are HBM-bound; DESIGN.md holds the byte counts they are measured against.
+#include "common.h"
+#include "fp8_math.h"
+#include "quant_math.h"
+#include "vec_powf.h"
+
+namespace llmc {
+
+static constexpr int SB = 256;            // threads per workgroup, every kernel of this file
+static constexpr int CS_ROWS = 16;        // rows one workgroup of k_col_stats_partial folds per turn (4 per wave)
+static constexpr int CS_MAX_BLOCKS = 2048;
+
+// ---- column statistics, stage 1: grid (column blocks, row chunks); a wave reads 64 consecutive vectors of one row ------
+template <typename T, int VEC>
+__global__ __launch_bounds__(SB) void k_col_stats_partial(const T* __restrict__ X, int64_t N, int64_t K, int64_t rows_per_chunk,
+                                                          float* __restrict__ part) {
+    __shared__ float smx[3][SB / 64 - 1][64 * VEC];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t c = ((int64_t)blockIdx.x * 64 + lane) * VEC;
+    const int64_t r0 = (int64_t)blockIdx.y * rows_per_chunk;
+    const int64_t r1 = r0 + rows_per_chunk < N ? r0 + rows_per_chunk : N;
+    float mx[VEC], mn[VEC], am[VEC];
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) {
+        mx[i] = -INFINITY;
+        mn[i] = INFINITY;
+        am[i] = 0.0f;
+    }
+    if (c < K) {
+#pragma unroll 4
+        for (int64_t r = r0 + wv; r < r1; r += SB / 64) {
+            T v[VEC];
+            if constexpr (VEC * sizeof(T) == 16) {
+                const uint4 raw = *reinterpret_cast<const uint4*>(X + r * K + c);
+                __builtin_memcpy(v, &raw, 16);
+            } else {
+                v[0] = X[r * K + c];
+            }
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) {
+                const float f = to_f32<T>(v[i]);
+                // torch.amax / amin / max propagate NaN; fmaxf drops it
+                mx[i] = (f != f || mx[i] != mx[i]) ? NAN : fmaxf(mx[i], f);
+                mn[i] = (f != f || mn[i] != mn[i]) ? NAN : fminf(mn[i], f);
+                am[i] = (f != f || am[i] != am[i]) ? NAN : fmaxf(am[i], fabsf(f));
+            }
+        }
+    }
+    if (wv > 0) {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) {
+            smx[0][wv - 1][lane * VEC + i] = mx[i];
+            smx[1][wv - 1][lane * VEC + i] = mn[i];
+            smx[2][wv - 1][lane * VEC + i] = am[i];
+        }
+    }
+    __syncthreads();
+    if (wv == 0 && c < K) {
+        float* p = part + (int64_t)blockIdx.y * 3 * K;
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) {
+            float a = mx[i], b = mn[i], d = am[i];
+#pragma unroll
+            for (int w = 0; w < SB / 64 - 1; ++w) {
+                const float a2 = smx[0][w][lane * VEC + i], b2 = smx[1][w][lane * VEC + i], d2 = smx[2][w][lane * VEC + i];
+                a = (a != a || a2 != a2) ? NAN : fmaxf(a, a2);
+                b = (b != b || b2 != b2) ? NAN : fminf(b, b2);
+                d = (d != d || d2 != d2) ? NAN : fmaxf(d, d2);
+            }
+            p[c + i] = a;
+            p[K + c + i] = b;
+            p[2 * K + c + i] = d;
+        }
+    }
+}
+
+__device__ __forceinline__ float nan_max(float a, float b) { return (a != a || b != b) ? NAN : fmaxf(a, b); }
+__device__ __forceinline__ float nan_min(float a, float b) { return (a != a || b != b) ? NAN : fminf(a, b); }
+
+// stage 2: the chunks of one column, folded into the running buffers (init: the running buffers are written, not read)
+__global__ __launch_bounds__(SB) void k_col_stats_fold(const float* __restrict__ part, int64_t nchunk, int64_t K, int init,
+                                                       float* __restrict__ run) {
+    const int64_t k = (int64_t)blockIdx.x * SB + threadIdx.x;
+    if (k >= K) return;
+    float a = init ? -INFINITY : run[k], b = init ? INFINITY : run[K + k], d = init ? 0.0f : run[2 * K + k];
+    for (int64_t ch = 0; ch < nchunk; ++ch) {
+        const float* p = part + ch * 3 * K;
+        a = nan_max(a, p[k]);
+        b = nan_min(b, p[K + k]);
+        d = nan_max(d, p[2 * K + k]);
+    }
+    run[k] = a;
+    run[K + k] = b;
+    run[2 * K + k] = d;
+}
+
+// stage 3 (optional): glob[0] = max(0, max_k run_max), glob[1] = min(0, min_k run_min) — osplus.py:97-102
+__global__ __launch_bounds__(1024) void k_col_stats_global(const float* __restrict__ run, int64_t K, float* __restrict__ glob) {
+    __shared__ float sa[16], sb[16];
+    __shared__ int snan[2];
+    if (threadIdx.x < 2) snan[threadIdx.x] = 0;
+    __syncthreads();
+    float a = -INFINITY, b = INFINITY;
+    int na = 0, nb = 0;
+    for (int64_t k = threadIdx.x; k < K; k += 1024) {
+        const float x = run[k], y = run[K + k];
+        na |= (x != x);
+        nb |= (y != y);
+        a = fmaxf(a, x);
+        b = fminf(b, y);
+    }
+    a = wave_max(a, 64);
+    b = wave_min(b, 64);
+    if (na) snan[0] = 1;
+    if (nb) snan[1] = 1;
+    if ((threadIdx.x & 63) == 0) {
+        sa[threadIdx.x >> 6] = a;
+        sb[threadIdx.x >> 6] = b;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < 16; ++i) {
+            a = fmaxf(a, sa[i]);
+            b = fminf(b, sb[i]);
+        }
+        // Python's max(x.max(), 0) / min(x.min(), 0): `0 > nan` is False, so a NaN extreme stays
+        glob[0] = snan[0] ? NAN : fmaxf(a, 0.0f);
+        glob[1] = snan[1] ? NAN : fminf(b, 0.0f);
+    }
+}
+
+// ---- SmoothQuant.search_scale_subset (smoothquant.py:54-59) -----------------------------------------------------------------
+// ATen's Tensor.pow(python_float) casts the exponent to the tensor dtype and evaluates 0.5 as sqrt; any other exponent goes to
+// its vectorised pow, which computes in fp32 for every dtype (vec_powf.h) and rounds to the tensor dtype.
+template <int DT> __device__ __forceinline__ float pow_dt(float x, float e) {
+    if (e == 0.5f) return rndc<DT>(sqrtf(x));
+    if (e == 1.0f) return x;
+    if (e == 0.0f) return 1.0f;
+    if (x > 0.0f && x < INFINITY) return rndc<DT>(sf_powf_pos(x, e));
+    return rndc<DT>((float)pow((double)x, (double)e));      // 0, inf, NaN
+}
+template <typename T>
+__global__ __launch_bounds__(SB) void k_smooth_scales(const float* __restrict__ xmax, const float* __restrict__ wmax, int64_t K,
+                                                      float alpha, float one_minus_alpha, T* __restrict__ out) {
+    constexpr int DT = dt_of<T>::value;
+    const int64_t k = (int64_t)blockIdx.x * SB + threadIdx.x;
+    if (k >= K) return;
+    const float lo = rndc<DT>(1e-5f);
+    const float ea = rndc<DT>(alpha), ew = rndc<DT>(one_minus_alpha);
+    const float x = rndc<DT>(xmax[k]);                 // x_max.to(dtype=w_max.dtype)
+    const float w = nan_max(wmax[k], lo);              // .clamp(min=1e-5) of get_weight_scale
+    const float s = rndc<DT>(pow_dt<DT>(x, ea) / pow_dt<DT>(w, ew));
+    out[k] = from_f32<T>(nan_max(s, lo));
+}
+
+// ---- OS+ cur_scale (osplus.py:118-131): thresholds already rounded to the activation dtype -----------------------------------
+template <typename T>
+__global__ __launch_bounds__(SB) void k_osplus_scale(const float* __restrict__ cmx, const float* __restrict__ cmn,
+                                                     const T* __restrict__ thr, int64_t K, T* __restrict__ out) {
+    constexpr int DT = dt_of<T>::value;
+    const int64_t k = (int64_t)blockIdx.x * SB + threadIdx.x;
+    if (k >= K) return;
+    const float st = to_f32<T>(thr[0]);
+    const float a = cmx[k], b = cmn[k];
+    const float ms = a > st ? rndc<DT>(a / st) : 1.0f;
+    const float ns = b < -st ? rndc<DT>(b / -st) : 1.0f;
+    out[k] = from_f32<T>(nan_max(ms, ns));
+}
+
+// ---- the fused activation step ---------------------------------------------------------------------------------------------
+// One workgroup per token row; thread t owns the 16-byte vectors t, t + 256, ... of the row (MAXV of them at most). The
+// quotients rnd(x / s) stay packed in registers; min / max go through a wave shuffle and 4 LDS words.
+static constexpr int ACT_INT = 0, ACT_FP8 = 1;
+
+template <typename T, int MAXV, int KIND>
+__global__ __launch_bounds__(SB) void k_osplus_act_step(const T* __restrict__ X, const T* __restrict__ s, int64_t N, int K,
+                                                        int sym, float qmin, float qmax, int mode, T* __restrict__ out) {
+    constexpr int DT = dt_of<T>::value;
+    constexpr int V = 16 / sizeof(T);
+    __shared__ float smn[SB / 64], smx[SB / 64];
+    const int nv = K / V;
+    for (int64_t row = blockIdx.x; row < N; row += gridDim.x) {
+        const T* xp = X + row * K;
+        uint4 q[MAXV];
+        float mn = INFINITY, mx = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < MAXV; ++j) {
+            const int vi = j * SB + threadIdx.x;
+            if (vi < nv) {
+                const uint4 rx = *reinterpret_cast<const uint4*>(xp + vi * V);
+                const uint4 rs = *reinterpret_cast<const uint4*>(s + vi * V);
+                T xv[V], sv[V], ov[V];
+                __builtin_memcpy(xv, &rx, 16);
+                __builtin_memcpy(sv, &rs, 16);
+#pragma unroll
+                for (int k = 0; k < V; ++k) {
+                    const float f = rndc<DT>(to_f32<T>(xv[k]) / to_f32<T>(sv[k]));     // llmc_div_cols
+                    ov[k] = from_f32<T>(f);
+                    mn = fminf(mn, f);
+                    mx = fmaxf(mx, f);
+                }
+                __builtin_memcpy(&q[j], ov, 16);
+            }
+        }
+        mn = wave_min(mn, 64);
+        mx = wave_max(mx, 64);
+        __syncthreads();                          // the previous row's readers are done
+        if ((threadIdx.x & 63) == 0) {
+            smn[threadIdx.x >> 6] = mn;
+            smx[threadIdx.x >> 6] = mx;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < SB / 64; ++i) {
+            mn = fminf(mn, smn[i]);
+            mx = fmaxf(mx, smx[i]);
+        }
+        T* op = out + row * K;
+        if constexpr (KIND == ACT_INT) {
+            const QParams qp = qparams_from_minmax(mn, mx, DT, sym, 1, qmin, qmax);
+            const Divisor dv = make_divisor(qp.s, fmaxf(fabsf(mn), fabsf(mx)));
+#pragma unroll
+            for (int j = 0; j < MAXV; ++j) {
+                const int vi = j * SB + threadIdx.x;
+                if (vi < nv) {
+                    T v[V], o[V];
+                    __builtin_memcpy(v, &q[j], 16);
+#pragma unroll
+                    for (int k = 0; k < V; ++k) {
+                        const float c = quant_code(to_f32<T>(v[k]), dv, qp.z, DT, DT, qmin, qmax);
+                        o[k] = from_f32<T>(dequant_code(c, qp.s, qp.z, DT));
+                    }
+                    uint4 ro;
+                    __builtin_memcpy(&ro, o, 16);
+                    *reinterpret_cast<uint4*>(op + vi * V) = ro;
+                }
+            }
+        } else {
+            // llmc_fp8_quant with dynamic per-row scales: amax = clamp(absmax, 1e-5) in dt (the symmetric qparams with
+            // qmax = 1), scale = rnd(amax / finfo.max), zero scales replaced by 1, quotient rounded in dt, the encoder of
+            // fp8_math.h, value * scale in fp32 rounded once.
+            const int fmt = (mode >> 4) & 3, sem = mode & 0x100;
+            const float amax = qparams_from_minmax(mn, mx, DT, 1, 1, -1.0f, 1.0f).s;
+            float sc = rndc<DT>(amax / fp8_format_max(fmt));
+            if (sc == 0.0f) sc = 1.0f;
+#pragma unroll 1
+            for (int j = 0; j < MAXV; ++j) {
+                const int vi = j * SB + threadIdx.x;
+                if (vi < nv) {
+                    uint4 rq = q[0];
+#pragma unroll
+                    for (int jj = 1; jj < MAXV; ++jj)
+                        if (jj == j) rq = q[jj];
+                    T v[V], o[V];
+                    __builtin_memcpy(v, &rq, 16);
+#pragma unroll
+                    for (int k = 0; k < V; ++k) {
+                        const float t = rndc<DT>(rndc<DT>(to_f32<T>(v[k]) / sc) + 0.0f);
+                        float val;
+                        (void)fp8_encode(t, fmt, sem, &val);
+                        o[k] = from_f32<T>(opaque_f32(val * sc));
+                    }
+                    uint4 ro;
+                    __builtin_memcpy(&ro, o, 16);
+                    *reinterpret_cast<uint4*>(op + vi * V) = ro;
+                }
+            }
+        }
+    }
+}
+
+// vectors per thread the row needs: 0 = the kernel does not take the width
+static inline int act_step_tier(int dt, int64_t K) {
+    const int V = 16 / dtype_size(dt);
+    if (K <= 0 || K % V != 0) return 0;
+    const int64_t per = ceil_div64(K / V, SB);
+    if (per <= 2) return 2;
+    if (per <= 4) return 4;
+    if (per <= 8) return 8;
+    if (per <= 14) return 14;
+    return 0;
+}
+
+}  // namespace llmc
+
+using namespace llmc;
+
+static inline int64_t cs_chunks(int64_t N, int64_t K, int vec) {
+    const int64_t colblocks = ceil_div64(K, 64 * (int64_t)vec);
+    int64_t cap = CS_MAX_BLOCKS / colblocks;
+    if (cap < 1) cap = 1;
+    int64_t n = ceil_div64(N, CS_ROWS);
+    if (n > cap) n = cap;
+    return n < 1 ? 1 : n;
+}
+
+extern "C" size_t llmc_col_stats_ws_bytes(int64_t N, int64_t K) {
+    if (N <= 0 || K <= 0) return 0;
+    // sized for the scalar form (the most column blocks leave the fewest chunks; the vector forms never need more per chunk)
+    int64_t n = cs_chunks(N, K, 8), n1 = cs_chunks(N, K, 1), n4 = cs_chunks(N, K, 4);
+    if (n1 > n) n = n1;
+    if (n4 > n) n = n4;
+    return (size_t)n * 3 * (size_t)K * sizeof(float);
+}
+
+extern "C" int llmc_col_stats(const void* X, int dt, int64_t N, int64_t K, int init, float* run, float* glob, void* ws,
+                              llmc_stream_t stream) {
+    LLMC_REQUIRE(dtype_ok(dt), "col_stats: bad dtype");
+    LLMC_REQUIRE(X && run && ws && N > 0 && K > 0, "col_stats: null/empty argument");
+    LLMC_REQUIRE(N < (1ll << 31) + 1 && K < (1ll << 31), "col_stats: N up to 2^31 rows, K below 2^31");
+    hipStream_t st = (hipStream_t)stream;
+    const int V = 16 / dtype_size(dt);
+    const bool vec = K % V == 0 && ((uintptr_t)X & 15) == 0;
+    const int v = vec ? V : 1;
+    const int64_t nchunk = cs_chunks(N, K, v);
+    const int64_t rpc = ceil_div64(N, nchunk);
+    const dim3 grid((unsigned)ceil_div64(K, 64 * (int64_t)v), (unsigned)nchunk);
+    float* part = (float*)ws;
+    if (vec) {
+        if (dt == LLMC_F16) hipLaunchKernelGGL((k_col_stats_partial<f16_t, 8>), grid, dim3(SB), 0, st, (const f16_t*)X, N, K, rpc, part);
+        else if (dt == LLMC_BF16) hipLaunchKernelGGL((k_col_stats_partial<bf16_t, 8>), grid, dim3(SB), 0, st, (const bf16_t*)X, N, K, rpc, part);
+        else hipLaunchKernelGGL((k_col_stats_partial<float, 4>), grid, dim3(SB), 0, st, (const float*)X, N, K, rpc, part);
+    } else {
+        if (dt == LLMC_F16) hipLaunchKernelGGL((k_col_stats_partial<f16_t, 1>), grid, dim3(SB), 0, st, (const f16_t*)X, N, K, rpc, part);
+        else if (dt == LLMC_BF16) hipLaunchKernelGGL((k_col_stats_partial<bf16_t, 1>), grid, dim3(SB), 0, st, (const bf16_t*)X, N, K, rpc, part);
+        else hipLaunchKernelGGL((k_col_stats_partial<float, 1>), grid, dim3(SB), 0, st, (const float*)X, N, K, rpc, part);
+    }
+    LLMC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_col_stats_fold, dim3((unsigned)ceil_div64(K, SB)), dim3(SB), 0, st, (const float*)part, nchunk, K,
+                       init, run);
+    LLMC_LAUNCH_CHECK();
+    if (glob) {
+        hipLaunchKernelGGL(k_col_stats_global, dim3(1), dim3(1024), 0, st, (const float*)run, K, glob);
+        LLMC_LAUNCH_CHECK();
+    }
+    return LLMC_OK;
+}
+
+extern "C" int llmc_smooth_scales(const float* x_absmax, const float* w_absmax, int dt, int64_t K, double alpha,
+                                  double one_minus_alpha, void* out, llmc_stream_t stream) {
+    LLMC_REQUIRE(dtype_ok(dt), "smooth_scales: bad dtype");
+    LLMC_REQUIRE(x_absmax && w_absmax && out && K > 0, "smooth_scales: null/empty argument");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)ceil_div64(K, SB));
+    if (dt == LLMC_F16) hipLaunchKernelGGL((k_smooth_scales<f16_t>), grid, dim3(SB), 0, st, x_absmax, w_absmax, K, (float)alpha, (float)one_minus_alpha, (f16_t*)out);
+    else if (dt == LLMC_BF16) hipLaunchKernelGGL((k_smooth_scales<bf16_t>), grid, dim3(SB), 0, st, x_absmax, w_absmax, K, (float)alpha, (float)one_minus_alpha, (bf16_t*)out);
+    else hipLaunchKernelGGL((k_smooth_scales<float>), grid, dim3(SB), 0, st, x_absmax, w_absmax, K, (float)alpha, (float)one_minus_alpha, (float*)out);
+    LLMC_LAUNCH_CHECK();
+    return LLMC_OK;
+}
+
+extern "C" int llmc_osplus_scale(const float* cmx, const float* cmn, const void* thresholds, int64_t index, int dt, int64_t K,
+                                 void* out, llmc_stream_t stream) {
+    LLMC_REQUIRE(dtype_ok(dt), "osplus_scale: bad dtype");
+    LLMC_REQUIRE(cmx && cmn && thresholds && out && K > 0 && index >= 0, "osplus_scale: null/empty argument");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)ceil_div64(K, SB));
+    const char* thr = (const char*)thresholds + (size_t)index * dtype_size(dt);
+    if (dt == LLMC_F16) hipLaunchKernelGGL((k_osplus_scale<f16_t>), grid, dim3(SB), 0, st, cmx, cmn, (const f16_t*)thr, K, (f16_t*)out);
+    else if (dt == LLMC_BF16) hipLaunchKernelGGL((k_osplus_scale<bf16_t>), grid, dim3(SB), 0, st, cmx, cmn, (const bf16_t*)thr, K, (bf16_t*)out);
+    else hipLaunchKernelGGL((k_osplus_scale<float>), grid, dim3(SB), 0, st, cmx, cmn, (const float*)thr, K, (float*)out);
+    LLMC_LAUNCH_CHECK();
+    return LLMC_OK;
+}
+
+extern "C" int llmc_osplus_act_step_tier(int dt, int64_t K) {
+    if (!dtype_ok(dt)) return 0;
+    return act_step_tier(dt, K);
+}
+
+template <typename T, int KIND>
+static int act_step_launch(int tier, const void* X, const void* s, int64_t N, int64_t K, int sym, float qmin, float qmax,
+                           int mode, void* out, hipStream_t st) {
+    const int64_t cap = (int64_t)device_cu_count() * 8;
+    const dim3 grid((unsigned)(N < cap ? N : cap));
+#define LLMC_ACT_STEP(M)                                                                                              \
+    hipLaunchKernelGGL((k_osplus_act_step<T, M, KIND>), grid, dim3(SB), 0, st, (const T*)X, (const T*)s, N, (int)K, sym, \
+                       qmin, qmax, mode, (T*)out)
+    switch (tier) {
+        case 2: LLMC_ACT_STEP(2); break;
+        case 4: LLMC_ACT_STEP(4); break;
+        case 8: LLMC_ACT_STEP(8); break;
+        default: LLMC_ACT_STEP(14); break;
+    }
+#undef LLMC_ACT_STEP
+    LLMC_LAUNCH_CHECK();
+    return LLMC_OK;
+}
+
+extern "C" int llmc_osplus_act_step(const void* X, const void* s, int dt, int64_t N, int64_t K, int kind, int sym, float qmin,
+                                    float qmax, int fp8_mode, void* out, llmc_stream_t stream) {
+    LLMC_REQUIRE(dtype_ok(dt), "osplus_act_step: bad dtype");
+    LLMC_REQUIRE(X && s && out && N > 0 && K > 0, "osplus_act_step: null/empty argument");
+    LLMC_REQUIRE(kind == ACT_INT || kind == ACT_FP8, "osplus_act_step: kind is 0 (integer) or 1 (FP8)");
+    LLMC_REQUIRE(kind == ACT_INT || ((fp8_mode >> 4) & 3) <= 1, "osplus_act_step: FP8 format is e4m3 or e5m2");
+    const int tier = act_step_tier(dt, K);
+    if (tier == 0 || ((uintptr_t)X & 15) || ((uintptr_t)s & 15) || ((uintptr_t)out & 15)) {
+        set_last_error_msg("osplus_act_step: rows of whole 16-byte vectors, at most 14 per thread of a 256-thread workgroup "
+                           "(K <= 28672 16-bit, 14336 fp32), 16-byte aligned buffers");
+        return LLMC_ENOTSUP;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int mode = fp8_mode & 0x130;
+    if (kind == ACT_INT) {
+        switch (dt) {
+            case LLMC_F16: return act_step_launch<f16_t, ACT_INT>(tier, X, s, N, K, sym, qmin, qmax, mode, out, st);
+            case LLMC_BF16: return act_step_launch<bf16_t, ACT_INT>(tier, X, s, N, K, sym, qmin, qmax, mode, out, st);
+            default: return act_step_launch<float, ACT_INT>(tier, X, s, N, K, sym, qmin, qmax, mode, out, st);
+        }
+    }
+    switch (dt) {
+        case LLMC_F16: return act_step_launch<f16_t, ACT_FP8>(tier, X, s, N, K, sym, qmin, qmax, mode, out, st);
+        case LLMC_BF16: return act_step_launch<bf16_t, ACT_FP8>(tier, X, s, N, K, sym, qmin, qmax, mode, out, st);
+        default: return act_step_launch<float, ACT_FP8>(tier, X, s, N, K, sym, qmin, qmax, mode, out, st);
+    }
+}

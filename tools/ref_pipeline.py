@@ -181,7 +181,14 @@ CONFIGS = {
                             calib_algo='static_minmax'),   # the shipped yml leaves the default 'minmax', which quant.py:573-574 refuses
                    special=dict(trans=True, trans_version='v2', weight_clip=True), quant_out=True),
         calib=dict(name='wikitext2', download=False, n_samples=32, bs=-1, seq_len=64, preproc='wikitext2_gptq')),
+    # configs/quantization/backend/vllm/smoothquant_w8a8.yml: SmoothQuant (alpha at its default 0.5) in front of W8A8
+    # per_channel / per_token
+    'smoothquant_w8a8': dict(
+        quant=dict(method='SmoothQuant', weight=dict(bit=8, symmetric=True, granularity='per_channel'),
+                   act=dict(bit=8, symmetric=True, granularity='per_token')),
+        calib=dict(name='wikitext2', download=False, n_samples=32, bs=1, seq_len=64, preproc='wikitext2_gptq')),
 }
+DEFAULT_NAMES = ('GPTQ', 'Awq', 'RTN', 'SpQR')
 
 
 def bind_restated_qtorch():
@@ -283,7 +290,10 @@ def run_one(M, arm, method, arch, assets, mdir, ddir, stubbed, ref_classes):
     if arm == 'ours':
         sys.path.insert(0, ROOT)
         import llmc_amd
-        llmc_amd.register_into(ALGO_REGISTRY)                     # <- the one line of INTEGRATION.md section 1
+        if key in DEFAULT_NAMES:
+            llmc_amd.register_into(ALGO_REGISTRY)                 # <- the one line of INTEGRATION.md section 1
+        else:                                                     # classes outside the default set are bound by naming them
+            llmc_amd.register_into(ALGO_REGISTRY, names=DEFAULT_NAMES + (key,))
         assert ALGO_REGISTRY[key] is not ref_classes[key]
     else:
         for k, c in ref_classes.items():                          # the reference's own classes (undo an earlier 'ours' pass)
@@ -410,7 +420,7 @@ def main():
     mdir, ddir = make_assets(a.assets, a.arch, n_layers=a.layers)
     M, stubbed = import_reference_main(ref_dir)
     from llmc.utils.registry_factory import ALGO_REGISTRY
-    ref_classes = {k: ALGO_REGISTRY[k] for k in ('GPTQ', 'Awq', 'RTN', 'SpQR')}
+    ref_classes = {k: ALGO_REGISTRY[k] for k in DEFAULT_NAMES + ('SmoothQuant', 'OsPlus')}
     dist.init_process_group(backend='nccl' if gpu else 'gloo', rank=0, world_size=1)     # llmc/__main__.py:191
     if gpu:
         torch.cuda.set_device(0)

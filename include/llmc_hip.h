@@ -92,6 +92,9 @@ int llmc_hip_set_cu_reserve(int n_cus);
  *   gemm3_no_wide     K3's far updates on k_gemm3s instead of k_gemm3w (128 x 128 tiles, two workgroups per CU); same bits
  *   sgemm_no_wide     K4's far update: 1 = on k_sgemm (the kernel of rounds 2-5), 4 = k_sgemm_wide's 256 x 128 form (one workgroup
  *                     per CU) instead of its 128 x 128 form (two per CU, the default); same bits
+ *   no_riders         without helper streams, a column group's far update as one launch over all later columns; default: the
+ *                     128 x 128 tiles of its last columns ride on the next group's in-block launches instead (k_gptq_block_riders,
+ *                     one tile per CU the chain leaves free); same bits
  * set: returns the previous value, or LLMC_EINVAL for an unknown key / negative value. get: the value, or LLMC_EINVAL.
  * option_name: the key of index 0, 1, ... (copied into buf), LLMC_EINVAL past the last one. No reference counterpart. */
 int llmc_hip_set_option(const char* key, int value);

@@ -31,6 +31,15 @@ int llmc_test_gemm3_planes(const float* A, const float* B, float* C, int64_t lda
 /* tools/probes/gemm3s_probe.py: the s_memtime stamps (8 waves x 128 slots, int64) one workgroup of the last k_gemm3s
  * launch wrote under LLMC_GEMM3S_DBG=4, copied to host memory. */
 int llmc_test_gemm3s_stamps(long long* host_out);
+/* tests/test_chain_riders_plan.py: the launches llmc_gptq_quantize_cols issues on one stream (no helper streams) for these
+ * shapes under the calling thread's options, in order, as records of 12 int32: kind (0 in-block kernel, 1 near update, 2 the
+ * next group's columns of a far update cut in three (k4_split_far), 3 far update, 4 flush of queued rider tiles), column
+ * group, the columns written [w0, w1), the err buffer read / written (-1: none), for an in-block launch that carries riders
+ * their group, columns [r0, r1) and err buffer (group -1: none), and the range [k0, k1) of the group's 512 err columns that
+ * riders or a flush apply (0, 0: all). Every field is read back from the arguments the launch would get. Pure host call.
+ * Returns the number of records (only the first `cap` are written) or an error. */
+int llmc_test_gptq_rider_plan(int64_t R, int64_t K, int64_t n_quant, int64_t group_size, int static_groups, int32_t* out,
+                              int cap);
 
 #ifdef __cplusplus
 }

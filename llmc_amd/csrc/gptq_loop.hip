@@ -15,6 +15,7 @@
 #include "common.h"
 #include "quant_math.h"
 #include "sgemm.h"
+#include "sgemm_wide_tile.h"
 #include "side_stream.h"
 #include "pipe_streams.h"
 
@@ -319,111 +320,58 @@ static constexpr int GBT = 512;  // threads per workgroup: 8 waves x 4 rows (102
 // per wave.
 template <int VARIANT, int NT>
 __global__ __launch_bounds__(NT) void k_gptq_block(GptqBlockArgs a) {
-    // Us[i][p*8 + e] = U[i1+i][i1 + p + 16e] for p+16e > i, else 0 ; dg[i] = U[i1+i][i1+i]
     __shared__ __attribute__((aligned(16))) float Us[BS * BS];
     __shared__ float dg[BS];
-    __shared__ float2 dtab[BS];   // fast path: {d, refined 1/d}
-    __shared__ int d_not_plain;   // some d of the block is outside the plain range: generic path for everyone
-    if (threadIdx.x == 0) d_not_plain = 0;
-    __syncthreads();
-    const int tid = threadIdx.x;
-    {
-        // all 8 float4 loads of a thread are issued before the first use (a per-element loop serialises 32
-        // L2 round trips, which used to be most of this kernel's time)
-        constexpr int NV = BS * BS / 4 / NT;
-        float4 v[NV];
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int idx = tid + NT * j;
-            const int i = idx >> 5, c4 = (idx & 31) * 4;   // count and i1 are multiples of 4
-            v[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (i < a.count && c4 < a.count)
-                v[j] = *reinterpret_cast<const float4*>(a.U + (int64_t)(a.i1 + i) * a.K + a.i1 + c4);
-        }
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int idx = tid + NT * j;
-            const int i = idx >> 5, c4 = (idx & 31) * 4;
-            const float vv[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int c = c4 + t;   // column inside the block
-                if (c == i && i < a.count) {
-                    dg[i] = vv[t];
-                    dtab[i] = make_float2(vv[t], rcp_refined(vv[t]));
-                    if (!plain_pos(vv[t])) d_not_plain = 1;
-                }
-                Us[i * BS + (c & 15) * 8 + (c >> 4)] = c > i ? vv[t] : 0.0f;
-            }
-        }
-    }
-    __syncthreads();
+    __shared__ float2 dtab[BS];
+    __shared__ int d_not_plain;
+#include "gptq_block_body.h"
+}
 
-    const int lane = tid & 63;
-    const int p = lane & 15;
-    const int64_t row = ((int64_t)blockIdx.x * (NT / 64) + (tid >> 6)) * 4 + (lane >> 4);
-    const bool active = row < a.R;
-    const int64_t rr = active ? row : a.R - 1;
+// ---------------------------------------------------------------------------------------------------------
+// The in-block kernel with RIDERS: one grid, two roles chosen by blockIdx, no data shared between them inside a launch.
+//   chain role  (blockIdx < nchain): exactly k_gptq_block<VARIANT, 512> on group g + 1's block (its columns, ErrBuf[(g+1) % 3]);
+//   rider role  (the rest): ONE queued 128 x 128 tile of group g's far update (columns beyond group g + 1, ErrBuf[g % 3], read-only
+//                rows of U), two of its four 128-k phases, on the workgroup's first four waves — exactly k_sgemm_wide<2>'s tile
+//                (sgemm_wide_tile.h): one accumulator per element and phase, ascending k from +0 on v_mfma_f32_32x32x2_f32, one
+//                rounding C - acc per phase, the C tile in registers over the launch's phases. The other four waves end at once
+//                (a barrier counts the surviving waves only).
+// A launch is as long as its longest workgroup, and the chain role takes 24-28 us. Measured on down_proj's chain alone (profiles/
+// NOTES.md, chain riders): two whole tiles per CU share its MFMA pipes and take 64-70 us (the launch: 69 us); one whole tile 37-39 us
+// (launch 39 us); one tile's two phases 26-27 us (launch 27 us) — hence one tile per CU, cut along k into RIDER_PASSES slices of
+// whole phases that different launches carry: the C tile goes to memory and comes back in between (fp32: exact), per element the
+// same chain. 72 KiB of LDS, the chain role uses the first 66 KiB. The chain workgroups have the lowest indices: they are
+// dispatched first, the riders take the CUs the chain leaves free (the host sizes the grid: one tile per free CU). Workgroup b
+// runs on XCD b % 8: where the counts allow, an XCD's riders are `per` = tm / 8 consecutive tile rows of every tile column of the
+// launch (`per` A panels and the launch's few B panels in that XCD's L2).
+struct RiderArgs {
+    wide::WideArgs w;     // this launch's slice of the previous group's far update: whole tile columns, whole phases
+    int nchain;           // chain-role workgroups
+    int per;              // tile rows per XCD (nchain % 8 == 0, tm % 8 == 0), or 0: tiles in column-major order
+};
+static constexpr int RIDER_LDS = wide::Wide<2>::LDS;     // 73728
+static constexpr int RIDER_PASSES = 2;                    // k slices of a rider tile (divides GRP = 4 phases and the 4 carrying launches)
 
-    if (VARIANT != 0 && !d_not_plain) {
-        const bool done = block_fast<VARIANT == 1, VARIANT == 1 ? BS : VARIANT>(a, Us, dtab, p, row, active);
-        if (done) return;
+template <int VARIANT>
+__global__ __launch_bounds__(GBT) void k_gptq_block_riders(GptqBlockArgs a, RiderArgs r) {
+    extern __shared__ __attribute__((aligned(16))) char smem_r[];
+    if ((int)blockIdx.x < r.nchain) {
+        constexpr int NT = GBT;
+        float* Us = reinterpret_cast<float*>(smem_r);
+        float* dg = Us + BS * BS;
+        float2* dtab = reinterpret_cast<float2*>(dg + BS);
+        int& d_not_plain = *reinterpret_cast<int*>(dtab + BS);
+#include "gptq_block_body.h"
+        return;
     }
-
-    float w[8], w0[8], er[8], ls[8], sc[8], zr[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int c = p + 16 * e;
-        w[e] = (c < a.count) ? a.W[rr * a.K + a.i1 + c] : 0.0f;
-        w0[e] = w[e];
-        er[e] = 0.0f;
-        ls[e] = 0.0f;
-        sc[e] = 1.0f;
-        zr[e] = 0.0f;
-        if (a.static_mode && c < a.count) {
-            const int g = a.col_group ? a.col_group[a.i1 + c] : (a.i1 + c) / a.col_gsz;
-            sc[e] = a.scales[rr * a.ng + g];
-            zr[e] = a.zeros ? a.zeros[rr * a.ng + g] : 0.0f;
-        }
+    if (threadIdx.x >= 256) return;
+    const int rw = (int)blockIdx.x - r.nchain;
+    int ti = rw % r.w.tm, tj = rw / r.w.tm;
+    if (r.per) {
+        const int q = rw >> 3;
+        ti = (rw & 7) * r.per + q % r.per;
+        tj = q / r.per;
     }
-    float s_cur = 1.0f, z_cur = 0.0f;
-    float s_grp[8], z_grp[8];  // dynamic mode: qparams captured at each 16-column boundary (group starts)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        s_grp[e] = 0.0f;
-        z_grp[e] = 0.0f;
-    }
-    const float* us = Us + p * 8;
-
-#define LLMC_CHUNK(E)                                                             \
-    gptq_steps16<16 * E>(w, w0, er, ls, sc, zr, us, dg, p, s_cur, z_cur, a);  \
-    s_grp[E] = s_cur;                                                             \
-    z_grp[E] = z_cur;
-    LLMC_CHUNK(0) LLMC_CHUNK(1) LLMC_CHUNK(2) LLMC_CHUNK(3) LLMC_CHUNK(4) LLMC_CHUNK(5) LLMC_CHUNK(6) LLMC_CHUNK(7)
-#undef LLMC_CHUNK
-
-    if (!active) return;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int c = p + 16 * e;
-        if (c < a.count) {
-            a.Wout[row * a.K + a.i1 + c] = w[e];
-            if (a.losses) a.losses[row * a.K + a.i1 + c] = ls[e];
-        }
-        a.Err[a.err_kmajor ? (int64_t)c * a.err_ld + row : (int64_t)row * a.err_ld + c] = (c < a.count) ? er[e] : 0.0f;
-    }
-    if (!a.static_mode && p == 0) {
-        // qparams of the groups that start in this block (gsz divides 128, multiple of 16)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int i = 16 * e;
-            if (i < a.count && (i % a.gsz) == 0) {
-                const int g = (a.i1 + i) / a.gsz;
-                a.scales[row * a.ng + g] = s_grp[e];
-                if (a.zeros) a.zeros[row * a.ng + g] = z_grp[e];
-            }
-        }
-    }
+    wide::wide_tile<2>(r.w, ti, tj, smem_r, (int)threadIdx.x);
 }
 
 }  // namespace llmc
@@ -459,10 +407,28 @@ struct MseSearch {
     float norm;
 };
 
+// The launches of one call in issue order, for tests (llmc_test_gptq_rider_plan): with a recorder the loop below launches
+// nothing and touches no device. A record is PLAN_W int32: kind, group, the columns it writes [w0, w1), the err buffer it reads /
+// writes (-1: none), and for an in-block launch with riders their group, columns [r0, r1) and err buffer; last the k range
+// [k0, k1) of the group's 512 err columns that the riders or a flush apply (0, 0: all of them).
+enum { PLAN_BLOCK = 0, PLAN_NEAR = 1, PLAN_NEAR_FAR = 2, PLAN_FAR = 3, PLAN_FLUSH = 4, PLAN_W = 12 };
+struct PlanRec {
+    int32_t* out;
+    int cap, n;
+    void add(int kind, int group, int64_t w0, int64_t w1, int err_rd, int err_wr, int rgroup = -1, int64_t r0 = 0, int64_t r1 = 0,
+             int rerr = -1, int k0 = 0, int k1 = 0) {
+        if (n < cap) {
+            const int32_t v[PLAN_W] = {kind, group, (int32_t)w0, (int32_t)w1, err_rd, err_wr, rgroup, (int32_t)r0, (int32_t)r1, rerr, k0, k1};
+            memcpy(out + (size_t)n * PLAN_W, v, sizeof(v));
+        }
+        ++n;
+    }
+};
+
 static int gptq_cols_impl(float* W, const float* Hinv, int64_t R, int64_t K, int64_t n_quant, int sym, float qmin,
                           float qmax, int64_t group_size, int static_groups, const int32_t* col_group, float* scales,
                           float* zeros, float* Wout, float* losses, int blocksize, void* ws, llmc_stream_t stream,
-                          const MseSearch* mse);
+                          const MseSearch* mse, PlanRec* rec = nullptr);
 
 extern "C" int llmc_gptq_quantize_cols(float* W, const float* Hinv, int64_t R, int64_t K, int64_t n_quant, int sym,
                                        float qmin, float qmax, int64_t group_size, int static_groups,
@@ -491,7 +457,7 @@ extern "C" int llmc_gptq_quantize_mse(float* W, const float* Hinv, int64_t R, in
 static int gptq_cols_impl(float* W, const float* Hinv, int64_t R, int64_t K, int64_t n_quant, int sym, float qmin,
                           float qmax, int64_t group_size, int static_groups, const int32_t* col_group, float* scales,
                           float* zeros, float* Wout, float* losses, int blocksize, void* ws, llmc_stream_t stream,
-                          const MseSearch* mse) {
+                          const MseSearch* mse, PlanRec* rec) {
     LLMC_REQUIRE(W && Hinv && Wout && scales && ws && R > 0 && K > 0, "gptq_quantize: null/empty argument");
     LLMC_REQUIRE(n_quant > 0 && n_quant <= K, "gptq_quantize: n_quant must be in (0, K]");
     const int64_t NQ = n_quant;
@@ -528,9 +494,101 @@ static int gptq_cols_impl(float* W, const float* Hinv, int64_t R, int64_t K, int
     // every group's far update, so the chain stood still while ~430 us of fp32 far update drained. Per element the updates
     // still arrive in the reference's order (block 0, 1, 2, ...: bulk stream order, then the chain behind C1), from the
     // same kernels on the same tile grid: bit-identical to one stream (llmc_hip_set_helper_streams(0)), which tests compare.
-    PipeStreams* ps = (!helper_streams_enabled()) ? nullptr : pipe_streams_for(caller);
+    PipeStreams* ps = (!helper_streams_enabled() || rec) ? nullptr : pipe_streams_for(caller);
     const bool merge_far = !opt(OPT_K4_SPLIT_FAR);
+    // Riders (one stream only; option no_riders: off, today's one launch over [gend, K)). The LAST columns of group g's far update,
+    // [p0, K) with p0 = max(gend2, K - 2 * rider_cols * 128), are not part of its launch: their 128 x 128 tiles are queued here and
+    // ride on the four in-block launches of group g + 1 (k_gptq_block_riders), whose chain role leaves CUs free — `rider_cols`
+    // tile columns per launch = one tile per free CU, half of a tile's k per launch: launches 1, 2 carry phases 0-1 of the two
+    // column ranges, launches 3, 4 phases 2-3. The launch behind group g covers [gend, p0): always the next group's columns,
+    // which the chain needs next. Group g + 1's launches write columns < gend2 <= p0 and ErrBuf[(g+1) % 3] only; its own far launch
+    // comes after its four blocks, its own riders later still: every element receives block 0, 1, 2, ...'s updates in that order
+    // from the same per-element arithmetic — bit-identical, which tests compare (tests/test_riders_*.py; the plan below is
+    // replayed there). OWQ's last group updates [n_quant, K) per block: what is queued is FLUSHED as plain launches before its
+    // first block. Where the chain role fills the chip (R >= 8192 on 256 CUs; 1024-thread workgroups from R = 16384) nothing is
+    // free and the schedule is today's. No flag, no atomic, no second stream: a launch's two roles never meet.
+    const int nt_all = R >= 16384 ? 1024 : GBT;
+    const int grid_all = (int)ceil_div64(R, nt_all / 16);
+    int rider_cols = 0;
+    if (!ps && merge_far && !opt(OPT_NO_RIDERS) && ekm && nt_all == GBT && R % 128 == 0 && K % 128 == 0 && NQ > (int64_t)BS * GRP &&
+        K > 2 * (int64_t)BS * GRP) {
+        SgemmArgs h{};      // the first group's far-far product: every later one has the same strides and alignment
+        h.A = ErrBuf[0]; h.lda = err_ld; h.B = Hinv + 2 * BS * GRP; h.ldb = K; h.C = W + 2 * BS * GRP; h.ldc = K;
+        h.M = h.M_last = (int)R; h.N = h.N_last = (int)(K - 2 * BS * GRP); h.Kd = h.Kd_last = BS * GRP;
+        h.epilogue = SG_SUB; h.batch = 1; h.phase_len = BS;
+        const int free_cus = device_cu_count() - grid_all;
+        // measured where the chain role takes at least half the CUs (R = 4096, 6144 on 256): below that nearly the whole far update
+        // would ride and the launch behind a group shrink to the next group's columns, a form that lost when it was measured
+        if (sgemm_wide_form(h, true, false) == 2 && free_cus > 0 && 2 * grid_all >= device_cu_count()) rider_cols = (int)(free_cus / (R / 128));
+    }
     hipStream_t st = ps ? pipe_chain_stream(ps, caller) : caller;
+    // the queue: slices of ONE group's far update, each a column range and a k range (whole 128-k phases) — worked off in order
+    struct Slice { int64_t c0, c1; int k0, k1; };
+    constexpr int CARRIERS = GRP;      // in-block launches of a whole group
+    static_assert(CARRIERS % RIDER_PASSES == 0 && GRP % RIDER_PASSES == 0, "a group's carrying launches and phases divide into the passes");
+    struct { int n, next, group; int64_t g0; float* Err; Slice s[CARRIERS]; } pend = {0, 0, 0, 0, nullptr, {}};
+    auto far_args = [&](float* Err, int64_t g0, int64_t c0, int64_t c1, int k0 = 0, int k1 = BS * GRP) {
+        SgemmArgs h{};
+        h.A = Err + (size_t)k0 * Rp; h.lda = err_ld; h.B = Hinv + (g0 + k0) * K + c0; h.ldb = K; h.C = W + c0; h.ldc = K;
+        h.M = h.M_last = (int)R; h.N = h.N_last = (int)(c1 - c0); h.Kd = h.Kd_last = k1 - k0;
+        h.epilogue = SG_SUB; h.batch = 1; h.phase_len = BS;
+        return h;
+    };
+    // One place that either launches or, for the plan recorder, writes down what WOULD be launched — read back from the very
+    // arguments the kernel gets (columns from C, k range from B's row, err buffer from A), not from the loop's own bookkeeping.
+    const size_t err_buf_elems = (size_t)Rp * ELD;
+    auto err_index = [&](const float* pe) { return (int)((size_t)(pe - (const float*)ws) / err_buf_elems); };
+    auto k_range = [&](int group, const float* B, int64_t c0, int kd, int* k0, int* k1) {
+        *k0 = (int)((B - Hinv - c0) / K - (int64_t)group * BS * GRP);
+        *k1 = *k0 + kd;
+        if (*k1 - *k0 == BS * GRP) *k0 = *k1 = 0;      // all of the group's err columns
+    };
+    auto product = [&](int kind, int group, const SgemmArgs& g, hipStream_t s) -> int {
+        if (!rec) return sgemm_launch(g, ekm, false, s);
+        const int64_t c0 = g.C - W;
+        int k0 = 0, k1 = 0;
+        if (kind != PLAN_NEAR) k_range(group, g.B, c0, g.Kd, &k0, &k1);
+        rec->add(kind, group, c0, c0 + g.N, err_index(g.A), -1, -1, 0, 0, -1, k0, k1);
+        return LLMC_OK;
+    };
+    auto in_block = [&](int group, const GptqBlockArgs& a, int variant, int nt, int grid, const RiderArgs* ra, int nr) -> int {
+        if (rec) {
+            if (ra) {
+                const int64_t r0 = ra->w.C - W;
+                int k0 = 0, k1 = 0;
+                k_range(pend.group, ra->w.B, r0, ra->w.nst * wide::W_K, &k0, &k1);
+                rec->add(PLAN_BLOCK, group, a.i1, a.i1 + a.count, -1, err_index(a.Err), pend.group, r0, r0 + (int64_t)ra->w.tn * 128,
+                         err_index(ra->w.A), k0, k1);
+            } else {
+                rec->add(PLAN_BLOCK, group, a.i1, a.i1 + a.count, -1, err_index(a.Err));
+            }
+            return LLMC_OK;
+        }
+        switch (variant) {
+#define LLMC_GB(V)                                                                                            \
+    case V:                                                                                                   \
+        if (ra) {                                                                                             \
+            if (int rc = ensure_dynamic_lds((const void*)k_gptq_block_riders<V>, RIDER_LDS)) return rc;       \
+            hipLaunchKernelGGL((k_gptq_block_riders<V>), dim3(grid + nr), dim3(GBT), RIDER_LDS, st, a, *ra); \
+        } else if (nt == 1024) {                                                                              \
+            hipLaunchKernelGGL((k_gptq_block<V, 1024>), dim3(grid), dim3(1024), 0, st, a);              \
+        } else {                                                                                              \
+            hipLaunchKernelGGL((k_gptq_block<V, GBT>), dim3(grid), dim3(GBT), 0, st, a);                \
+        }                                                                                                     \
+        break;
+            LLMC_GB(0) LLMC_GB(1) LLMC_GB(128)
+#undef LLMC_GB
+        }
+        LLMC_LAUNCH_CHECK();
+        return LLMC_OK;
+    };
+    auto flush = [&]() -> int {
+        for (; pend.next < pend.n; ++pend.next) {
+            const Slice& q = pend.s[pend.next];
+            if (int rc = product(PLAN_FLUSH, pend.group, far_args(pend.Err, pend.g0, q.c0, q.c1, q.k0, q.k1), caller)) return rc;
+        }
+        return LLMC_OK;
+    };
     hipStream_t bulk = ps ? ps->bulk : st;
     if (ps) {
         hipEvent_t e0 = nullptr;
@@ -554,6 +612,10 @@ static int gptq_cols_impl(float* W, const float* Hinv, int64_t R, int64_t K, int
         // never-visited columns beyond n_quant (their group-wide phased update could start on a ragged phase)
         const int64_t near_end = gend == NQ ? K : gend;
         float* Err = ErrBuf[gidx % 3];
+        if (near_end > gend) {      // riders: this group's per-block updates reach [n_quant, K), which the queued tiles also write
+            int rc = flush();
+            if (rc) return rc;
+        }
         if (ps && near_end > gend) {
             // OWQ's last group: its per-block updates reach the never-visited columns [n_quant, K), which the earlier
             // groups' far-far updates on the bulk stream also write (nothing else orders the two when
@@ -576,28 +638,30 @@ static int gptq_cols_impl(float* W, const float* Hinv, int64_t R, int64_t K, int
             a.static_mode = static_mode; a.sym = sym; a.qmin = qmin; a.qmax = qmax;
             // 64 KB of LDS per workgroup = 2 workgroups per CU: tall weights use 1024-thread workgroups so that the
             // whole grid is resident at once (R = 28672: 448 workgroups on 512 slots instead of 896)
-            const int nt = R >= 16384 ? 1024 : GBT;
-            const int grid = (int)ceil_div64(R, nt / 16);
+            const int nt = nt_all;
+            const int grid = grid_all;
             // group sizes 16/32/64 with qparams taken mid-block stay on the generic path (their fast variants
             // spill: the qparams change inside the unrolled loop)
             const int variant = (count != BS || force_generic) ? 0 : static_mode ? 1 : gsz == BS ? BS : 0;
-            if (mse) {
+            if (mse && !rec) {
                 // every group starting in [i1, i1 + count) from the block-start panel (gsz divides 128, so groups start
                 // at i1 + k * gsz; the last one is clipped at n_quant like the reference's min(i + g, columns - n_out))
                 int rc = llmc_mse_qparams_panel(W, R, K, i1, count, gsz, sym, mse->round_zp, qmin, qmax, mse->nsteps,
                                                 mse->grid, mse->norm, scales, zeros, ng, i1 / gsz, (llmc_stream_t)st);
                 if (rc) return rc;
             }
-            switch (variant) {
-#define LLMC_GB(V)                                                                                   \
-    case V:                                                                                          \
-        if (nt == 1024) hipLaunchKernelGGL((k_gptq_block<V, 1024>), dim3(grid), dim3(1024), 0, st, a); \
-        else hipLaunchKernelGGL((k_gptq_block<V, GBT>), dim3(grid), dim3(GBT), 0, st, a);             \
-        break;
-                LLMC_GB(0) LLMC_GB(1) LLMC_GB(128)
-#undef LLMC_GB
+            // riders: the next slice of the queue
+            if (pend.next < pend.n) {
+                const Slice q = pend.s[pend.next++];
+                const int tm = (int)(R / 128), nr = (int)((q.c1 - q.c0) / 128) * tm;
+                RiderArgs ra{};
+                wide::wide_operands<2>(far_args(pend.Err, pend.g0, q.c0, q.c1, q.k0, q.k1), ra.w);
+                ra.nchain = grid;
+                ra.per = (grid % 8 == 0 && tm % 8 == 0) ? tm / 8 : 0;
+                if (int rc = in_block(gidx, a, variant, nt, grid, &ra, nr)) return rc;
+            } else {
+                if (int rc = in_block(gidx, a, variant, nt, grid, nullptr, 0)) return rc;
             }
-            LLMC_LAUNCH_CHECK();
             const int64_t i2 = i1 + count;
             if (i2 < near_end) {   // near columns of the group
                 // the GEMM wants 16-B aligned operands: a ragged n_quant (OWQ) starts up to 3 columns early, on
@@ -609,7 +673,7 @@ static int gptq_cols_impl(float* W, const float* Hinv, int64_t R, int64_t K, int
                 g.C = W + c0; g.ldc = K;
                 g.M = g.M_last = (int)R; g.N = g.N_last = (int)(near_end - c0); g.Kd = g.Kd_last = count;
                 g.epilogue = SG_SUB; g.batch = 1;
-                int rc = sgemm_launch(g, ekm, false, st);
+                int rc = product(PLAN_NEAR, gidx, g, st);
                 if (rc) return rc;
             }
         }
@@ -631,11 +695,23 @@ static int gptq_cols_impl(float* W, const float* Hinv, int64_t R, int64_t K, int
             // every kernel the GEMM may pick computes an element the same way (one accumulator per phase from +0 in ascending k,
             // then one rounding C - acc): same bits, two launches less per group and no half-empty 128-workgroup grids.
             const bool one_far = !ps && merge_far;
-            if (one_far) g.N = g.N_last = (int)(K - gend);
-            int rc = sgemm_launch(g, ekm, false, st);
+            // riders: the last columns of this update wait for the next group's four in-block launches, RIDER_PASSES slices of
+            // rider_cols tile columns for each of the CARRIERS / RIDER_PASSES column ranges (at most CARRIERS slices)
+            const int64_t rspan = (int64_t)(CARRIERS / RIDER_PASSES) * rider_cols * 128;
+            const int64_t p0 = (one_far && rider_cols > 0 && gend2 < K) ? (gend2 > K - rspan ? gend2 : K - rspan) : K;
+            if (one_far) g.N = g.N_last = (int)(p0 - gend);
+            int rc = flush();       // (nothing is left by now: four launches carry at most what was queued)
+            if (rc) return rc;
+            rc = product(one_far ? PLAN_FAR : PLAN_NEAR_FAR, gidx, g, st);
             if (rc) return rc;
             C1_prev = nullptr;
-            if (gend2 < K && !one_far) {
+            if (p0 < K) {
+                pend.n = pend.next = 0; pend.group = gidx; pend.g0 = g0; pend.Err = Err;
+                const int kd = BS * GRP / RIDER_PASSES;
+                for (int pass = 0; pass < RIDER_PASSES; ++pass)       // a column's k ranges in ascending order
+                    for (int64_t c = p0; c < K; c += (int64_t)rider_cols * 128)
+                        pend.s[pend.n++] = Slice{c, c + (int64_t)rider_cols * 128 < K ? c + (int64_t)rider_cols * 128 : K, pass * kd, (pass + 1) * kd};
+            } else if (gend2 < K && !one_far) {
                 if (ps) {
                     hipEvent_t e = nullptr;       // this group's err columns are complete on the chain
                     if ((rc = ps->record(st, &e))) return rc;
@@ -648,20 +724,21 @@ static int gptq_cols_impl(float* W, const float* Hinv, int64_t R, int64_t K, int
                 h.B = Hinv + g0 * K + gend2;
                 h.C = W + gend2;
                 h.N = h.N_last = (int)(gend3 - gend2);
-                if ((rc = sgemm_launch(h, ekm, false, bulk))) return rc;
+                if ((rc = product(PLAN_FAR, gidx, h, bulk))) return rc;
                 if (ps && (rc = ps->record(bulk, &C1_prev))) return rc;
                 if (gend3 < K) {
                     SgemmArgs h2 = g;
                     h2.B = Hinv + g0 * K + gend3;
                     h2.C = W + gend3;
                     h2.N = h2.N_last = (int)(K - gend3);
-                    if ((rc = sgemm_launch(h2, ekm, false, bulk))) return rc;
+                    if ((rc = product(PLAN_FAR, gidx, h2, bulk))) return rc;
                 }
                 if (ps && (rc = ps->record(bulk, &C2_hist[gidx % 3]))) return rc;
                 bulk_tail = C2_hist[gidx % 3];
             }
         }
     }
+    if (int rc = flush()) return rc;
     if (ps) {
         hipEvent_t e = nullptr;
         int rc = ps->record(bulk, &e);
@@ -673,4 +750,19 @@ static int gptq_cols_impl(float* W, const float* Hinv, int64_t R, int64_t K, int
         }
     }
     return LLMC_OK;
+}
+
+// Test hook (include/llmc_hip_test.h): the launch plan of the one-stream column loop for these shapes under the calling thread's
+// options, without a device.
+extern "C" int llmc_test_gptq_rider_plan(int64_t R, int64_t K, int64_t n_quant, int64_t group_size, int static_groups,
+                                         int32_t* out, int cap) {
+    LLMC_REQUIRE(out && cap >= 0, "gptq_rider_plan: null output");
+    PlanRec rec{out, cap, 0};
+    // addresses that are only ever offset and compared, never read: 256-B aligned like device allocations, far apart
+    float* const base = (float*)(uintptr_t)((uint64_t)1 << 40);
+    const size_t span = (size_t)1 << 36;
+    int32_t* cg = (int32_t*)(base + 6 * span);
+    int rc = gptq_cols_impl(base, base + span, R, K, n_quant, 0, 0.0f, 15.0f, group_size, static_groups, cg, base + 2 * span,
+                            base + 3 * span, base + 4 * span, nullptr, BS, base + 5 * span, nullptr, nullptr, &rec);
+    return rc ? rc : rec.n;
 }

@@ -47,6 +47,8 @@ int sgemm_launch(const SgemmArgs& a, bool TA, bool TB, hipStream_t st);
 // sgemm_wide.hip: same chain, same bits as sgemm_launch's other kernels
 bool sgemm_wide_eligible(const SgemmArgs& a, bool TA, bool TB);
 int sgemm_wide_launch(const SgemmArgs& a, hipStream_t st);
+// the form sgemm_wide_launch would run: 0 = not eligible, 2 = 128 x 128 tiles (two workgroups per CU), 4 = 256 x 128
+int sgemm_wide_form(const SgemmArgs& a, bool TA, bool TB);
 
 // C -= A^T B (A [Kd x M], B [Kd x N], both k-major) on the 16-bit MFMA pipe with three bf16 terms per fp32 operand
 // (gemm3.hip): fp32-level accuracy, NOT the bitwise fma chain above — K3 only.

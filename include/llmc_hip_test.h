@@ -40,6 +40,13 @@ int llmc_test_gemm3s_stamps(long long* host_out);
  * Returns the number of records (only the first `cap` are written) or an error. */
 int llmc_test_gptq_rider_plan(int64_t R, int64_t K, int64_t n_quant, int64_t group_size, int static_groups, int32_t* out,
                               int cap);
+/* tests/test_gptq_pipe_plan.py: the same for the helper-stream schedule, whatever llmc_hip_set_helper_streams says. Records of 13
+ * int32: the 12 fields above and the lane the launch is issued on (0 chain = the caller's stream, 1 bulk). Between them event
+ * rows in issue order: kind 5 (record) or 6 (wait), the event's id (from 1, each recorded once) in the second field, the lane
+ * that records or waits in the last. Lanes run in order; a wait puts what follows it on its lane behind everything the recording
+ * lane had issued before the record. Pure host call. */
+int llmc_test_gptq_pipe_plan(int64_t R, int64_t K, int64_t n_quant, int64_t group_size, int static_groups, int32_t* out,
+                             int cap);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,6 @@
 #include "quant_math.h"
 #include "sgemm.h"
 #include "sgemm_wide_tile.h"
-#include "side_stream.h"
 #include "pipe_streams.h"
 
 namespace llmc {
@@ -143,15 +142,6 @@ __device__ __forceinline__ bool plain_num(float x) {
     const uint32_t b = __float_as_uint(x);
     return ((b & 0x7fffffffu) - 0x2B800000u) < 0x28000000u || b == 0u;
 }
-// n / d for plain d > 0 with y = rcp_refined(d) and n a plain numerator: the tail of hipcc's division sequence
-__device__ __forceinline__ float div_plain(float n, float d, float y) {
-    const float q0 = n * y;
-    const float e1 = fmaf(-d, q0, n);
-    const float q1 = fmaf(e1, y, q0);
-    const float e2 = fmaf(-d, q1, n);
-    return fmaf(e2, y, q1);
-}
-
 // One step. (u, dd) were loaded during the previous step; this step loads (un, ddn) for the next one first.
 template <int I, bool STATIC>
 __device__ __forceinline__ void fast_step(float (&w)[8], float (&er)[8], float (&df)[8], const float (&sc)[8],
@@ -174,13 +164,13 @@ __device__ __forceinline__ void fast_step(float (&w)[8], float (&er)[8], float (
         y = row_bcast<PO>(ys[EO]);
     }
     const float wi = row_bcast<PO>(w[EO]);
-    float t = div_plain(wi, s, y);                  // quant_code(): x / s
+    float t = div_tail(wi, s, y);                   // quant_code(): x / s; plain s > 0, y = rcp_refined(s), wi a plain numerator
     t = rintf(t);
     t = t + z;
     const float qc = fminf(fmaxf(t, qmin), qmax);
     const float q = (qc - z) * s;                   // dequant_code()
     const float diff = wi - q;
-    const float err = div_plain(diff, dd.x, dd.y);
+    const float err = div_tail(diff, dd.x, dd.y);
     const bool own = p == PO;
     er[EO] = own ? err : er[EO];
     df[EO] = own ? diff : df[EO];
@@ -379,10 +369,11 @@ __global__ __launch_bounds__(GBT) void k_gptq_block_riders(GptqBlockArgs a, Ride
 using namespace llmc;
 
 static constexpr int GRP = 4;  // 128-column blocks per outer group (far updates are applied once per group; 8 measured the same: 12.4 vs 12.6 ms)
+static constexpr int GW = BS * GRP;   // columns of an outer group = err columns of one err buffer
 
 extern "C" size_t llmc_gptq_quantize_ws_bytes(int64_t R, int64_t K) {
     if (R <= 0 || K <= 0) return 0;
-    return 3 * (size_t)((R + 3) & ~(int64_t)3) * BS * GRP * sizeof(float);   // err columns of three groups in flight (pipelined far updates)
+    return 3 * (size_t)((R + 3) & ~(int64_t)3) * GW * sizeof(float);   // err columns of three groups in flight (pipelined far updates)
 }
 
 extern "C" int llmc_gptq_quantize(float* W, const float* Hinv, int64_t R, int64_t K, int sym, float qmin,
@@ -400,35 +391,325 @@ extern "C" int llmc_gptq_quantize(float* W, const float* Hinv, int64_t R, int64_
 // calib_algo = 'mse' with dynamic groups: the searched qparams of every group that starts in a block (gptq.py:216-221 ->
 // get_mse_range). The reference searches W[:, i:i+g], which inside a block still holds the values the block started
 // with, so each block's groups are searched on the running panel right before its in-block kernel, on the same stream.
-struct MseSearch {
-    int round_zp;
-    int nsteps;
-    int grid;
-    float norm;
+struct MseSearch { int round_zp, nsteps, grid; float norm; };
+
+#define LLMC_TRY(expr) do { if (int _rc = (expr)) return _rc; } while (0)
+
+// The host schedule (how it came about: DESIGN.md §3 "K4's host schedule"). Every weight receives the blocks' updates in the
+// reference's order (block 0, 1, 2, ...), each as "W -= chain over the block's 128 k" (gptq.py:244): columns of the current outer
+// group right after each block (near product), columns beyond it once per group (far product: GRP phases of 128 k, the C tile in
+// registers), cut into PIECES on lanes. Column tiles are independent and every kernel that may run a piece computes an element the
+// same way (one accumulator per phase from +0 in ascending k, one rounding C - acc): any cut on any lane gives the same bits as
+// long as per element the updates arrive in block order — which the waits in gptq_cols_impl state and tests replay from the plans.
+enum Lane {
+    CHAIN = 0,   // in-block kernel and near product per block, per group the far piece the next group needs. The caller's stream
+    BULK = 1,    // far pieces beyond the next group: a helper stream (pipe_streams.h), or without helper streams the chain stream
+    CALLER = 2,  // the caller's stream where the chain is not (NULL-stream caller with CU-masked helpers: pipe_chain_stream)
+    RIDE = 3     // no stream: on the in-block launches of the NEXT group (k_gptq_block_riders), one slice per launch
+};
+struct Piece { int64_t c0, c1; int k0, k1; Lane lane; };    // columns [c0, c1), the group's err columns [k0, k1) (whole 128-k phases)
+static constexpr int CARRIERS = GRP;      // in-block launches of a whole group
+static_assert(CARRIERS % RIDER_PASSES == 0 && GRP % RIDER_PASSES == 0, "a group's carrying launches and phases divide into the passes");
+
+// The far update [gend, K) of a group that ends at gend, in issue order.
+//   merged (one stream, default): [gend, p0) on the chain and the tail [p0, K), p0 = max(gend2, K - 2 * rider_cols * 128), as RIDE
+//     slices: per pass (ascending k) rider_cols tile columns per carrying launch, half a tile's k per launch. rider_cols = 0: p0 = K.
+//   split (helper streams, or option k4_split_far on one stream): the next group's columns on the chain, then on the bulk lane the
+//     columns of the group after next FIRST (all that the next group's own far update waits for), then the rest.
+static int far_pieces(int64_t gend, int64_t K, bool merged, int rider_cols, Piece* p) {
+    const int64_t gend2 = gend + GW < K ? gend + GW : K, gend3 = gend2 + GW < K ? gend2 + GW : K;
+    if (!merged) {
+        p[0] = Piece{gend, gend2, 0, GW, CHAIN}, p[1] = Piece{gend2, gend3, 0, GW, BULK}, p[2] = Piece{gend3, K, 0, GW, BULK};
+        return 1 + (gend2 < K) + (gend3 < K);
+    }
+    const int64_t rw = (int64_t)rider_cols * 128, rspan = (CARRIERS / RIDER_PASSES) * rw;
+    const int64_t p0 = (rider_cols > 0 && gend2 < K) ? (gend2 > K - rspan ? gend2 : K - rspan) : K;
+    p[0] = Piece{gend, p0, 0, GW, CHAIN};
+    int n = 1;
+    const int kd = GW / RIDER_PASSES;
+    for (int pass = 0; pass < RIDER_PASSES; ++pass)
+        for (int64_t c = p0; c < K; c += rw) p[n++] = Piece{c, c + rw < K ? c + rw : K, pass * kd, (pass + 1) * kd, RIDE};
+    return n;
+}
+
+// What every launch's arguments are made from: the call's pointers, dims, err layout and qparam mode. The three builders are the
+// only pointer arithmetic of the loop.
+struct ColCall {
+    float* W; const float* U; float* Wout; float* losses; float* scales; float* zeros; const int32_t* col_group;
+    int64_t R, K, NQ;
+    // err columns of three groups in flight, K-MAJOR [GRP * 128][Rp] (16-B LDS writes when the GEMMs stage them as A; option
+    // k4_err_rowmajor: [R][512], same bits)
+    bool ekm; int64_t Rp, err_ld; float* ErrBuf[3];
+    int ng, gsz, static_mode, sym; float qmin, qmax;
+    const MseSearch* mse;
+
+    float* err(int group, int64_t k) const { return ErrBuf[group % 3] + (ekm ? k * Rp : k); }     // err column k of the group
+    int64_t group_end(int64_t g0) const { return g0 + GW < NQ ? g0 + GW : NQ; }
+    // columns updated right after every block: up to the end of the outer group; in the LAST group also the never-visited columns
+    // beyond n_quant (their group-wide phased update could start on a ragged phase)
+    int64_t near_end(int64_t g0) const { return group_end(g0) == NQ ? K : group_end(g0); }
+    int count(int64_t i1) const { return (int)(NQ - i1 < BS ? NQ - i1 : BS); }
+
+    GptqBlockArgs block(int64_t i1) const {
+        GptqBlockArgs a;
+        a.W = W; a.U = U; a.Wout = Wout; a.losses = losses;
+        a.Err = err((int)(i1 / GW), i1 % GW); a.err_ld = (int)err_ld; a.err_kmajor = ekm ? 1 : 0;
+        // mse: qparams searched per block into scales / zeros, then read like static groups in processing order
+        a.scales = scales; a.zeros = zeros; a.col_group = mse ? nullptr : col_group; a.col_gsz = mse ? gsz : 1 << 30;
+        a.R = R; a.K = (int)K; a.i1 = (int)i1; a.count = count(i1); a.ng = ng; a.gsz = static_mode ? BS : gsz;
+        a.static_mode = static_mode; a.sym = sym; a.qmin = qmin; a.qmax = qmax;
+        return a;
+    }
+    // W[:, c0:c1] -= Err[:, k rows] @ U[row0 : row0 + kd, c0:c1]
+    SgemmArgs product(const float* A, int64_t row0, int kd, int64_t c0, int64_t c1, int phase_len) const {
+        SgemmArgs g{};
+        g.A = A; g.lda = err_ld; g.B = U + row0 * K + c0; g.ldb = K; g.C = W + c0; g.ldc = K;
+        g.M = g.M_last = (int)R; g.N = g.N_last = (int)(c1 - c0); g.Kd = g.Kd_last = kd;
+        g.epilogue = SG_SUB; g.batch = 1; g.phase_len = phase_len;
+        return g;
+    }
+    // block i1's update of the rest of its group's columns. The GEMM wants 16-B aligned operands: a ragged n_quant (OWQ) starts
+    // up to 3 columns early, on columns the loop has already visited — W is dead there (their values live in Wout)
+    SgemmArgs near(int64_t i1) const {
+        const int64_t g0 = i1 - i1 % GW, c0 = (i1 + count(i1)) & ~(int64_t)3;
+        return product(err((int)(i1 / GW), i1 % GW), i1, count(i1), c0, near_end(g0), 0);
+    }
+    SgemmArgs far(int group, int64_t c0, int64_t c1, int k0, int k1) const {
+        return product(err(group, k0), (int64_t)group * GW + k0, k1 - k0, c0, c1, BS);
+    }
+    RiderArgs riders(int group, const Piece& q, int nchain) const {
+        RiderArgs ra{};
+        wide::wide_operands<2>(far(group, q.c0, q.c1, q.k0, q.k1), ra.w);
+        ra.nchain = nchain; ra.per = (nchain % 8 == 0 && ra.w.tm % 8 == 0) ? ra.w.tm / 8 : 0;
+        return ra;
+    }
 };
 
-// The launches of one call in issue order, for tests (llmc_test_gptq_rider_plan): with a recorder the loop below launches
-// nothing and touches no device. A record is PLAN_W int32: kind, group, the columns it writes [w0, w1), the err buffer it reads /
-// writes (-1: none), and for an in-block launch with riders their group, columns [r0, r1) and err buffer; last the k range
-// [k0, k1) of the group's 512 err columns that the riders or a flush apply (0, 0: all of them).
-enum { PLAN_BLOCK = 0, PLAN_NEAR = 1, PLAN_NEAR_FAR = 2, PLAN_FAR = 3, PLAN_FLUSH = 4, PLAN_W = 12 };
+// The launches of one call in issue order, for tests: with a recorder the loop launches nothing and touches no device. The records
+// are laid out as include/llmc_hip_test.h says: PLAN_W int32 for the one-stream plan, one more (the lane) for the pipelined plan,
+// which also has event rows (the event's id where a launch has its group).
+enum { PLAN_BLOCK = 0, PLAN_NEAR = 1, PLAN_NEAR_FAR = 2, PLAN_FAR = 3, PLAN_FLUSH = 4, PLAN_RECORD = 5, PLAN_WAIT = 6, PLAN_W = 12 };
 struct PlanRec {
-    int32_t* out;
-    int cap, n;
-    void add(int kind, int group, int64_t w0, int64_t w1, int err_rd, int err_wr, int rgroup = -1, int64_t r0 = 0, int64_t r1 = 0,
-             int rerr = -1, int k0 = 0, int k1 = 0) {
+    int32_t* out; int cap, n, width;      // width: PLAN_W, or PLAN_W + 1 with lanes and events
+    void add(int lane, int kind, int group, int64_t w0 = 0, int64_t w1 = 0, int err_rd = -1, int err_wr = -1, int rgroup = -1,
+             int64_t r0 = 0, int64_t r1 = 0, int rerr = -1, int k0 = 0, int k1 = 0) {
         if (n < cap) {
-            const int32_t v[PLAN_W] = {kind, group, (int32_t)w0, (int32_t)w1, err_rd, err_wr, rgroup, (int32_t)r0, (int32_t)r1, rerr, k0, k1};
-            memcpy(out + (size_t)n * PLAN_W, v, sizeof(v));
+            const int32_t v[PLAN_W + 1] = {kind, group, (int32_t)w0, (int32_t)w1, err_rd, err_wr, rgroup, (int32_t)r0, (int32_t)r1, rerr, k0, k1, lane};
+            memcpy(out + (size_t)n * width, v, (size_t)width * sizeof(int32_t));
         }
         ++n;
     }
 };
 
+// The chain and bulk streams of a call, and the events between them. Three forms: real helper streams (PipeStreams); one stream,
+// where both lanes are the caller's stream and record / wait do nothing; the pipelined plan, where an event is an integer id that
+// is written down. Either way the column loop states its dependencies once.
+struct Ev { hipEvent_t h; int id; };      // {}: nothing to wait for
+struct Lanes {
+    hipStream_t s[3];
+    PipeStreams* ps = nullptr; PlanRec* plan = nullptr; int ids = 0;
+    Lanes(hipStream_t st, PlanRec* rec) : s{st, st, st} {
+        if (rec && rec->width > PLAN_W) {
+            plan = rec;
+            s[BULK] = (hipStream_t)(uintptr_t)1;     // only ever compared (lane_of): a recorder launches nothing
+        } else if (!rec && helper_streams_enabled() && (ps = pipe_streams_for(st))) {
+            s[CHAIN] = pipe_chain_stream(ps, st);
+            s[BULK] = ps->bulk;
+        }
+    }
+    bool piped() const { return s[BULK] != s[CHAIN]; }
+    int lane_of(hipStream_t st) const { return st == s[CHAIN] ? CHAIN : BULK; }
+    int record(Lane l, Ev* e) {
+        if (ps) return ps->record(s[l], &e->h);
+        if (plan) plan->add(lane_of(s[l]), PLAN_RECORD, e->id = ++ids);
+        return LLMC_OK;
+    }
+    int wait(Lane l, const Ev& e) {
+        if (ps) return pipe_wait(s[l], e.h);
+        if (plan && e.id) plan->add(lane_of(s[l]), PLAN_WAIT, e.id);
+        return LLMC_OK;
+    }
+    int order(Lane first, Lane then) {      // what `then` issues from here on comes after everything `first` has issued
+        Ev e{};
+        LLMC_TRY(record(first, &e));
+        return wait(then, e);
+    }
+    // Both lanes start behind the caller's earlier work, and everything is fenced back into the caller's stream before the entry
+    // point returns: the C ABI contract (complete, in stream order, on the stream passed in)
+    int fork() {
+        Ev e{};
+        LLMC_TRY(record(CALLER, &e));
+        if (s[CHAIN] != s[CALLER]) LLMC_TRY(wait(CHAIN, e));
+        return wait(BULK, e);
+    }
+    int join() {
+        LLMC_TRY(order(BULK, CHAIN));
+        return s[CHAIN] == s[CALLER] ? LLMC_OK : order(CHAIN, CALLER);
+    }
+};
+
+// One place that either launches or, for a plan, writes down what WOULD be launched — read back from the very arguments the
+// kernel gets (columns from C, k range from B's row, err buffer from A, lane from the stream), not from the loop's own bookkeeping.
+struct Sink {
+    const ColCall& o; const Lanes& ln; PlanRec* rec;
+    int err_index(const float* pe) const { return (int)((size_t)(pe - o.ErrBuf[0]) / ((size_t)o.Rp * GW)); }
+    void k_range(int group, const float* B, int64_t c0, int kd, int* k0, int* k1) const {
+        *k0 = (int)((B - o.U - c0) / o.K - (int64_t)group * GW);
+        *k1 = *k0 + kd;
+        if (kd == GW) *k0 = *k1 = 0;      // all of the group's err columns
+    }
+    int product(int kind, int group, const SgemmArgs& g, hipStream_t st) const {
+        if (!rec) return sgemm_launch(g, o.ekm, false, st);
+        const int64_t c0 = g.C - o.W;
+        int k0 = 0, k1 = 0;
+        if (kind != PLAN_NEAR) k_range(group, g.B, c0, g.Kd, &k0, &k1);
+        rec->add(ln.lane_of(st), kind, group, c0, c0 + g.N, err_index(g.A), -1, -1, 0, 0, -1, k0, k1);
+        return LLMC_OK;
+    }
+    // the in-block kernel of block a.i1 on the chain, with the rider tiles `ra` of group `rgroup` if any
+    int in_block(int group, const GptqBlockArgs& a, int variant, int nt, int grid, const RiderArgs* ra, int rgroup) const {
+        const hipStream_t st = ln.s[CHAIN];
+        if (rec) {
+            int64_t r0 = 0, r1 = 0;
+            int rerr = -1, k0 = 0, k1 = 0;
+            if (ra) {
+                r0 = ra->w.C - o.W, r1 = r0 + (int64_t)ra->w.tn * 128, rerr = err_index(ra->w.A);
+                k_range(rgroup, ra->w.B, r0, ra->w.nst * wide::W_K, &k0, &k1);
+            }
+            rec->add(CHAIN, PLAN_BLOCK, group, a.i1, a.i1 + a.count, -1, err_index(a.Err), rgroup, r0, r1, rerr, k0, k1);
+            return LLMC_OK;
+        }
+        switch (variant) {
+#define LLMC_GB(V)                                                                                                          \
+    case V:                                                                                                                 \
+        if (ra) {                                                                                                           \
+            LLMC_TRY(ensure_dynamic_lds((const void*)k_gptq_block_riders<V>, RIDER_LDS));                                   \
+            hipLaunchKernelGGL((k_gptq_block_riders<V>), dim3(grid + ra->w.tm * ra->w.tn), dim3(GBT), RIDER_LDS, st, a, *ra); \
+        } else if (nt == 1024) {                                                                                            \
+            hipLaunchKernelGGL((k_gptq_block<V, 1024>), dim3(grid), dim3(1024), 0, st, a);                                  \
+        } else {                                                                                                            \
+            hipLaunchKernelGGL((k_gptq_block<V, GBT>), dim3(grid), dim3(GBT), 0, st, a);                                    \
+        }                                                                                                                   \
+        break;
+            LLMC_GB(0) LLMC_GB(1) LLMC_GB(128)
+#undef LLMC_GB
+        }
+        LLMC_LAUNCH_CHECK();
+        return LLMC_OK;
+    }
+};
+
+// Tile columns of a far update that one in-block launch carries as riders: one 128 x 128 tile per CU the chain role leaves free.
+// 0: nothing rides — split schedule, shapes off whole tiles or with fewer than three groups, a chain role that fills the chip (R >=
+// 8192 on 256 CUs; 1024-thread workgroups) or takes less than half of it (nearly the whole far update would ride: measured, lost).
+static int rider_quota(const ColCall& o, bool merged, int nt, int grid) {
+    if (!merged || opt(OPT_NO_RIDERS) || !o.ekm || nt != GBT || o.R % 128 || o.K % 128 || o.NQ <= GW || o.K <= 2 * (int64_t)GW) return 0;
+    const int free_cus = device_cu_count() - grid;
+    // the first group's far-far product: every later one has the same strides and alignment
+    if (sgemm_wide_form(o.far(0, 2 * GW, o.K, 0, GW), true, false) != 2 || free_cus <= 0 || 2 * grid < device_cu_count()) return 0;
+    return (int)(free_cus / (o.R / 128));
+}
+
 static int gptq_cols_impl(float* W, const float* Hinv, int64_t R, int64_t K, int64_t n_quant, int sym, float qmin,
                           float qmax, int64_t group_size, int static_groups, const int32_t* col_group, float* scales,
                           float* zeros, float* Wout, float* losses, int blocksize, void* ws, llmc_stream_t stream,
-                          const MseSearch* mse, PlanRec* rec = nullptr);
+                          const MseSearch* mse, PlanRec* rec = nullptr) {
+    LLMC_REQUIRE(W && Hinv && Wout && scales && ws && R > 0 && K > 0, "gptq_quantize: null/empty argument");
+    LLMC_REQUIRE(n_quant > 0 && n_quant <= K, "gptq_quantize: n_quant must be in (0, K]");
+    LLMC_REQUIRE(blocksize == BS, "gptq_quantize: blocksize must be 128");
+    LLMC_REQUIRE(K % 4 == 0 && K < (1 << 30), "gptq_quantize: K must be a multiple of 4");
+    LLMC_REQUIRE(sym || zeros, "gptq_quantize: zeros required for asymmetric");
+    const bool per_channel = group_size <= 0;
+    const int static_mode = static_groups || per_channel || mse != nullptr;
+    const int gsz = (int)group_size;
+    if (!static_mode || mse) {
+        if (!(gsz == 16 || gsz == 32 || gsz == 64 || gsz == 128)) {
+            set_last_error_msg("gptq_quantize: dynamic group qparams need group_size in {16,32,64,128}");
+            return LLMC_ENOTSUP;
+        }
+    } else if (!per_channel) {
+        LLMC_REQUIRE(col_group != nullptr, "gptq_quantize: col_group required with static groups");
+    }
+    const bool ekm = !opt(OPT_K4_ERR_ROWMAJOR);
+    const int64_t Rp = (R + 3) & ~(int64_t)3;
+    const ColCall o{W, Hinv, Wout, losses, scales, zeros, per_channel ? nullptr : col_group, R, K, n_quant,
+                    ekm, Rp, ekm ? Rp : GW, {(float*)ws, (float*)ws + (size_t)Rp * GW, (float*)ws + 2 * (size_t)Rp * GW},
+                    per_channel ? 1 : (int)ceil_div64(K, group_size), gsz, static_mode, sym, qmin, qmax, mse};
+    Lanes ln((hipStream_t)stream, rec);
+    const Sink sink{o, ln, rec};
+    const bool merged = !ln.piped() && !opt(OPT_K4_SPLIT_FAR);
+    // 64 KB of LDS per workgroup = 2 workgroups per CU: tall weights use 1024-thread workgroups so that the whole grid is resident
+    // at once (R = 28672: 448 workgroups on 512 slots instead of 896)
+    const int nt = R >= 16384 ? 1024 : GBT;
+    const int grid = (int)ceil_div64(R, nt / 16);
+    const int rider_cols = rider_quota(o, merged, nt, grid);
+    const bool force_generic = opt(OPT_GPTQ_GENERIC) != 0;
+    // The far update of group `fg` in pieces. pc[next .. np) is the rider queue: its RIDE pieces, worked off in order by the next
+    // group's in-block launches; what is still queued when something else is about to write its columns goes out as plain launches.
+    Piece pc[1 + CARRIERS];
+    int np = 0, next = 0, fg = 0;
+    auto flush = [&]() -> int {
+        for (; next < np; ++next)
+            LLMC_TRY(sink.product(PLAN_FLUSH, fg, o.far(fg, pc[next].c0, pc[next].c1, pc[next].k0, pc[next].k1), ln.s[CHAIN]));
+        return LLMC_OK;
+    };
+    Ev reached_next{};     // bulk: the previous group's far update has reached the columns of the group after it
+    Ev err_read[3] = {};   // bulk: the far update that read this err buffer is complete (the buffer may be rewritten)
+    Ev bulk_tail{};        // bulk: behind its most recent launch
+    LLMC_TRY(ln.fork());
+    int g = 0;
+    for (int64_t g0 = 0; g0 < o.NQ; g0 += GW, ++g) {
+        const int64_t gend = o.group_end(g0), near_end = o.near_end(g0);
+        if (near_end > gend) {
+            // OWQ's last group: its per-block updates reach the never-visited columns [n_quant, K), which queued rider tiles and
+            // the earlier groups' pieces on the bulk lane also write (nothing else orders the two when last_group_start + 512 < K)
+            LLMC_TRY(flush());
+            LLMC_TRY(ln.wait(CHAIN, bulk_tail));
+        }
+        // this group's err buffer was read three groups ago (implied today: the wait for reached_next one group back is behind
+        // those pieces on the in-order bulk lane — stated all the same, it is the dependency)
+        LLMC_TRY(ln.wait(CHAIN, err_read[g % 3]));
+        for (int64_t i1 = g0; i1 < gend; i1 += BS) {
+            const GptqBlockArgs a = o.block(i1);
+            // group sizes 16/32/64 with qparams taken mid-block stay on the generic path (their fast variants spill: the qparams
+            // change inside the unrolled loop)
+            const int variant = (a.count != BS || force_generic) ? 0 : static_mode ? 1 : gsz == BS ? BS : 0;
+            if (mse && !rec) {
+                // every group starting in [i1, i1 + count) from the block-start panel (gsz divides 128, so groups start at
+                // i1 + k * gsz; the last one is clipped at n_quant like the reference's min(i + g, columns - n_out))
+                LLMC_TRY(llmc_mse_qparams_panel(W, R, K, i1, a.count, gsz, sym, mse->round_zp, qmin, qmax, mse->nsteps, mse->grid,
+                                                mse->norm, scales, zeros, o.ng, i1 / gsz, (llmc_stream_t)ln.s[CHAIN]));
+            }
+            // riders write columns >= gend2 of the group before and read its err buffer; this group's launches write columns < gend2
+            // and their own err buffer: a launch's two roles never meet
+            const bool ride = next < np;
+            const RiderArgs ra = ride ? o.riders(fg, pc[next++], grid) : RiderArgs{};
+            LLMC_TRY(sink.in_block(g, a, variant, nt, grid, ride ? &ra : nullptr, ride ? fg : -1));
+            if (i1 + a.count < near_end) LLMC_TRY(sink.product(PLAN_NEAR, g, o.near(i1), ln.s[CHAIN]));
+        }
+        if (near_end == K) continue;
+        // the next group's columns were last written by the previous group's first piece on the bulk lane
+        LLMC_TRY(ln.wait(CHAIN, reached_next));
+        reached_next = Ev{};
+        LLMC_TRY(flush());       // (nothing is left by now: four launches carry at most what was queued)
+        np = far_pieces(gend, K, merged, rider_cols, pc);
+        fg = g;
+        int nbulk = 0;
+        for (next = 0; next < np && pc[next].lane != RIDE; ++next) {      // RIDE pieces come last: they stay queued
+            const Piece& p = pc[next];
+            if (p.lane == BULK && nbulk == 0) LLMC_TRY(ln.order(CHAIN, BULK));      // this group's err columns are complete on the chain
+            const int kind = (p.lane == CHAIN && !merged) ? PLAN_NEAR_FAR : PLAN_FAR;
+            LLMC_TRY(sink.product(kind, g, o.far(g, p.c0, p.c1, p.k0, p.k1), ln.s[p.lane]));
+            if (p.lane == BULK && nbulk++ == 0) LLMC_TRY(ln.record(BULK, &reached_next));
+        }
+        if (nbulk) {
+            LLMC_TRY(ln.record(BULK, &err_read[g % 3]));
+            bulk_tail = err_read[g % 3];
+        }
+    }
+    LLMC_TRY(flush());
+    return ln.join();
+}
 
 extern "C" int llmc_gptq_quantize_cols(float* W, const float* Hinv, int64_t R, int64_t K, int64_t n_quant, int sym,
                                        float qmin, float qmax, int64_t group_size, int static_groups,
@@ -454,310 +735,11 @@ extern "C" int llmc_gptq_quantize_mse(float* W, const float* Hinv, int64_t R, in
                           blocksize, ws, stream, &m);
 }
 
-static int gptq_cols_impl(float* W, const float* Hinv, int64_t R, int64_t K, int64_t n_quant, int sym, float qmin,
-                          float qmax, int64_t group_size, int static_groups, const int32_t* col_group, float* scales,
-                          float* zeros, float* Wout, float* losses, int blocksize, void* ws, llmc_stream_t stream,
-                          const MseSearch* mse, PlanRec* rec) {
-    LLMC_REQUIRE(W && Hinv && Wout && scales && ws && R > 0 && K > 0, "gptq_quantize: null/empty argument");
-    LLMC_REQUIRE(n_quant > 0 && n_quant <= K, "gptq_quantize: n_quant must be in (0, K]");
-    const int64_t NQ = n_quant;
-    LLMC_REQUIRE(blocksize == BS, "gptq_quantize: blocksize must be 128");
-    LLMC_REQUIRE(K % 4 == 0 && K < (1 << 30), "gptq_quantize: K must be a multiple of 4");
-    LLMC_REQUIRE(sym || zeros, "gptq_quantize: zeros required for asymmetric");
-    const bool per_channel = group_size <= 0;
-    // mse: qparams searched per block into scales / zeros, then read like static groups in processing order
-    int static_mode = static_groups || per_channel || mse != nullptr;
-    int gsz = (int)group_size;
-    int ng = per_channel ? 1 : (int)ceil_div64(K, group_size);
-    if (!static_mode || mse) {
-        if (!(gsz == 16 || gsz == 32 || gsz == 64 || gsz == 128)) {
-            set_last_error_msg("gptq_quantize: dynamic group qparams need group_size in {16,32,64,128}");
-            return LLMC_ENOTSUP;
-        }
-    } else if (!per_channel) {
-        LLMC_REQUIRE(col_group != nullptr, "gptq_quantize: col_group required with static groups");
-    }
-    hipStream_t caller = (hipStream_t)stream;
-    const int ELD = BS * GRP;
-    // Round 5: the error columns are kept K-MAJOR, [GRP * 128][Rp] — the fp32 GEMMs stage a k-major A panel with 16-B LDS writes,
-    // a row-major one ([R][512]) through four scalar transposing writes per float4 (square 4096: 130 vs 122 TFLOP/s). The in-block
-    // kernel's stores become 16-B segments (four rows of one column); the volume is 2 MB per block. option k4_err_rowmajor: the old
-    // layout (same bits).
-    const bool ekm = !opt(OPT_K4_ERR_ROWMAJOR);
-    const int64_t Rp = (R + 3) & ~(int64_t)3;
-    const int64_t err_ld = ekm ? Rp : ELD;
-    float* ErrBuf[3] = {(float*)ws, (float*)ws + (size_t)Rp * ELD, (float*)ws + 2 * (size_t)Rp * ELD};   // [R, GRP*128] or [GRP*128, Rp], x 3
-    // Round 4 schedule. The caller's stream carries the CHAIN: per 128-column block the in-block kernel and the update of the
-    // rest of its group's columns, per group the update of the NEXT group's columns. The `bulk` helper stream (CU-masked:
-    // pipe_streams.h) carries the update of everything beyond the next group, the columns of the group after next FIRST
-    // (event C1: all the next group's own update waits for), then the rest. Round 3 joined the whole side update before
-    // every group's far update, so the chain stood still while ~430 us of fp32 far update drained. Per element the updates
-    // still arrive in the reference's order (block 0, 1, 2, ...: bulk stream order, then the chain behind C1), from the
-    // same kernels on the same tile grid: bit-identical to one stream (llmc_hip_set_helper_streams(0)), which tests compare.
-    PipeStreams* ps = (!helper_streams_enabled() || rec) ? nullptr : pipe_streams_for(caller);
-    const bool merge_far = !opt(OPT_K4_SPLIT_FAR);
-    // Riders (one stream only; option no_riders: off, today's one launch over [gend, K)). The LAST columns of group g's far update,
-    // [p0, K) with p0 = max(gend2, K - 2 * rider_cols * 128), are not part of its launch: their 128 x 128 tiles are queued here and
-    // ride on the four in-block launches of group g + 1 (k_gptq_block_riders), whose chain role leaves CUs free — `rider_cols`
-    // tile columns per launch = one tile per free CU, half of a tile's k per launch: launches 1, 2 carry phases 0-1 of the two
-    // column ranges, launches 3, 4 phases 2-3. The launch behind group g covers [gend, p0): always the next group's columns,
-    // which the chain needs next. Group g + 1's launches write columns < gend2 <= p0 and ErrBuf[(g+1) % 3] only; its own far launch
-    // comes after its four blocks, its own riders later still: every element receives block 0, 1, 2, ...'s updates in that order
-    // from the same per-element arithmetic — bit-identical, which tests compare (tests/test_riders_*.py; the plan below is
-    // replayed there). OWQ's last group updates [n_quant, K) per block: what is queued is FLUSHED as plain launches before its
-    // first block. Where the chain role fills the chip (R >= 8192 on 256 CUs; 1024-thread workgroups from R = 16384) nothing is
-    // free and the schedule is today's. No flag, no atomic, no second stream: a launch's two roles never meet.
-    const int nt_all = R >= 16384 ? 1024 : GBT;
-    const int grid_all = (int)ceil_div64(R, nt_all / 16);
-    int rider_cols = 0;
-    if (!ps && merge_far && !opt(OPT_NO_RIDERS) && ekm && nt_all == GBT && R % 128 == 0 && K % 128 == 0 && NQ > (int64_t)BS * GRP &&
-        K > 2 * (int64_t)BS * GRP) {
-        SgemmArgs h{};      // the first group's far-far product: every later one has the same strides and alignment
-        h.A = ErrBuf[0]; h.lda = err_ld; h.B = Hinv + 2 * BS * GRP; h.ldb = K; h.C = W + 2 * BS * GRP; h.ldc = K;
-        h.M = h.M_last = (int)R; h.N = h.N_last = (int)(K - 2 * BS * GRP); h.Kd = h.Kd_last = BS * GRP;
-        h.epilogue = SG_SUB; h.batch = 1; h.phase_len = BS;
-        const int free_cus = device_cu_count() - grid_all;
-        // measured where the chain role takes at least half the CUs (R = 4096, 6144 on 256): below that nearly the whole far update
-        // would ride and the launch behind a group shrink to the next group's columns, a form that lost when it was measured
-        if (sgemm_wide_form(h, true, false) == 2 && free_cus > 0 && 2 * grid_all >= device_cu_count()) rider_cols = (int)(free_cus / (R / 128));
-    }
-    hipStream_t st = ps ? pipe_chain_stream(ps, caller) : caller;
-    // the queue: slices of ONE group's far update, each a column range and a k range (whole 128-k phases) — worked off in order
-    struct Slice { int64_t c0, c1; int k0, k1; };
-    constexpr int CARRIERS = GRP;      // in-block launches of a whole group
-    static_assert(CARRIERS % RIDER_PASSES == 0 && GRP % RIDER_PASSES == 0, "a group's carrying launches and phases divide into the passes");
-    struct { int n, next, group; int64_t g0; float* Err; Slice s[CARRIERS]; } pend = {0, 0, 0, 0, nullptr, {}};
-    auto far_args = [&](float* Err, int64_t g0, int64_t c0, int64_t c1, int k0 = 0, int k1 = BS * GRP) {
-        SgemmArgs h{};
-        h.A = Err + (size_t)k0 * Rp; h.lda = err_ld; h.B = Hinv + (g0 + k0) * K + c0; h.ldb = K; h.C = W + c0; h.ldc = K;
-        h.M = h.M_last = (int)R; h.N = h.N_last = (int)(c1 - c0); h.Kd = h.Kd_last = k1 - k0;
-        h.epilogue = SG_SUB; h.batch = 1; h.phase_len = BS;
-        return h;
-    };
-    // One place that either launches or, for the plan recorder, writes down what WOULD be launched — read back from the very
-    // arguments the kernel gets (columns from C, k range from B's row, err buffer from A), not from the loop's own bookkeeping.
-    const size_t err_buf_elems = (size_t)Rp * ELD;
-    auto err_index = [&](const float* pe) { return (int)((size_t)(pe - (const float*)ws) / err_buf_elems); };
-    auto k_range = [&](int group, const float* B, int64_t c0, int kd, int* k0, int* k1) {
-        *k0 = (int)((B - Hinv - c0) / K - (int64_t)group * BS * GRP);
-        *k1 = *k0 + kd;
-        if (*k1 - *k0 == BS * GRP) *k0 = *k1 = 0;      // all of the group's err columns
-    };
-    auto product = [&](int kind, int group, const SgemmArgs& g, hipStream_t s) -> int {
-        if (!rec) return sgemm_launch(g, ekm, false, s);
-        const int64_t c0 = g.C - W;
-        int k0 = 0, k1 = 0;
-        if (kind != PLAN_NEAR) k_range(group, g.B, c0, g.Kd, &k0, &k1);
-        rec->add(kind, group, c0, c0 + g.N, err_index(g.A), -1, -1, 0, 0, -1, k0, k1);
-        return LLMC_OK;
-    };
-    auto in_block = [&](int group, const GptqBlockArgs& a, int variant, int nt, int grid, const RiderArgs* ra, int nr) -> int {
-        if (rec) {
-            if (ra) {
-                const int64_t r0 = ra->w.C - W;
-                int k0 = 0, k1 = 0;
-                k_range(pend.group, ra->w.B, r0, ra->w.nst * wide::W_K, &k0, &k1);
-                rec->add(PLAN_BLOCK, group, a.i1, a.i1 + a.count, -1, err_index(a.Err), pend.group, r0, r0 + (int64_t)ra->w.tn * 128,
-                         err_index(ra->w.A), k0, k1);
-            } else {
-                rec->add(PLAN_BLOCK, group, a.i1, a.i1 + a.count, -1, err_index(a.Err));
-            }
-            return LLMC_OK;
-        }
-        switch (variant) {
-#define LLMC_GB(V)                                                                                            \
-    case V:                                                                                                   \
-        if (ra) {                                                                                             \
-            if (int rc = ensure_dynamic_lds((const void*)k_gptq_block_riders<V>, RIDER_LDS)) return rc;       \
-            hipLaunchKernelGGL((k_gptq_block_riders<V>), dim3(grid + nr), dim3(GBT), RIDER_LDS, st, a, *ra); \
-        } else if (nt == 1024) {                                                                              \
-            hipLaunchKernelGGL((k_gptq_block<V, 1024>), dim3(grid), dim3(1024), 0, st, a);              \
-        } else {                                                                                              \
-            hipLaunchKernelGGL((k_gptq_block<V, GBT>), dim3(grid), dim3(GBT), 0, st, a);                \
-        }                                                                                                     \
-        break;
-            LLMC_GB(0) LLMC_GB(1) LLMC_GB(128)
-#undef LLMC_GB
-        }
-        LLMC_LAUNCH_CHECK();
-        return LLMC_OK;
-    };
-    auto flush = [&]() -> int {
-        for (; pend.next < pend.n; ++pend.next) {
-            const Slice& q = pend.s[pend.next];
-            if (int rc = product(PLAN_FLUSH, pend.group, far_args(pend.Err, pend.g0, q.c0, q.c1, q.k0, q.k1), caller)) return rc;
-        }
-        return LLMC_OK;
-    };
-    hipStream_t bulk = ps ? ps->bulk : st;
-    if (ps) {
-        hipEvent_t e0 = nullptr;
-        int rc = ps->record(caller, &e0);
-        if (rc) return rc;
-        if (st != caller && (rc = pipe_wait(st, e0))) return rc;
-        if ((rc = pipe_wait(bulk, e0))) return rc;
-    }
-    hipEvent_t C1_prev = nullptr;                 // the previous group's far-far update has reached the next group's columns
-    hipEvent_t C2_hist[3] = {nullptr, nullptr, nullptr};   // ... is complete (its err buffer may be rewritten)
-    hipEvent_t bulk_tail = nullptr;               // behind the most recent launch on the bulk stream
-    const int force_generic = opt(OPT_GPTQ_GENERIC) ? 1 : 0;
-    // Every weight receives the blocks' updates in the reference's order (block 0, 1, 2, ...), each as
-    // "W -= chain over the block's 128 k" (gptq.py:244). Columns inside the current outer group get them right
-    // after each block (the next block needs them); columns beyond the group get the group's GRP updates in one
-    // phased GEMM that keeps the C tile in registers — same arithmetic, one pass over the far columns per group.
-    int gidx = 0;
-    for (int64_t g0 = 0; g0 < NQ; g0 += (int64_t)BS * GRP, ++gidx) {
-        const int64_t gend = g0 + (int64_t)BS * GRP < NQ ? g0 + (int64_t)BS * GRP : NQ;
-        // columns updated right after every block: up to the end of the outer group; in the LAST group also the
-        // never-visited columns beyond n_quant (their group-wide phased update could start on a ragged phase)
-        const int64_t near_end = gend == NQ ? K : gend;
-        float* Err = ErrBuf[gidx % 3];
-        if (near_end > gend) {      // riders: this group's per-block updates reach [n_quant, K), which the queued tiles also write
-            int rc = flush();
-            if (rc) return rc;
-        }
-        if (ps && near_end > gend) {
-            // OWQ's last group: its per-block updates reach the never-visited columns [n_quant, K), which the earlier
-            // groups' far-far updates on the bulk stream also write (nothing else orders the two when
-            // last_group_start + 512 < K). Everything queued on the bulk stream so far has to land first.
-            int rc = pipe_wait(st, bulk_tail);
-            if (rc) return rc;
-        }
-        if (ps && C2_hist[gidx % 3]) {            // the far-far update that read this err buffer three groups ago
-            int rc = pipe_wait(st, C2_hist[gidx % 3]);
-            if (rc) return rc;
-        }
-        for (int64_t i1 = g0; i1 < gend; i1 += BS) {
-            const int count = (int)(NQ - i1 < BS ? NQ - i1 : BS);
-            GptqBlockArgs a;
-            a.W = W; a.U = Hinv; a.Wout = Wout; a.losses = losses;
-            a.Err = Err + (ekm ? (i1 - g0) * Rp : (i1 - g0)); a.err_ld = (int)err_ld; a.err_kmajor = ekm ? 1 : 0;
-            a.scales = scales; a.zeros = zeros; a.col_group = (per_channel || mse) ? nullptr : col_group;
-            a.col_gsz = mse ? gsz : 1 << 30;
-            a.R = R; a.K = (int)K; a.i1 = (int)i1; a.count = count; a.ng = ng; a.gsz = static_mode ? BS : gsz;
-            a.static_mode = static_mode; a.sym = sym; a.qmin = qmin; a.qmax = qmax;
-            // 64 KB of LDS per workgroup = 2 workgroups per CU: tall weights use 1024-thread workgroups so that the
-            // whole grid is resident at once (R = 28672: 448 workgroups on 512 slots instead of 896)
-            const int nt = nt_all;
-            const int grid = grid_all;
-            // group sizes 16/32/64 with qparams taken mid-block stay on the generic path (their fast variants
-            // spill: the qparams change inside the unrolled loop)
-            const int variant = (count != BS || force_generic) ? 0 : static_mode ? 1 : gsz == BS ? BS : 0;
-            if (mse && !rec) {
-                // every group starting in [i1, i1 + count) from the block-start panel (gsz divides 128, so groups start
-                // at i1 + k * gsz; the last one is clipped at n_quant like the reference's min(i + g, columns - n_out))
-                int rc = llmc_mse_qparams_panel(W, R, K, i1, count, gsz, sym, mse->round_zp, qmin, qmax, mse->nsteps,
-                                                mse->grid, mse->norm, scales, zeros, ng, i1 / gsz, (llmc_stream_t)st);
-                if (rc) return rc;
-            }
-            // riders: the next slice of the queue
-            if (pend.next < pend.n) {
-                const Slice q = pend.s[pend.next++];
-                const int tm = (int)(R / 128), nr = (int)((q.c1 - q.c0) / 128) * tm;
-                RiderArgs ra{};
-                wide::wide_operands<2>(far_args(pend.Err, pend.g0, q.c0, q.c1, q.k0, q.k1), ra.w);
-                ra.nchain = grid;
-                ra.per = (grid % 8 == 0 && tm % 8 == 0) ? tm / 8 : 0;
-                if (int rc = in_block(gidx, a, variant, nt, grid, &ra, nr)) return rc;
-            } else {
-                if (int rc = in_block(gidx, a, variant, nt, grid, nullptr, 0)) return rc;
-            }
-            const int64_t i2 = i1 + count;
-            if (i2 < near_end) {   // near columns of the group
-                // the GEMM wants 16-B aligned operands: a ragged n_quant (OWQ) starts up to 3 columns early, on
-                // columns the loop has already visited — W is dead there (their values live in Wout)
-                const int64_t c0 = i2 & ~(int64_t)3;
-                SgemmArgs g{};
-                g.A = Err + (ekm ? (i1 - g0) * Rp : (i1 - g0)); g.lda = err_ld;
-                g.B = Hinv + i1 * K + c0; g.ldb = K;
-                g.C = W + c0; g.ldc = K;
-                g.M = g.M_last = (int)R; g.N = g.N_last = (int)(near_end - c0); g.Kd = g.Kd_last = count;
-                g.epilogue = SG_SUB; g.batch = 1;
-                int rc = product(PLAN_NEAR, gidx, g, st);
-                if (rc) return rc;
-            }
-        }
-        if (near_end < K) {    // far columns: GRP phases of 128
-            const int64_t gend2 = gend + (int64_t)BS * GRP < K ? gend + (int64_t)BS * GRP : K;
-            // the next group's columns were last written by the previous group's far-far update (its first part)
-            if (ps) {
-                int rc = pipe_wait(st, C1_prev);
-                if (rc) return rc;
-            }
-            SgemmArgs g{};
-            g.A = Err; g.lda = err_ld;
-            g.B = Hinv + g0 * K + gend; g.ldb = K;
-            g.C = W + gend; g.ldc = K;
-            g.M = g.M_last = (int)R; g.N = g.N_last = (int)(gend2 - gend); g.Kd = g.Kd_last = (int)(gend - g0);
-            g.epilogue = SG_SUB; g.batch = 1; g.phase_len = BS;
-            // Without helper streams the three column ranges of the group's far update (the next group's columns, the group
-            // after next, the rest) are one product on one stream: ONE launch over [gend, K). Column tiles are independent and
-            // every kernel the GEMM may pick computes an element the same way (one accumulator per phase from +0 in ascending k,
-            // then one rounding C - acc): same bits, two launches less per group and no half-empty 128-workgroup grids.
-            const bool one_far = !ps && merge_far;
-            // riders: the last columns of this update wait for the next group's four in-block launches, RIDER_PASSES slices of
-            // rider_cols tile columns for each of the CARRIERS / RIDER_PASSES column ranges (at most CARRIERS slices)
-            const int64_t rspan = (int64_t)(CARRIERS / RIDER_PASSES) * rider_cols * 128;
-            const int64_t p0 = (one_far && rider_cols > 0 && gend2 < K) ? (gend2 > K - rspan ? gend2 : K - rspan) : K;
-            if (one_far) g.N = g.N_last = (int)(p0 - gend);
-            int rc = flush();       // (nothing is left by now: four launches carry at most what was queued)
-            if (rc) return rc;
-            rc = product(one_far ? PLAN_FAR : PLAN_NEAR_FAR, gidx, g, st);
-            if (rc) return rc;
-            C1_prev = nullptr;
-            if (p0 < K) {
-                pend.n = pend.next = 0; pend.group = gidx; pend.g0 = g0; pend.Err = Err;
-                const int kd = BS * GRP / RIDER_PASSES;
-                for (int pass = 0; pass < RIDER_PASSES; ++pass)       // a column's k ranges in ascending order
-                    for (int64_t c = p0; c < K; c += (int64_t)rider_cols * 128)
-                        pend.s[pend.n++] = Slice{c, c + (int64_t)rider_cols * 128 < K ? c + (int64_t)rider_cols * 128 : K, pass * kd, (pass + 1) * kd};
-            } else if (gend2 < K && !one_far) {
-                if (ps) {
-                    hipEvent_t e = nullptr;       // this group's err columns are complete on the chain
-                    if ((rc = ps->record(st, &e))) return rc;
-                    if ((rc = pipe_wait(bulk, e))) return rc;
-                }
-                // first the columns of the group after next, then the rest (same tiles as one launch: column tiles are
-                // independent and both cuts are multiples of the tile width)
-                const int64_t gend3 = gend2 + (int64_t)BS * GRP < K ? gend2 + (int64_t)BS * GRP : K;
-                SgemmArgs h = g;
-                h.B = Hinv + g0 * K + gend2;
-                h.C = W + gend2;
-                h.N = h.N_last = (int)(gend3 - gend2);
-                if ((rc = product(PLAN_FAR, gidx, h, bulk))) return rc;
-                if (ps && (rc = ps->record(bulk, &C1_prev))) return rc;
-                if (gend3 < K) {
-                    SgemmArgs h2 = g;
-                    h2.B = Hinv + g0 * K + gend3;
-                    h2.C = W + gend3;
-                    h2.N = h2.N_last = (int)(K - gend3);
-                    if ((rc = product(PLAN_FAR, gidx, h2, bulk))) return rc;
-                }
-                if (ps && (rc = ps->record(bulk, &C2_hist[gidx % 3]))) return rc;
-                bulk_tail = C2_hist[gidx % 3];
-            }
-        }
-    }
-    if (int rc = flush()) return rc;
-    if (ps) {
-        hipEvent_t e = nullptr;
-        int rc = ps->record(bulk, &e);
-        if (rc) return rc;
-        if ((rc = pipe_wait(st, e))) return rc;
-        if (st != caller) {
-            if ((rc = ps->record(st, &e))) return rc;
-            if ((rc = pipe_wait(caller, e))) return rc;
-        }
-    }
-    return LLMC_OK;
-}
-
-// Test hook (include/llmc_hip_test.h): the launch plan of the one-stream column loop for these shapes under the calling thread's
-// options, without a device.
-extern "C" int llmc_test_gptq_rider_plan(int64_t R, int64_t K, int64_t n_quant, int64_t group_size, int static_groups,
-                                         int32_t* out, int cap) {
-    LLMC_REQUIRE(out && cap >= 0, "gptq_rider_plan: null output");
-    PlanRec rec{out, cap, 0};
+// Test hooks (include/llmc_hip_test.h): the launch plan of the column loop for these shapes under the calling thread's options,
+// without a device — on one stream (width PLAN_W) or with helper streams (PLAN_W + 1: lanes and events).
+static int gptq_plan(int64_t R, int64_t K, int64_t n_quant, int64_t group_size, int static_groups, int32_t* out, int cap, int width) {
+    LLMC_REQUIRE(out && cap >= 0, "gptq plan: null output");
+    PlanRec rec{out, cap, 0, width};
     // addresses that are only ever offset and compared, never read: 256-B aligned like device allocations, far apart
     float* const base = (float*)(uintptr_t)((uint64_t)1 << 40);
     const size_t span = (size_t)1 << 36;
@@ -765,4 +747,10 @@ extern "C" int llmc_test_gptq_rider_plan(int64_t R, int64_t K, int64_t n_quant, 
     int rc = gptq_cols_impl(base, base + span, R, K, n_quant, 0, 0.0f, 15.0f, group_size, static_groups, cg, base + 2 * span,
                             base + 3 * span, base + 4 * span, nullptr, BS, base + 5 * span, nullptr, nullptr, &rec);
     return rc ? rc : rec.n;
+}
+extern "C" int llmc_test_gptq_rider_plan(int64_t R, int64_t K, int64_t n_quant, int64_t group_size, int static_groups, int32_t* out, int cap) {
+    return gptq_plan(R, K, n_quant, group_size, static_groups, out, cap, PLAN_W);
+}
+extern "C" int llmc_test_gptq_pipe_plan(int64_t R, int64_t K, int64_t n_quant, int64_t group_size, int static_groups, int32_t* out, int cap) {
+    return gptq_plan(R, K, n_quant, group_size, static_groups, out, cap, PLAN_W + 1);
 }

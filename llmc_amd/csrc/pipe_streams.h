@@ -27,7 +27,7 @@
 namespace llmc {
 
 struct PipeStreams {
-    hipStream_t fast = nullptr, bulk = nullptr, inv = nullptr;
+    hipStream_t bulk = nullptr;    // K4's far update beyond the next group
     hipStream_t chain = nullptr;   // stands in for the caller's stream when that is the NULL stream (see pipe_chain_stream)
     static constexpr int NEV = 512;
     hipEvent_t ev[NEV] = {};
@@ -100,15 +100,14 @@ inline PipeStreams* pipe_streams_for(hipStream_t main_st) {
     const bool masked = opt(OPT_SIDE_CU_MASK) != 0;
     p->masked = masked;
     auto fail = [&]() -> PipeStreams* {
-        for (hipStream_t* s : {&p->fast, &p->bulk, &p->inv, &p->chain})
+        for (hipStream_t* s : {&p->bulk, &p->chain})
             if (*s) { (void)hipStreamDestroy(*s); *s = nullptr; }
         for (int i = 0; i < PipeStreams::NEV; ++i)
             if (p->ev[i]) { (void)hipEventDestroy(p->ev[i]); p->ev[i] = nullptr; }
         (void)hipGetLastError();
         return nullptr;
     };
-    if (!pipe_make_stream(&p->fast, masked) || !pipe_make_stream(&p->bulk, masked) || !pipe_make_stream(&p->inv, masked))
-        return fail();
+    if (!pipe_make_stream(&p->bulk, masked)) return fail();
     // NORMAL priority: a high-priority chain stream made everything slower (K3 32.1 ms against 21.9 with the chain on the
     // caller's own normal-priority stream, gpurun_out/r04c/k3_time_q8.txt) — the far updates' waves are evicted for every
     // small chain kernel

@@ -214,6 +214,9 @@ int llmc_pack_awq_gemm(const void* weight, int wdt, const void* scales, int sdt,
  *   bit 9      evaluate every element with the IEEE division and the general encoder. Results are identical with and
  *              without it: 16-bit e4m3 calls otherwise use w * fl(1 / scale) and send only the lanes near a rounding
  *              boundary (or outside the 8-bit format's normal range) through the division (tests/test_fp8_fast_gpu.py).
+ *   bit 11     dynamic scales only: write back the scale as get_qparams forms it (quant.py:545-553) — one that underflows
+ *              in fp16 stays 0 — instead of the value quant() leaves in place (`scales[scales == 0] = 1`, quant.py:1062).
+ *              The elements are quantized with 1 either way. For get_tensor_qparams, which never reaches quant().
  * Codes are OCP e4m3fn / IEEE e5m2 bytes in both cases (every qtorch result is representable). scales [G] in dtype sdt:
  * ATen yields fp32 for the 0-dim per-tensor scale and the tensor dtype for per-channel.
  * static_scales != 0: `scales` is INPUT (fake_quant_act_static / real_quant_weight_static, quant.py:1083-1099). */
@@ -352,6 +355,22 @@ int llmc_gptq_quantize_cols(float* W, const float* Hinv, int64_t R, int64_t K, i
                        float qmax, int64_t group_size, int static_groups, const int32_t* col_group,
                        float* scales, float* zeros, float* Wout, float* losses, int blocksize,
                        void* ws, llmc_stream_t stream);
+/* The same loop (arguments as llmc_gptq_quantize_cols) for a FloatQuantizer weight quantizer with use_qtorch (quant.py:963-1081;
+ * the shipped gptq_fp8.yml): every visited column is rounded to an FP8 grid instead of an integer grid,
+ *   q = float_quantize(w / s + 0, E, M, 'nearest') * s      with s = 1 where s == 0 (quant.py:1062),
+ * fmt 0 = e4m3 (E, M = 4, 3; qtorch saturates at 240), 1 = e5m2 (5, 2; 57344); another fmt returns LLMC_ENOTSUP. The quantizer
+ * is symmetric: there are no zero points.
+ *   W      [R, K] fp32, overwritten with the running updated weights (columns from n_quant on: every block's feedback applied)
+ *   Wout   [R, K] fp32 = `tmp`, losses [R, K] fp32 or NULL: written for the first n_quant columns
+ *   group_size = 0 (per_channel): scales [R] fp32 is INPUT (a 16-bit scale promoted to fp32 is exact);
+ *   static_groups = 1: scales [R, K/group_size] INPUT in original column order, col_group as above;
+ *   static_groups = 0: group_size in {16, 32, 64, 128} (others LLMC_ENOTSUP); scales [R, ceil(K / group_size)] is OUTPUT in
+ *     processing order, s = max(|min|, |max|).clamp(1e-5) / finfo(fmt).max of the group at its start (quant.py:545-553); groups the
+ *     loop never visits (n_quant < K) keep their input values.
+ * ws: llmc_gptq_quantize_ws_bytes(R, K) bytes, 256-B aligned. Runs on `stream`, complete in stream order; allocates nothing. */
+int llmc_gptq_quantize_fp8_cols(float* W, const float* Hinv, int64_t R, int64_t K, int64_t n_quant, int fmt,
+                                int64_t group_size, int static_groups, const int32_t* col_group, float* scales,
+                                float* Wout, float* losses, int blocksize, void* ws, llmc_stream_t stream);
 /* The same loop (n_quant as in llmc_gptq_quantize_cols) with calib_algo 'mse' dynamic groups: the qparams of a group
  * are searched (get_mse_range, as llmc_mse_qparams_panel) on W[:, i : min(i + group_size, n_quant)] as it stands when
  * the 128-column block holding column i begins, the values the reference's search sees (gptq.py:216-221). Once per

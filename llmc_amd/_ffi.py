@@ -73,6 +73,7 @@ SIGNATURES = {
                                   _i32, _vp, _vp]),
     'llmc_gptq_quantize_cols': (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _f32, _f32, _i64, _i32, _vp, _vp, _vp, _vp, _vp,
                                        _i32, _vp, _vp]),
+    'llmc_gptq_quantize_fp8_cols': (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     'llmc_gptq_quantize_mse_ws_bytes': (_sz, [_i64, _i64]),
     'llmc_gptq_quantize_mse': (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _f32, _f32, _i64, _i32, _i32, _i32, _f32, _vp, _vp,
                                       _vp, _vp, _i32, _vp, _vp]),

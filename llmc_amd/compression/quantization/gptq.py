@@ -11,6 +11,11 @@ per-batch all_reduce of H — with several ranks (data-parallel calibration) H i
 (`_sync_hessian`), mathematically identical because every rank's running mean covers the same number of
 sequences; no `.item()` sync per layer. OWQ (gptq.py:44-50, 66-83): the floating-point columns ride through the same
 column loop (`quantize_owq`, llmc_gptq_quantize_cols).
+
+FP8 weight quantizers (`float-quant` e4m3 / e5m2 with use_qtorch: the shipped gptq_fp8.yml): the column loop rounds to the
+FloatQuantizer's grid (llmc_gptq_quantize_fp8_cols) — per_channel, per_group with dynamic or static groups, actorder. Refused
+at construction, with the reason: fp8_semantics='cast', calib_algo mse / hqq, granularity per_block / per_tensor, and OWQ with a
+float quantizer.
 """
 import copy
 import math
@@ -25,6 +30,7 @@ from . import gptq_ops
 from .gptq_pipeline import GptqConfig, owq_permutation, quantize_owq, quantize_stacked
 from .hessian import HessianAccumulator
 from .module_utils import _LLMC_LINEAR_TYPES_, _TRANSFORMERS_LINEAR_TYPES_
+from .quant import FloatQuantizer
 
 
 @ALGO_REGISTRY
@@ -62,6 +68,7 @@ class GPTQ(BaseBlockwiseQuantization):
             self.actorder = False
         mse = None
         wq = self.wquantizer
+        self.fp8 = self._fp8_format(wq, self.owq)
         if wq.calib_algo == 'mse' and not self.static_groups and wq.granularity == 'per_group':
             # dynamic groups: get_mse_range at every group start (gptq.py:216-221), searched once per 128-column block
             # on the block-start weights (llmc_gptq_quantize_mse). static_groups / per_channel take the quantizer's
@@ -80,6 +87,35 @@ class GPTQ(BaseBlockwiseQuantization):
         self.gcfg = GptqConfig(bit=self.wquantizer.bit, symmetric=self.wquantizer.sym, group_size=gs,
                                actorder=self.actorder, static_groups=self.static_groups, percdamp=self.percdamp,
                                blocksize=self.blocksize, mse=mse)
+
+    @staticmethod
+    def _fp8_format(wq, owq=False):
+        """'e4m3' / 'e5m2' for a FloatQuantizer the column loop has a grid for, None for an integer quantizer; what it has no
+        grid for is refused here, at construction, instead of being quantized by some other rule."""
+        if not isinstance(wq, FloatQuantizer):
+            return None
+        if wq.kwargs.get('fp8_semantics', 'qtorch') != 'qtorch':
+            raise NotImplementedError("GPTQ with a float quantizer and fp8_semantics='cast': a compensated weight that rounds "
+                                      'above the largest e4m3fn value is NaN under the dtype cast, and the NaN would enter the '
+                                      "error feedback of every later column; the column loop rounds with qtorch's saturating "
+                                      "float_quantize (fp8_semantics='qtorch', the reference's use_qtorch path)")
+        if wq.calib_algo in ('mse', 'hqq'):
+            raise NotImplementedError(f'GPTQ with a float quantizer and calib_algo={wq.calib_algo}: the searched ranges of the '
+                                      'column loop (llmc_gptq_quantize_mse) are evaluated on the integer grid only; use '
+                                      'calib_algo minmax')
+        if wq.granularity == 'per_block':
+            raise NotImplementedError('GPTQ with a float quantizer and granularity=per_block: the column loop takes one scale per '
+                                      'row (per_channel) or per row and column group (per_group); per_block tiles span rows, '
+                                      'which the row-independent loop does not model')
+        if wq.granularity not in ('per_channel', 'per_group'):
+            raise NotImplementedError(f'GPTQ with a float quantizer and granularity={wq.granularity}: the per-layer qparam '
+                                      'bookkeeping of the column loop (search_layer_qparams, weight_transform) holds one scale per '
+                                      'row, a 0-dim per_tensor scale or per_head scales are not laid out that way (the integer '
+                                      'loop does not take them either); use per_channel or per_group')
+        if owq:
+            raise NotImplementedError('GPTQ with a float quantizer and special.owq: no golden of the reference covers the '
+                                      'combination, so it is not routed to the FP8 column loop')
+        return wq.bit
 
     def _check_mse_rows(self, R):
         """get_mse_range's assertion (quant.py:147-150) on one layer's [R, g] group tensor: mse_b_num must divide R."""
@@ -321,6 +357,8 @@ class GPTQ(BaseBlockwiseQuantization):
         if self.gcfg.static_groups or not self.gcfg.group_size:
             static = []
             for l in layers:   # RTN qparams of the ORIGINAL weights, original column order
+                if self.fp8 is not None:           # quant.py:1062: a zero scale becomes 1, in place, in the layer's buffer
+                    l.buf_scales[l.buf_scales == 0] = 1
                 z = l.buf_zeros if (torch.is_tensor(l.buf_zeros) and l.buf_zeros.dim() > 0) else None
                 static.append((l.buf_scales, z))
         results = quantize_stacked([l.weight.data for l in layers], H, self.gcfg, static_qparams=static)
@@ -451,6 +489,7 @@ class GPTQ(BaseBlockwiseQuantization):
         R, K = W.shape
         n_nonout = int(getattr(self, 'n_nonout', K))
         qmin, qmax = float(wq.qmin), float(wq.qmax)
+        fp8 = self._fp8_format(wq, getattr(self, 'owq', False))
         dynamic = per_group and not self.static_groups
         col_group = scales = zeros = init_s = init_z = None
         if dynamic:
@@ -469,6 +508,12 @@ class GPTQ(BaseBlockwiseQuantization):
             scales = self.qparams['scale'].reshape(R, 1).float()
             if not wq.sym:
                 zeros = self.qparams['zero'].reshape(R, 1).float()
+        if fp8 is not None and not dynamic:
+            # FloatQuantizer.quant's `scales[scales == 0] = 1` (quant.py:1062) acts IN PLACE on the qparams every visited column
+            # reads: per_channel that is layer.buf_scales itself, static groups the entries of self.groups (the kernel reads a
+            # zero scale as 1 either way)
+            for q in (self.groups if per_group else [self.qparams]):
+                q['scale'][q['scale'] == 0] = 1
         if not W.is_contiguous():
             raise ValueError('GPTQ.weight_transform: W must be contiguous (it is updated in place)')
         mse = getattr(getattr(self, 'gcfg', None), 'mse', None) if dynamic else None
@@ -477,7 +522,7 @@ class GPTQ(BaseBlockwiseQuantization):
         t, l, s, z = gptq_ops.gptq_quantize(W, Hinv.contiguous(), wq.sym, qmin, qmax, gs, self.static_groups, col_group, scales,
                                             zeros, want_losses=True, blocksize=self.blocksize,
                                             n_quant=n_nonout if n_nonout < K else None, init_scales=init_s, init_zeros=init_z,
-                                            mse=mse)
+                                            mse=mse, fp8=fp8)
         tmp.copy_(t)
         Losses.copy_(l)
         if dynamic:

@@ -120,15 +120,27 @@ def release_workspaces():
     _chol_ws.clear()
 
 
+FP8_FORMATS = {'e4m3': 0, 'e5m2': 1}      # llmc_gptq_quantize_fp8_cols' fmt
+
+
 def gptq_quantize(W, Hinv, sym, qmin, qmax, group_size, static_groups=False, col_group=None, scales=None,
-                  zeros=None, want_losses=True, blocksize=128, n_quant=None, init_scales=None, init_zeros=None, mse=None):
+                  zeros=None, want_losses=True, blocksize=128, n_quant=None, init_scales=None, init_zeros=None, mse=None,
+                  fp8=None):
     """gptq.py:199-244. W [R,K] fp32 (overwritten with the running weights), Hinv [K,K] fp32 upper.
     Returns (tmp [R,K], losses [R,K] | None, scales [R,ng], zeros [R,ng] | None).
     n_quant < K (OWQ): only the first n_quant columns are quantized, the rest keep receiving the error feedback and
     are left in W; tmp / losses are zero there and dynamic-group qparams of never-visited groups keep
     init_scales / init_zeros (the reference's `self.groups` starts from the layer's RTN qparams, gptq.py:380-395).
     mse = (round_zp, nsteps, grid, norm): calib_algo 'mse' dynamic groups (llmc_gptq_quantize_mse), the qparams of each
-    group searched on the block-start weights; nsteps = int(maxshrink * mse_grid), grid = mse_grid, norm = 2.4."""
+    group searched on the block-start weights; nsteps = int(maxshrink * mse_grid), grid = mse_grid, norm = 2.4.
+    fp8 = 'e4m3' | 'e5m2': a FloatQuantizer grid with qtorch rounding (llmc_gptq_quantize_fp8_cols) instead of the integer grid:
+    sym / qmin / qmax / zeros are not read (the quantizer is symmetric, the grid saturates by itself) and zeros is returned None."""
+    if fp8 is not None:
+        if fp8 not in FP8_FORMATS:
+            raise ValueError(f"gptq_quantize: fp8 must be None, 'e4m3' or 'e5m2', got {fp8!r}")
+        if mse is not None:
+            raise ValueError('gptq_quantize: mse searches integer qparams; there is no FP8 form of it')
+        sym, zeros, init_zeros = True, None, None
     _ffi.require_gpu(W, Hinv)
     L = _ffi.lib()
     R, K = W.shape
@@ -147,11 +159,11 @@ def gptq_quantize(W, Hinv, sym, qmin, qmax, group_size, static_groups=False, col
     else:
         if init_scales is not None:
             scales = init_scales.to(device=dev, dtype=torch.float32).reshape(R, ng).contiguous().clone()
-            zeros = (init_zeros.to(device=dev, dtype=torch.float32).reshape(R, ng).contiguous().clone()
+            zeros = None if fp8 is not None else (init_zeros.to(device=dev, dtype=torch.float32).reshape(R, ng).contiguous().clone()
                      if init_zeros is not None else torch.zeros((R, ng), dtype=torch.float32, device=dev))
         else:
             scales = torch.empty((R, ng), dtype=torch.float32, device=dev)
-            zeros = torch.empty((R, ng), dtype=torch.float32, device=dev)
+            zeros = None if fp8 is not None else torch.empty((R, ng), dtype=torch.float32, device=dev)
     if col_group is not None:
         col_group = col_group.to(device=dev, dtype=torch.int32).contiguous()
     nq = K if n_quant is None else int(n_quant)
@@ -167,6 +179,12 @@ def gptq_quantize(W, Hinv, sym, qmin, qmax, group_size, static_groups=False, col
             _ffi.ptr(losses), int(blocksize), _ffi.ptr(ws), _ffi.stream()), 'llmc_gptq_quantize_mse')
         return tmp, losses, scales, zeros
     ws = _ffi.workspace(L.llmc_gptq_quantize_ws_bytes(R, K), dev)
+    if fp8 is not None:
+        _ffi.check(L.llmc_gptq_quantize_fp8_cols(
+            _ffi.ptr(W), _ffi.ptr(Hinv), R, K, nq, FP8_FORMATS[fp8], int(group_size or 0), int(bool(static_groups)),
+            _ffi.ptr(col_group), _ffi.ptr(scales), _ffi.ptr(tmp), _ffi.ptr(losses), int(blocksize), _ffi.ptr(ws),
+            _ffi.stream()), 'llmc_gptq_quantize_fp8_cols')
+        return tmp, losses, scales, None
     _ffi.check(L.llmc_gptq_quantize_cols(
         _ffi.ptr(W), _ffi.ptr(Hinv), R, K, nq, int(bool(sym)), float(qmin), float(qmax), int(group_size or 0),
         int(bool(static_groups)), _ffi.ptr(col_group), _ffi.ptr(scales), _ffi.ptr(zeros), _ffi.ptr(tmp),

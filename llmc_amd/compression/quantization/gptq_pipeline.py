@@ -17,7 +17,7 @@ from .hessian import HessianAccumulator
 
 @dataclass
 class GptqConfig:
-    bit: int = 4
+    bit: int = 4                   # or 'e4m3' / 'e5m2': a FloatQuantizer grid with qtorch rounding (symmetric, no zero points)
     symmetric: bool = False
     group_size: int = 128          # 0 = per_channel
     actorder: bool = True
@@ -28,8 +28,23 @@ class GptqConfig:
     # (round_zp, nsteps = int(maxshrink * mse_grid), grid = mse_grid, norm = 2.4) as gptq_ops.gptq_quantize takes it
     mse: tuple = None
 
+    def __post_init__(self):
+        if isinstance(self.bit, str):
+            if self.bit not in gptq_ops.FP8_FORMATS:
+                raise NotImplementedError(f"GptqConfig bit={self.bit!r}: the FP8 column loop has the e4m3 and e5m2 grids")
+            if self.mse is not None:
+                raise NotImplementedError('GptqConfig: calib_algo mse searches integer qparams; there is no FP8 form of it')
+            self.symmetric = True
+
+    @property
+    def fp8(self):
+        return self.bit if isinstance(self.bit, str) else None
+
     @property
     def qrange(self):
+        if self.fp8:
+            fmax = 448.0 if self.bit == 'e4m3' else 57344.0      # finfo(float8_e4m3fn / float8_e5m2).max
+            return -fmax, fmax
         if self.symmetric:
             return float(-(2 ** (self.bit - 1))), float(2 ** (self.bit - 1) - 1)
         return 0.0, float(2 ** self.bit - 1)
@@ -115,7 +130,7 @@ def quantize_stacked(W_list, H, cfg, static_qparams=None, h_work=None, want_loss
     tmp, losses, s, z = gptq_ops.gptq_quantize(Wp, U, cfg.symmetric, qmin, qmax, cfg.group_size,
                                                cfg.static_groups, col_group, scales, zeros,
                                                want_losses=want_losses, blocksize=cfg.blocksize,
-                                               mse=None if static_mode else cfg.mse)
+                                               mse=None if static_mode else cfg.mse, fp8=cfg.fp8)
     if perm is not None:
         invperm = _inverse_permutation(perm)
         K4 = tmp.shape[1]
@@ -145,6 +160,8 @@ def quantize_owq(W, H, cfg, n_out, wquantizer, rtn_scales=None, rtn_zeros=None, 
     """GPTQ + OWQ for ONE layer (gptq.py:44-56, 128-196): n_out outlier columns (largest Hessian diagonal) are moved
     last, kept in floating point and only receive the error feedback. Returns a GptqResult whose `weight` already has
     the compensated fp outlier columns in place and is back in the original column order; `n_nonout` rides in `extra`."""
+    if cfg.fp8:
+        raise NotImplementedError('quantize_owq with an FP8 grid: not built (GPTQ refuses special.owq with a float quantizer)')
     _ffi.require_gpu(H, W)
     K = H.shape[0]
     n_nonout = K - int(n_out)

@@ -10,6 +10,8 @@ Also in scope: calib_algo 'learnable' (get_learnable_range, quant.py:205-224: th
 Also in scope: calib_algo 'hqq' on IntegerQuantizer per_group weights with group sizes 16 / 32 / 64 / 128 (get_hqq_qparams,
 optimize_weights_proximal, quant.py:588-610, 680-697: the half-quadratic zero-point solver, llmc_hqq_optimize); the method
 HQQ (hqq.py) runs the same solver. FloatQuantizer refuses hqq: the reference's solver rounds to an integer grid.
+FloatQuantizer under GPTQ: the column loop rounds to the quantizer's own grid (gptq.py, llmc_gptq_quantize_fp8_cols) for
+per_channel and per_group weights with fp8_semantics='qtorch' and calib_algo 'minmax'; GPTQ refuses the rest at construction.
 Out of scope (raise NotImplementedError): W48; calib_algo 'hqq' inside GPTQ's column loop, AWQ's search, AutoClipper and
 SpQR (the algorithms refuse it).
 
@@ -656,7 +658,7 @@ class FloatQuantizer(BaseQuantizer):
         self.qmax = torch.tensor(fmax)
         self.qmin = torch.tensor(-fmax)
 
-    def _run(self, tensor, fake, scales=None):
+    def _run(self, tensor, fake, scales=None, raw_scales=False):
         _ffi.require_gpu(tensor, scales)
         L = _ffi.lib()
         tensor = tensor.contiguous()
@@ -672,7 +674,8 @@ class FloatQuantizer(BaseQuantizer):
             s = torch.empty(G, dtype=sdtype, device=tensor.device)
         out = torch.empty_like(tensor) if fake else torch.empty(tensor.shape, dtype=torch.uint8, device=tensor.device)
         ws = None if static else _ffi.workspace(L.llmc_fp8_quant_ws_bytes(G, g), tensor.device)
-        _ffi.check(L.llmc_fp8_quant(_ffi.ptr(tensor), _ffi.dt(tensor), G, g, int(bool(fake)) | self._mode, _ffi.ptr(out), _ffi.ptr(s),
+        _ffi.check(L.llmc_fp8_quant(_ffi.ptr(tensor), _ffi.dt(tensor), G, g, int(bool(fake)) | self._mode | (0x800 if raw_scales else 0),
+                                    _ffi.ptr(out), _ffi.ptr(s),
                                     _ffi.dt(sdtype), int(static), _ffi.ptr(ws), _ffi.stream()), 'llmc_fp8_quant')
         return out, s.reshape(self._qparam_shape(tensor))
 
@@ -706,7 +709,10 @@ class FloatQuantizer(BaseQuantizer):
                 t[:M, :N] = tensor
             return t.view(mb, b, nb, b), s.view(mb, 1, nb, 1), torch.tensor(0.0), self.qmax, self.qmin
         tensor = self.reshape_tensor(tensor)
-        _, scales = self._run(tensor, True)
+        # get_qparams alone (quant.py:545-553) returns a scale that underflowed as 0 — clamp(1e-5) / qmax is below fp16's
+        # smallest subnormal — and only quant() turns it into 1, in place (quant.py:1062). Callers that keep these qparams
+        # (collect_block_qparams -> buf_scales, GPTQ's static groups) must see what the reference hands them.
+        _, scales = self._run(tensor, True, raw_scales=True)
         return tensor, scales, torch.tensor(0.0), self.qmax, self.qmin
 
     # ---- static arithmetic with given scales (quant.py:1061-1081) ----------------------------------------------------
@@ -765,7 +771,8 @@ class FloatQuantizer(BaseQuantizer):
             bits, s = self._run_block(weight, False, scales=args['scales'])
             return bits.view(torch.float8_e4m3fn), s, None
         bits, scales = self._run(self.reshape_tensor(weight), False, scales=args['scales'])
-        return self._finish(bits, scales, weight.shape)
+        # quant.py:1062: the scales the reference returns have been through `scales[scales == 0] = 1`
+        return self._finish(bits, torch.where(scales == 0, torch.ones_like(scales), scales), weight.shape)
 
     def __repr__(self):
         return (f'FloatQuantizer(bit={self.bit},e_bits={self.e_bits}, m_bits={self.m_bits},'

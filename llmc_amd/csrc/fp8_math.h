@@ -112,6 +112,25 @@ __device__ __forceinline__ float qtorch_e4m3_select(float x) {
     return a < 0x3c800000u ? d : n;
 }
 
+// qtorch_quantize<E, M> without control flow for a FINITE x, any (E, M) with 8-bit storage: qtorch_e4m3_select's two ranges with
+// the format's constants and no NaN test — the caller proves finiteness (GPTQ's fast in-block step: a quotient of plain operands,
+// gptq_loop.hip). Normal range: ties away on the bits, the saturation as a clamp to +-max (the next representable magnitude is
+// 2^(max_exp + 1): nothing lies between); below 2^min_exp: fl32(|x| + 2^min_exp), ties away at the subnormal spacing on the sum's
+// bits, shifted back, sign restored, a zero result is +0. e4m3: max 240, min_exp -6; e5m2: max 57344, min_exp -14.
+template <int E, int M> __device__ __forceinline__ float qtorch_select_finite(float x) {
+    constexpr int min_exp = -((1 << (E - 1)) - 2);
+    constexpr uint32_t half = 1u << (22 - M), keep = ~((1u << (23 - M)) - 1u);
+    constexpr uint32_t lo_bits = (uint32_t)(127 + min_exp) << 23;                                       // 2^min_exp
+    constexpr uint32_t max_bits = ((uint32_t)((1 << (E - 1)) - 1 + 127) << 23) | (((1u << M) - 1u) << (23 - M));
+    const float lo = __uint_as_float(lo_bits), mx = __uint_as_float(max_bits);
+    const uint32_t u = __float_as_uint(x), a = u & 0x7fffffffu;
+    const float n = __builtin_amdgcn_fmed3f(__uint_as_float((u + half) & keep), -mx, mx);
+    const float va = opaque_f32(__uint_as_float(a) + lo);
+    const float r = __uint_as_float((__float_as_uint(va) + half) & keep) - lo;
+    const float d = __uint_as_float(__float_as_uint(r) | (u & 0x80000000u)) + 0.0f;
+    return a < lo_bits ? d : n;
+}
+
 // One element of a FloatQuantizer cast. fmt: 0 = e4m3, 1 = e5m2. sem: 0 = the dtype cast of torch (float8_e4m3fn /
 // float8_e5m2: round to nearest even), 1 = qtorch.float_quantize. Returns the code; *val receives the decoded value.
 __device__ __forceinline__ uint8_t fp8_encode(float t, int fmt, int sem, float* val) {

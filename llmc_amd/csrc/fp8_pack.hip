@@ -30,6 +30,7 @@ static constexpr int FB = 256;
 // mode: bit 0 fake (write dequantized values), bits 4-5 format (0 e4m3, 1 e5m2), bit 8 semantics (0 torch's dtype cast,
 // 1 qtorch.float_quantize: fp8_math.h)
 static constexpr int FP8_FAKE = 1, FP8_FMT_SHIFT = 4, FP8_QTORCH = 0x100;
+static constexpr int FP8_RAW_SCALES = 0x800;     // dynamic scales: the scale written back is get_qparams' own (an underflowed one stays 0)
 static constexpr int FP8_NO_PACKED16 = 0x400;    // A/B: the float form of the division-free path (round 4) instead of the packed 16-bit one
 template <typename T>
 __device__ __forceinline__ void fp8_one(float w, float s, int tdt, int mode, int DT, T* of, uint8_t* ob) {
@@ -255,8 +256,10 @@ __global__ __launch_bounds__(FB) void k_fp8_cast(const T* __restrict__ W, const 
                     s = load_as_f32(scales, row, sdt);
                 } else {
                     s = rnd(to_f32<T>(amax[row]) / fmax, sdt);
-                    if (s == 0.0f) s = 1.0f;                          // scales[scales == 0] = 1 IN PLACE (quant.py:1062): the returned scale too
-                    if (i * V == row * g) store_from_f32(scales, row, sdt, s);
+                    // scales[scales == 0] = 1 IN PLACE (quant.py:1062): the returned scale too, unless the caller asked for
+                    // get_qparams' own value (FP8_RAW_SCALES: get_tensor_qparams alone never reaches quant())
+                    if (i * V == row * g) store_from_f32(scales, row, sdt, (s == 0.0f && !(mode & FP8_RAW_SCALES)) ? 1.0f : s);
+                    if (s == 0.0f) s = 1.0f;
                 }
                 return s == 0.0f ? 1.0f : s;                          // (static scales: the caller's tensor is left alone)
             };
@@ -318,7 +321,7 @@ __global__ __launch_bounds__(FB) void k_fp8_cast(const T* __restrict__ W, const 
                     }
                     T of[2];
                     uint8_t ob[2];
-                    fp8_two<T>(w0, w1, s, tdt, mode & ~(FP8_EXACT_DIV | FP8_NO_PACKED16), of, ob);
+                    fp8_two<T>(w0, w1, s, tdt, mode & ~(FP8_EXACT_DIV | FP8_NO_PACKED16 | FP8_RAW_SCALES), of, ob);
                     const int64_t e = i * V + 2 * pr;
                     if (fake) {
                         ((T*)out)[e] = of[0];
@@ -339,13 +342,12 @@ __global__ __launch_bounds__(FB) void k_fp8_cast(const T* __restrict__ W, const 
             s = load_as_f32(scales, row, sdt);
         } else {
             s = rnd(to_f32<T>(amax[row]) / fmax, sdt);
-            if (s == 0.0f) s = 1.0f;
-            if (i == row * g) store_from_f32(scales, row, sdt, s);
+            if (i == row * g) store_from_f32(scales, row, sdt, (s == 0.0f && !(mode & FP8_RAW_SCALES)) ? 1.0f : s);
         }
         if (s == 0.0f) s = 1.0f;
         T of;
         uint8_t ob;
-        fp8_one<T>(to_f32<T>(W[i]), s, tdt, mode & ~(FP8_EXACT_DIV | FP8_NO_PACKED16), DT, &of, &ob);
+        fp8_one<T>(to_f32<T>(W[i]), s, tdt, mode & ~(FP8_EXACT_DIV | FP8_NO_PACKED16 | FP8_RAW_SCALES), DT, &of, &ob);
         if (fake) ((T*)out)[i] = of; else ((uint8_t*)out)[i] = ob;
     }
 }

@@ -1,7 +1,7 @@
 // gptq_block_body.h — the statement body of the in-block kernel, included INSIDE a kernel: k_gptq_block (static LDS) and the chain
-// role of k_gptq_block_riders (the same arrays carved from dynamic LDS) in gptq_loop.hip. Text and not a function on purpose: as an
+// role of k_gptq_block_riders (the same arrays carved from dynamic LDS) in gptq_block_kernels.h. Text and not a function on purpose: as an
 // inlined function the same statements compiled to other register counts (k_gptq_block<128, 1024>: 78 instead of 64 VGPRs, one
-// workgroup per CU instead of two). The including scope provides: GptqBlockArgs a; constexpr int VARIANT, NT; LDS objects
+// workgroup per CU instead of two). The including scope provides: GptqBlockArgs a; constexpr int VARIANT, NT, KIND; LDS objects
 // float Us[BS * BS] (16-B aligned), float dg[BS], float2 dtab[BS] (fast path: {d, refined 1/d}), int d_not_plain (some d of the
 // block is outside the plain range: generic path for everyone). `return` leaves the kernel.
 //   Us[i][p*8 + e] = U[i1+i][i1 + p + 16e] for p+16e > i, else 0 ; dg[i] = U[i1+i][i1+i]
@@ -47,7 +47,7 @@
     const int64_t rr = active ? row : a.R - 1;
 
     if (VARIANT != 0 && !d_not_plain) {
-        const bool done = block_fast<VARIANT == 1, VARIANT == 1 ? BS : VARIANT>(a, Us, dtab, p, row, active);
+        const bool done = block_fast<VARIANT == 1, VARIANT == 1 ? BS : VARIANT, KIND>(a, Us, dtab, p, row, active);
         if (done) return;
     }
 
@@ -77,7 +77,7 @@
     const float* us = Us + p * 8;
 
 #define LLMC_CHUNK(E)                                                             \
-    gptq_steps16<16 * E>(w, w0, er, ls, sc, zr, us, dg, p, s_cur, z_cur, a);  \
+    gptq_steps16<16 * E, KIND>(w, w0, er, ls, sc, zr, us, dg, p, s_cur, z_cur, a);  \
     s_grp[E] = s_cur;                                                             \
     z_grp[E] = z_cur;
     LLMC_CHUNK(0) LLMC_CHUNK(1) LLMC_CHUNK(2) LLMC_CHUNK(3) LLMC_CHUNK(4) LLMC_CHUNK(5) LLMC_CHUNK(6) LLMC_CHUNK(7)

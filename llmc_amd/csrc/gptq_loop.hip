@@ -11,360 +11,8 @@
 // lane's registers end up holding exactly `tmp` (the weight of each column at the time it was visited).
 // Trailing update W[:, i2:] -= Err1 @ U[i1:i2, i2:] runs on the fp32 MFMA pipe (sgemm.hip) with the
 // k-ordered fma chain that reproduces the reference's CPU sgemm bit for bit.
-#include <stdlib.h>
-#include "common.h"
-#include "quant_math.h"
-#include "sgemm.h"
-#include "sgemm_wide_tile.h"
+#include "gptq_block_kernels.h"
 #include "pipe_streams.h"
-
-namespace llmc {
-
-static constexpr int BS = 128;  // GPTQ blocksize
-
-template <int PO> __device__ __forceinline__ float group_bcast(float v) {
-    // lane' = (lane & 0x10) | PO inside each 32-lane half: broadcast of lane PO of every 16-lane group
-    return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), 0x10 | (PO << 5)));
-}
-
-struct GptqBlockArgs {
-    const float* W;       // [R, K] running weights (panel read at cols i1..i1+count)
-    const float* U;       // [K, K] upper factor
-    float* Wout;          // [R, K] tmp
-    float* losses;        // [R, K] or null
-    float* Err;           // err of this block, c < 128: Err[row * err_ld + c], or k-major (err_kmajor) Err[c * err_ld + row]
-    int err_ld;
-    int err_kmajor;
-    float* scales;        // [R, ng]
-    float* zeros;         // [R, ng] or null (sym static)
-    const int32_t* col_group;  // [K] group of processed column (static mode), or null: group (i1 + c) / col_gsz
-    int col_gsz;          // static mode without col_group: processing-order groups (per_channel: 1 << 30, group 0)
-    int64_t R;
-    int K;
-    int i1;
-    int count;            // columns in this block (<= 128)
-    int ng;               // groups per row in scales/zeros
-    int gsz;              // dynamic mode: group size (<= 128, divides 128); static mode: unused
-    int static_mode;      // 0: qparams from current W at group starts; 1: given, gathered by col_group
-    int sym;
-    float qmin, qmax;
-};
-
-template <int I> struct StepIdx {
-    static constexpr int PO = I & 15;
-    static constexpr int EO = I >> 4;
-};
-
-// one column step, I compile-time
-template <int I>
-__device__ __forceinline__ void gptq_step(float (&w)[8], const float (&w0)[8], float (&er)[8], float (&ls)[8],
-                                          float (&sc)[8], float (&zr)[8], const float* __restrict__ us,
-                                          float d, int p, float& s_cur, float& z_cur, const GptqBlockArgs& a) {
-    constexpr int PO = StepIdx<I>::PO, EO = StepIdx<I>::EO;
-    // ---- group start (dynamic mode). The reference takes min/max from W[:, i:i+g] (gptq.py:216), which
-    // inside a block still holds the values the block STARTED with (only the clone W1 receives the
-    // in-block updates), hence w0 and not w for groups that start mid-block (group_size < 128).
-    if (!a.static_mode && (I % 16 == 0)) {
-        if ((I % a.gsz) == 0) {
-            float mn = INFINITY, mx = -INFINITY;
-            const int e1 = (I + a.gsz) >> 4;  // gsz is a multiple of 16
-#pragma unroll
-            for (int e = EO; e < 8; ++e)
-                if (e < e1 && p + 16 * e < a.count) {
-                    mn = fminf(mn, w0[e]);
-                    mx = fmaxf(mx, w0[e]);
-                }
-            mn = wave_min(mn, 16);
-            mx = wave_max(mx, 16);
-            QParams q = qparams_from_minmax(mn, mx, LLMC_F32, a.sym, 1, a.qmin, a.qmax);
-            s_cur = q.s;
-            z_cur = q.z;
-        }
-    }
-    float wi = group_bcast<PO>(w[EO]);
-    float s = s_cur, z = z_cur;
-    if (a.static_mode) {
-        s = group_bcast<PO>(sc[EO]);
-        z = group_bcast<PO>(zr[EO]);
-    }
-    const float qc = quant_code(wi, s, z, LLMC_F32, LLMC_F32, a.qmin, a.qmax);
-    const float q = dequant_code(qc, s, z, LLMC_F32);
-    const float diff = wi - q;
-    const float err = diff / d;
-    if (p == PO) {
-        er[EO] = err;
-        ls[EO] = (diff * diff) / (2.0f * (d * d));
-    }
-#pragma unroll
-    for (int e = EO; e < 8; ++e) {
-        const float u = us[I * BS + e];
-        const float t = err * u;
-        w[e] = w[e] - t;
-    }
-}
-
-template <int I0>
-__device__ __forceinline__ void gptq_steps16(float (&w)[8], const float (&w0)[8], float (&er)[8], float (&ls)[8],
-                                             float (&sc)[8], float (&zr)[8], const float* __restrict__ us,
-                                             const float* __restrict__ dg, int p, float& s_cur, float& z_cur,
-                                             const GptqBlockArgs& a) {
-#define LLMC_STEP(J)                                                                         \
-    if (I0 + J < a.count) gptq_step<I0 + J>(w, w0, er, ls, sc, zr, us, dg[I0 + J], p, s_cur, z_cur, a);
-    LLMC_STEP(0) LLMC_STEP(1) LLMC_STEP(2) LLMC_STEP(3) LLMC_STEP(4) LLMC_STEP(5) LLMC_STEP(6) LLMC_STEP(7)
-    LLMC_STEP(8) LLMC_STEP(9) LLMC_STEP(10) LLMC_STEP(11) LLMC_STEP(12) LLMC_STEP(13) LLMC_STEP(14) LLMC_STEP(15)
-#undef LLMC_STEP
-}
-
-
-// ---------------------------------------------------------------------------------------------------------
-// Fast in-block path (count == 128). The serial chain of a column step is what bounds this kernel (one wave
-// per SIMD at R = 4096), so the chain is cut to ~22 dependent VALU ops:
-//   * the two IEEE divisions (w / scale and diff / d) divide by values that are fixed for many steps, so
-//     the reciprocal refinement  y = rcp(d) * (2 - d * rcp(d))  is hoisted (per column for d, per group for
-//     the scale) and each quotient is the remaining 5 ops of the very sequence hipcc emits for `n / d`
-//     (mul, fma, fma, fma, div_fmas == fma).  That sequence first passes n and d through v_div_scale_f32,
-//     which is the identity when both are "plain" (2^-40 <= |x| < 2^40, see the ISA's scaling rules), and
-//     ends in v_div_fixup_f32, which only acts on zero / inf / nan / denormal operands.  Every numerator
-//     of the block is still in registers after the loop (w[] holds each column's value at the time it was
-//     visited, df[] each diff), so ONE check after the 128 steps proves all operands were plain (+0 counts:
-//     the 5-op chain returns +0 for it, like the division); a wave that saw anything else (-0, tiny, huge,
-//     inf, nan) discards its work and redoes the block with the generic path below, so results are
-//     bit-identical by construction, not by argument.
-//   * the broadcast of the current column is a DPP row_newbcast (VALU latency) instead of an LDS swizzle;
-//   * the U row, d and 1/d of a step do not depend on the chain and are read from LDS ahead of it; there is
-//     no control flow inside the 128 steps, the losses are evaluated after the loop.
-template <int PO> __device__ __forceinline__ float row_bcast(float v) {
-    // row_newbcast:PO (gfx90a+): every lane of a 16-lane row reads lane PO of its row
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x150 + PO, 0xf, 0xf, false));
-}
-// plain numerator: 2^-40 <= |x| < 2^40, or +0
-__device__ __forceinline__ bool plain_num(float x) {
-    const uint32_t b = __float_as_uint(x);
-    return ((b & 0x7fffffffu) - 0x2B800000u) < 0x28000000u || b == 0u;
-}
-// One step. (u, dd) were loaded during the previous step; this step loads (un, ddn) for the next one first.
-template <int I, bool STATIC>
-__device__ __forceinline__ void fast_step(float (&w)[8], float (&er)[8], float (&df)[8], const float (&sc)[8],
-                                          const float (&zr)[8], const float (&ys)[8],
-                                          const float* __restrict__ us, const float2* __restrict__ dtab, int p,
-                                          float s_cur, float z_cur, float y_cur, float qmin, float qmax,
-                                          const float (&u)[8], const float2& dd, float (&un)[8],
-                                          float2& ddn) {
-    constexpr int PO = StepIdx<I>::PO, EO = StepIdx<I>::EO;
-    if (I + 1 < BS) {
-        constexpr int EN = StepIdx<I + 1>::EO;
-#pragma unroll
-        for (int e = EN; e < 8; ++e) un[e] = us[(I + 1) * BS + e];
-        ddn = dtab[I + 1];
-    }
-    float s = s_cur, z = z_cur, y = y_cur;
-    if (STATIC) {
-        s = row_bcast<PO>(sc[EO]);
-        z = row_bcast<PO>(zr[EO]);
-        y = row_bcast<PO>(ys[EO]);
-    }
-    const float wi = row_bcast<PO>(w[EO]);
-    float t = div_tail(wi, s, y);                   // quant_code(): x / s; plain s > 0, y = rcp_refined(s), wi a plain numerator
-    t = rintf(t);
-    t = t + z;
-    const float qc = fminf(fmaxf(t, qmin), qmax);
-    const float q = (qc - z) * s;                   // dequant_code()
-    const float diff = wi - q;
-    const float err = div_tail(diff, dd.x, dd.y);
-    const bool own = p == PO;
-    er[EO] = own ? err : er[EO];
-    df[EO] = own ? diff : df[EO];
-    // pin the two selects here: left alone, the optimiser turns the 16-deep select chains into a private array
-    // indexed by p after the loop, which keeps all 256 err / diff values alive (spills)
-    asm volatile("" : "+v"(er[EO]), "+v"(df[EO]));
-    // w[e] -= fl(err * u[e]) for e >= EO, two columns per packed instruction where a pair is whole
-    typedef float v2f __attribute__((ext_vector_type(2)));
-    if (EO & 1) {
-        const float tt = err * u[EO];
-        w[EO] = w[EO] - tt;
-    }
-#pragma unroll
-    for (int e = (EO + 1) & ~1; e < 8; e += 2) {
-        const v2f uu = {u[e], u[e + 1]};
-        v2f ww = {w[e], w[e + 1]};
-        const v2f tt = uu * err;
-        ww = ww - tt;
-        w[e] = ww.x;
-        w[e + 1] = ww.y;
-    }
-    __builtin_amdgcn_sched_barrier(0);   // keep the scheduler from hoisting later steps' loads (register blow-up)
-}
-
-template <int I0, bool STATIC>
-__device__ __forceinline__ void fast_steps16(float (&w)[8], float (&er)[8], float (&df)[8], const float (&sc)[8],
-                                             const float (&zr)[8], const float (&ys)[8],
-                                             const float* __restrict__ us, const float2* __restrict__ dtab,
-                                             int p, float s_cur, float z_cur, float y_cur, float qmin,
-                                             float qmax, float (&ua)[8], float2& da, float (&ub)[8],
-                                             float2& db) {
-#define LLMC_FSTEP2(J)                                                                                        \
-    fast_step<I0 + J, STATIC>(w, er, df, sc, zr, ys, us, dtab, p, s_cur, z_cur, y_cur, qmin, qmax, ua, da, \
-                              ub, db);                                                                        \
-    fast_step<I0 + J + 1, STATIC>(w, er, df, sc, zr, ys, us, dtab, p, s_cur, z_cur, y_cur, qmin, qmax, ub, \
-                                  db, ua, da);
-    LLMC_FSTEP2(0) LLMC_FSTEP2(2) LLMC_FSTEP2(4) LLMC_FSTEP2(6) LLMC_FSTEP2(8) LLMC_FSTEP2(10) LLMC_FSTEP2(12)
-    LLMC_FSTEP2(14)
-#undef LLMC_FSTEP2
-}
-
-// Whole block for one wave (4 rows); returns false (and stores nothing) if any lane met a non-plain operand.
-template <bool STATIC, int GSZ>
-__device__ __forceinline__ bool block_fast(const GptqBlockArgs& a, const float* __restrict__ Us,
-                                           const float2* __restrict__ dtab, int p, int64_t row, bool active) {
-    const int64_t rr = active ? row : a.R - 1;
-    float w[8], w0[8], er[8], df[8], sc[8], zr[8], ys[8];
-    bool bad = false;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int c = p + 16 * e;
-        w[e] = a.W[rr * a.K + a.i1 + c];
-        w0[e] = w[e];
-        er[e] = 0.0f;
-        df[e] = 0.0f;
-        sc[e] = 1.0f;
-        zr[e] = 0.0f;
-        ys[e] = 1.0f;
-        if (STATIC) {
-            const int g = a.col_group ? a.col_group[a.i1 + c] : (a.i1 + c) / a.col_gsz;
-            sc[e] = a.scales[rr * a.ng + g];
-            zr[e] = a.zeros ? a.zeros[rr * a.ng + g] : 0.0f;
-            ys[e] = rcp_refined(sc[e]);
-            bad |= !plain_pos(sc[e]);
-        }
-    }
-    float s_cur = 1.0f, z_cur = 0.0f, y_cur = 1.0f;
-    float s_grp[8], z_grp[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        s_grp[e] = 0.0f;
-        z_grp[e] = 0.0f;
-    }
-    const float* us = Us + p * 8;
-    float ua[8], ub[8];
-    float2 da = dtab[0], db = da;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        ua[e] = us[e];
-        ub[e] = 0.0f;
-    }
-#define LLMC_FCHUNK(E)                                                                                 \
-    if (!STATIC && ((16 * E) % GSZ) == 0) {                                                            \
-        float mn = INFINITY, mx = -INFINITY;                                                           \
-        constexpr int e1 = (16 * E + GSZ) >> 4;                                                        \
-        _Pragma("unroll") for (int e = E; e < 8; ++e) if (e < e1) {                                    \
-            mn = fminf(mn, w0[e]);                                                                     \
-            mx = fmaxf(mx, w0[e]);                                                                     \
-        }                                                                                              \
-        mn = wave_min(mn, 16);                                                                         \
-        mx = wave_max(mx, 16);                                                                         \
-        const QParams qp = qparams_from_minmax(mn, mx, LLMC_F32, a.sym, 1, a.qmin, a.qmax);            \
-        s_cur = qp.s;                                                                                  \
-        z_cur = qp.z;                                                                                  \
-        y_cur = rcp_refined(s_cur);                                                                    \
-        bad |= !plain_pos(s_cur);                                                                      \
-    }                                                                                                  \
-    fast_steps16<16 * E, STATIC>(w, er, df, sc, zr, ys, us, dtab, p, s_cur, z_cur, y_cur, a.qmin, a.qmax, \
-                                 ua, da, ub, db);                                                      \
-    s_grp[E] = s_cur;                                                                                  \
-    z_grp[E] = z_cur;
-    LLMC_FCHUNK(0) LLMC_FCHUNK(1) LLMC_FCHUNK(2) LLMC_FCHUNK(3) LLMC_FCHUNK(4) LLMC_FCHUNK(5) LLMC_FCHUNK(6)
-    LLMC_FCHUNK(7)
-#undef LLMC_FCHUNK
-#pragma unroll
-    for (int e = 0; e < 8; ++e) bad |= !plain_num(w[e]) | !plain_num(df[e]);
-    if (__any(bad)) return false;
-    if (!active) return true;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int c = p + 16 * e;
-        a.Wout[row * a.K + a.i1 + c] = w[e];
-        if (a.losses) {
-            const float d = dtab[c].x;
-            a.losses[row * a.K + a.i1 + c] = (df[e] * df[e]) / (2.0f * (d * d));
-        }
-        a.Err[a.err_kmajor ? (int64_t)c * a.err_ld + row : (int64_t)row * a.err_ld + c] = er[e];
-    }
-    if (!STATIC && p == 0) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int i = 16 * e;
-            if ((i % GSZ) == 0) {
-                const int g = (a.i1 + i) / GSZ;
-                a.scales[row * a.ng + g] = s_grp[e];
-                if (a.zeros) a.zeros[row * a.ng + g] = z_grp[e];
-            }
-        }
-    }
-    return true;
-}
-
-static constexpr int GBT = 512;  // threads per workgroup: 8 waves x 4 rows (1024 for tall weights, see launch)
-
-// VARIANT: 0 generic path only; 1 fast path for given qparams (static groups / per-channel); 16/32/64/128 fast
-// path for qparams taken at group starts with that group size. The fast variants fall back to the generic code
-// per wave.
-template <int VARIANT, int NT>
-__global__ __launch_bounds__(NT) void k_gptq_block(GptqBlockArgs a) {
-    __shared__ __attribute__((aligned(16))) float Us[BS * BS];
-    __shared__ float dg[BS];
-    __shared__ float2 dtab[BS];
-    __shared__ int d_not_plain;
-#include "gptq_block_body.h"
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// The in-block kernel with RIDERS: one grid, two roles chosen by blockIdx, no data shared between them inside a launch.
-//   chain role  (blockIdx < nchain): exactly k_gptq_block<VARIANT, 512> on group g + 1's block (its columns, ErrBuf[(g+1) % 3]);
-//   rider role  (the rest): ONE queued 128 x 128 tile of group g's far update (columns beyond group g + 1, ErrBuf[g % 3], read-only
-//                rows of U), two of its four 128-k phases, on the workgroup's first four waves — exactly k_sgemm_wide<2>'s tile
-//                (sgemm_wide_tile.h): one accumulator per element and phase, ascending k from +0 on v_mfma_f32_32x32x2_f32, one
-//                rounding C - acc per phase, the C tile in registers over the launch's phases. The other four waves end at once
-//                (a barrier counts the surviving waves only).
-// A launch is as long as its longest workgroup, and the chain role takes 24-28 us. Measured on down_proj's chain alone (profiles/
-// NOTES.md, chain riders): two whole tiles per CU share its MFMA pipes and take 64-70 us (the launch: 69 us); one whole tile 37-39 us
-// (launch 39 us); one tile's two phases 26-27 us (launch 27 us) — hence one tile per CU, cut along k into RIDER_PASSES slices of
-// whole phases that different launches carry: the C tile goes to memory and comes back in between (fp32: exact), per element the
-// same chain. 72 KiB of LDS, the chain role uses the first 66 KiB. The chain workgroups have the lowest indices: they are
-// dispatched first, the riders take the CUs the chain leaves free (the host sizes the grid: one tile per free CU). Workgroup b
-// runs on XCD b % 8: where the counts allow, an XCD's riders are `per` = tm / 8 consecutive tile rows of every tile column of the
-// launch (`per` A panels and the launch's few B panels in that XCD's L2).
-struct RiderArgs {
-    wide::WideArgs w;     // this launch's slice of the previous group's far update: whole tile columns, whole phases
-    int nchain;           // chain-role workgroups
-    int per;              // tile rows per XCD (nchain % 8 == 0, tm % 8 == 0), or 0: tiles in column-major order
-};
-static constexpr int RIDER_LDS = wide::Wide<2>::LDS;     // 73728
-static constexpr int RIDER_PASSES = 2;                    // k slices of a rider tile (divides GRP = 4 phases and the 4 carrying launches)
-
-template <int VARIANT>
-__global__ __launch_bounds__(GBT) void k_gptq_block_riders(GptqBlockArgs a, RiderArgs r) {
-    extern __shared__ __attribute__((aligned(16))) char smem_r[];
-    if ((int)blockIdx.x < r.nchain) {
-        constexpr int NT = GBT;
-        float* Us = reinterpret_cast<float*>(smem_r);
-        float* dg = Us + BS * BS;
-        float2* dtab = reinterpret_cast<float2*>(dg + BS);
-        int& d_not_plain = *reinterpret_cast<int*>(dtab + BS);
-#include "gptq_block_body.h"
-        return;
-    }
-    if (threadIdx.x >= 256) return;
-    const int rw = (int)blockIdx.x - r.nchain;
-    int ti = rw % r.w.tm, tj = rw / r.w.tm;
-    if (r.per) {
-        const int q = rw >> 3;
-        ti = (rw & 7) * r.per + q % r.per;
-        tj = q / r.per;
-    }
-    wide::wide_tile<2>(r.w, ti, tj, smem_r, (int)threadIdx.x);
-}
-
-}  // namespace llmc
 
 using namespace llmc;
 
@@ -442,6 +90,7 @@ struct ColCall {
     bool ekm; int64_t Rp, err_ld; float* ErrBuf[3];
     int ng, gsz, static_mode, sym; float qmin, qmax;
     const MseSearch* mse;
+    int kind;     // QKind of the in-block step
 
     float* err(int group, int64_t k) const { return ErrBuf[group % 3] + (ekm ? k * Rp : k); }     // err column k of the group
     int64_t group_end(int64_t g0) const { return g0 + GW < NQ ? g0 + GW : NQ; }
@@ -579,23 +228,10 @@ struct Sink {
             rec->add(CHAIN, PLAN_BLOCK, group, a.i1, a.i1 + a.count, -1, err_index(a.Err), rgroup, r0, r1, rerr, k0, k1);
             return LLMC_OK;
         }
-        switch (variant) {
-#define LLMC_GB(V)                                                                                                          \
-    case V:                                                                                                                 \
-        if (ra) {                                                                                                           \
-            LLMC_TRY(ensure_dynamic_lds((const void*)k_gptq_block_riders<V>, RIDER_LDS));                                   \
-            hipLaunchKernelGGL((k_gptq_block_riders<V>), dim3(grid + ra->w.tm * ra->w.tn), dim3(GBT), RIDER_LDS, st, a, *ra); \
-        } else if (nt == 1024) {                                                                                            \
-            hipLaunchKernelGGL((k_gptq_block<V, 1024>), dim3(grid), dim3(1024), 0, st, a);                                  \
-        } else {                                                                                                            \
-            hipLaunchKernelGGL((k_gptq_block<V, GBT>), dim3(grid), dim3(GBT), 0, st, a);                                    \
-        }                                                                                                                   \
-        break;
-            LLMC_GB(0) LLMC_GB(1) LLMC_GB(128)
-#undef LLMC_GB
-        }
-        LLMC_LAUNCH_CHECK();
-        return LLMC_OK;
+        // one translation unit per quantizer kind holds its kernels (gptq_block_kernels.h)
+        return o.kind == QK_E4M3 ? gptq_launch_in_block_e4m3(a, variant, nt, grid, ra, st)
+             : o.kind == QK_E5M2 ? gptq_launch_in_block_e5m2(a, variant, nt, grid, ra, st)
+                                 : launch_in_block<QK_INT>(a, variant, nt, grid, ra, st);
     }
 };
 
@@ -613,7 +249,7 @@ static int rider_quota(const ColCall& o, bool merged, int nt, int grid) {
 static int gptq_cols_impl(float* W, const float* Hinv, int64_t R, int64_t K, int64_t n_quant, int sym, float qmin,
                           float qmax, int64_t group_size, int static_groups, const int32_t* col_group, float* scales,
                           float* zeros, float* Wout, float* losses, int blocksize, void* ws, llmc_stream_t stream,
-                          const MseSearch* mse, PlanRec* rec = nullptr) {
+                          const MseSearch* mse, PlanRec* rec = nullptr, int kind = QK_INT) {
     LLMC_REQUIRE(W && Hinv && Wout && scales && ws && R > 0 && K > 0, "gptq_quantize: null/empty argument");
     LLMC_REQUIRE(n_quant > 0 && n_quant <= K, "gptq_quantize: n_quant must be in (0, K]");
     LLMC_REQUIRE(blocksize == BS, "gptq_quantize: blocksize must be 128");
@@ -634,7 +270,7 @@ static int gptq_cols_impl(float* W, const float* Hinv, int64_t R, int64_t K, int
     const int64_t Rp = (R + 3) & ~(int64_t)3;
     const ColCall o{W, Hinv, Wout, losses, scales, zeros, per_channel ? nullptr : col_group, R, K, n_quant,
                     ekm, Rp, ekm ? Rp : GW, {(float*)ws, (float*)ws + (size_t)Rp * GW, (float*)ws + 2 * (size_t)Rp * GW},
-                    per_channel ? 1 : (int)ceil_div64(K, group_size), gsz, static_mode, sym, qmin, qmax, mse};
+                    per_channel ? 1 : (int)ceil_div64(K, group_size), gsz, static_mode, sym, qmin, qmax, mse, kind};
     Lanes ln((hipStream_t)stream, rec);
     const Sink sink{o, ln, rec};
     const bool merged = !ln.piped() && !opt(OPT_K4_SPLIT_FAR);
@@ -717,6 +353,21 @@ extern "C" int llmc_gptq_quantize_cols(float* W, const float* Hinv, int64_t R, i
                                        float* losses, int blocksize, void* ws, llmc_stream_t stream) {
     return gptq_cols_impl(W, Hinv, R, K, n_quant, sym, qmin, qmax, group_size, static_groups, col_group, scales, zeros,
                           Wout, losses, blocksize, ws, stream, nullptr);
+}
+
+// The same loop on a FloatQuantizer grid (QK_E4M3 / QK_E5M2). The quantizer is symmetric without zero points; qmax is the
+// format's largest value (finfo(float8_e4m3fn / float8_e5m2).max, quant.py:982-996) and only scales the dynamic groups' range,
+// the float grid saturates by itself.
+extern "C" int llmc_gptq_quantize_fp8_cols(float* W, const float* Hinv, int64_t R, int64_t K, int64_t n_quant, int fmt,
+                                           int64_t group_size, int static_groups, const int32_t* col_group, float* scales,
+                                           float* Wout, float* losses, int blocksize, void* ws, llmc_stream_t stream) {
+    if (fmt != 0 && fmt != 1) {
+        set_last_error_msg("gptq_quantize_fp8_cols: fmt must be 0 (e4m3) or 1 (e5m2)");
+        return LLMC_ENOTSUP;
+    }
+    const float qmax = fmt ? 57344.0f : 448.0f;
+    return gptq_cols_impl(W, Hinv, R, K, n_quant, 1, -qmax, qmax, group_size, static_groups, col_group, scales, nullptr, Wout,
+                          losses, blocksize, ws, stream, nullptr, nullptr, fmt ? QK_E5M2 : QK_E4M3);
 }
 
 extern "C" size_t llmc_gptq_quantize_mse_ws_bytes(int64_t R, int64_t K) { return llmc_gptq_quantize_ws_bytes(R, K); }

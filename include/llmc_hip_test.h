@@ -47,6 +47,22 @@ int llmc_test_gptq_rider_plan(int64_t R, int64_t K, int64_t n_quant, int64_t gro
  * lane had issued before the record. Pure host call. */
 int llmc_test_gptq_pipe_plan(int64_t R, int64_t K, int64_t n_quant, int64_t group_size, int static_groups, int32_t* out,
                              int cap);
+/* tests/test_chol_plan.py: the launches llmc_chol_inv_upper (rev: llmc_chol_inv_upper_rev) issues for this K under the calling
+ * thread's options, in order; with_lanes: the helper-stream schedule, whatever llmc_hip_set_helper_streams says, else the
+ * one-stream schedule. Records of 22 int32, with lanes 23:
+ *   [0] kind: 0 antitranspose, 1 k_potrf_inv, 2 panel solve, 3 in-block update, 4 plane split, 7 far update, 8 k_place_diag_inv,
+ *       9 k_zero_subdiag, 10 / 11 the X = A^-1 C / C = -X B^-1 product of an inverse level;
+ *   [1] form: 0 the kernel named by the kind, 1 fp32 product (sgemm), 2 split-bf16 product (gemm3), 3 gemm6;
+ *   [2..6] the rectangle written, [7..11] and [12..16] up to two rectangles read, [17..21] a second rectangle written
+ *       (k_potrf_inv: the V block; gemm6: its workspace). A rectangle is buffer, rows [r0, r1), columns [c0, c1); buffer 0 the
+ *       working matrix (K x K), 1 the V blocks (128 columns), 2 X / bf16 planes and 3 the gemm6 workspace (both flat: rows [0, 1),
+ *       columns counted in floats), 4 the caller's other matrix (K x K: the input before, U after), -1 none. A batched product's
+ *       rectangles are the hull of its first and last problem;
+ *   [22] the lane (0 chain = the caller's stream, 1 bulk).
+ * Every field is read back from the pointers and leading dimensions the launch would get. Event rows as in
+ * llmc_test_gptq_pipe_plan: kind 5 / 6, the event's id in [1], every buffer -1, the lane last. Pure host call. Returns the number
+ * of records (only the first `cap` are written) or an error. */
+int llmc_test_chol_plan(int64_t K, int rev, int with_lanes, int32_t* out, int cap);
 
 #ifdef __cplusplus
 }

@@ -22,7 +22,7 @@ void set_last_error(const char* where, hipError_t e) {
 void set_last_error_msg(const char* msg) { snprintf(g_last_error, sizeof(g_last_error), "%s", msg); }
 
 // ---- per-device facts and per-(device, kernel) function attributes ---------------------------------------
-// The only process-wide mutable state of the library besides the side-stream pool; both are guarded by a mutex so
+// The only process-wide mutable state of the library besides the helper-stream pool (pipe_streams.h); both are guarded by a mutex so
 // that entry points may be called from several host threads (re-entrant).
 static std::mutex g_dev_mu;
 static int g_cu_count[LLMC_MAX_DEVICES] = {};

@@ -12,7 +12,7 @@
 #include <stdlib.h>
 #include "common.h"
 #include "sgemm.h"
-#include "side_stream.h"
+#include "pipe_lanes.h"
 
 namespace llmc {
 
@@ -555,23 +555,6 @@ __global__ __launch_bounds__(256) void k_reverse_perm(const int64_t* __restrict_
 }  // namespace llmc
 
 static int hessian_prep_impl(float* H, const void* W, int wdt, int64_t R, int64_t K, const int64_t* perm, float percdamp,
-                             float* Hout, float* Wout, void* ws, llmc_stream_t stream, bool rev);
-
-extern "C" int llmc_hessian_prep(float* H, const void* W, int wdt, int64_t R, int64_t K, const int64_t* perm,
-                                 float percdamp, float* Hout, float* Wout, void* ws, llmc_stream_t stream) {
-    return hessian_prep_impl(H, W, wdt, R, K, perm, percdamp, Hout, Wout, ws, stream, false);
-}
-
-// The same preparation with Hout written index-REVERSED: Hout[i][j] = Hp[K-1-i][K-1-j] (Hp = the permuted, damped matrix
-// llmc_hessian_prep writes). For a symmetric H that is Hp reflected across its anti-diagonal — exactly the matrix
-// llmc_chol_inv_upper builds first from Hp with a transposing pass over K^2 floats — at no cost: it is the same gather with
-// the permutation read backwards. llmc_chol_inv_upper_rev takes it. W is gathered with `perm` as always.
-extern "C" int llmc_hessian_prep_rev(float* H, const void* W, int wdt, int64_t R, int64_t K, const int64_t* perm,
-                                     float percdamp, float* Hout, float* Wout, void* ws, llmc_stream_t stream) {
-    return hessian_prep_impl(H, W, wdt, R, K, perm, percdamp, Hout, Wout, ws, stream, true);
-}
-
-static int hessian_prep_impl(float* H, const void* W, int wdt, int64_t R, int64_t K, const int64_t* perm, float percdamp,
                              float* Hout, float* Wout, void* ws, llmc_stream_t stream, bool rev) {
     LLMC_REQUIRE(H && ws && K > 0, "hessian_prep: null/empty argument");
     LLMC_REQUIRE((W && Wout && R > 0) || (!W && !Wout), "hessian_prep: W and Wout go together");
@@ -627,6 +610,20 @@ static int hessian_prep_impl(float* H, const void* W, int wdt, int64_t R, int64_
     return LLMC_OK;
 }
 
+extern "C" int llmc_hessian_prep(float* H, const void* W, int wdt, int64_t R, int64_t K, const int64_t* perm,
+                                 float percdamp, float* Hout, float* Wout, void* ws, llmc_stream_t stream) {
+    return hessian_prep_impl(H, W, wdt, R, K, perm, percdamp, Hout, Wout, ws, stream, false);
+}
+
+// The same preparation with Hout written index-REVERSED: Hout[i][j] = Hp[K-1-i][K-1-j] (Hp = the permuted, damped matrix
+// llmc_hessian_prep writes). For a symmetric H that is Hp reflected across its anti-diagonal — exactly the matrix
+// llmc_chol_inv_upper builds first from Hp with a transposing pass over K^2 floats — at no cost: it is the same gather with
+// the permutation read backwards. llmc_chol_inv_upper_rev takes it. W is gathered with `perm` as always.
+extern "C" int llmc_hessian_prep_rev(float* H, const void* W, int wdt, int64_t R, int64_t K, const int64_t* perm,
+                                     float percdamp, float* Hout, float* Wout, void* ws, llmc_stream_t stream) {
+    return hessian_prep_impl(H, W, wdt, R, K, perm, percdamp, Hout, Wout, ws, stream, true);
+}
+
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // doubling levels of the triangular inverse from this block size on run on the one-wave-per-SIMD GEMM (gemm6_launch)
@@ -641,15 +638,265 @@ static size_t gemm6_bytes(int64_t K) {
     return align256(mx);
 }
 
-extern "C" size_t llmc_chol_inv_upper_ws_bytes(int64_t K) {
-    if (K <= 0) return 0;
-    size_t work = align256((size_t)K * K * 4);
-    size_t vbuf = align256((size_t)ceil_div64(K, NB) * NB * NB * 4);
-    size_t xbuf = align256((size_t)(K / 2 + NB) * (K / 2 + NB) * 4);
-    return work + vbuf + xbuf + gemm6_bytes(K);
+// The workspace: the working matrix (unused by the in-place form), the inverted diagonal blocks V, X (the inverse levels' A^-1 C,
+// and the bf16 planes of a far update's panel), gemm6's planes. Byte offsets, each 256-B aligned.
+struct FactorWs { size_t work, vbuf, xbuf, xbuf_bytes, g6, total; };
+static FactorWs factor_ws(int64_t K) {
+    FactorWs w{};
+    w.vbuf = align256((size_t)K * K * 4);
+    w.xbuf = w.vbuf + align256((size_t)ceil_div64(K, NB) * NB * NB * 4);
+    w.xbuf_bytes = (size_t)(K / 2 + NB) * (K / 2 + NB) * 4;
+    w.g6 = w.xbuf + align256(w.xbuf_bytes);
+    w.total = w.g6 + gemm6_bytes(K);
+    return w;
 }
 
-static int chol_inv_upper_impl(float* A, float* Uout, int64_t K64, void* ws, int32_t* info_dev, llmc_stream_t stream);
+extern "C" size_t llmc_chol_inv_upper_ws_bytes(int64_t K) { return K <= 0 ? 0 : factor_ws(K).total; }
+
+// The host schedule: DESIGN.md §3 "K3's host schedule". Two-level blocked upper Cholesky Wk = U'^T U' — 128-wide factor steps
+// inside 512-wide outer blocks, whose rows beyond the block receive ONE far update with Kd = 512 — then V = U'^-1 by doubling
+// levels. Where a step's columns and a far update's rows are cut, and onto which lane, is data (pieces); every kernel computes an
+// element the same way whatever the cut, so the factor is bit-identical with or without the helper stream as long as per element
+// the updates arrive in step order — which the waits in chol_inv_upper_impl state and tests/test_chol_plan.py replays.
+static constexpr int NBO = 4 * NB;
+struct Piece { int a0, a1; Lane lane; };      // columns of a factor step, or rows of a far update
+// A factor step's columns [c1, K): in one piece on one stream (the split costs two more launches per step and buys nothing there),
+// else NEAR (the block's own, which the next step needs) on the chain and FAR (the bulk of a step's work) on the bulk lane.
+static int step_pieces(int c1, int oend, int K, bool piped, Piece* p) {
+    if (!piped || oend >= K) return p[0] = Piece{c1, K, CHAIN}, 1;
+    return p[0] = Piece{c1, oend, CHAIN}, p[1] = Piece{oend, K, BULK}, 2;
+}
+// An outer block's far update of the rows [oend, K): merged (one stream: one launch less per block, no round of 216 tiles on its
+// own), else the NEXT block's rows first, on the chain (its factor steps need them), and the rest on the bulk lane.
+static int far_pieces(int oend, int K, bool merged, Piece* p) {
+    if (merged || oend + NBO >= K) return p[0] = Piece{oend, K, CHAIN}, 1;
+    return p[0] = Piece{oend, oend + NBO, CHAIN}, p[1] = Piece{oend + NBO, K, BULK}, 2;
+}
+
+// What every launch's arguments are made from: the buffers, K and the options, read once. The only pointer arithmetic of K3.
+struct Level { int64_t h, stride, ldX; int npairs, n2_last; bool x3, g6; };
+struct FactorCall {
+    float* Wk; float* Vbuf; float* Xbuf; void* G6buf; int K; size_t xbuf_bytes;
+    // x3: the large products (far updates, inverse levels >= 512) as split-bf16 products on the 16-bit MFMA pipe (gemm3.hip:
+    // fp32-level accuracy, 1.3-1.5x the fp32-MFMA kernel; option k3_fp32). planes: a far update's panel split ONCE into bf16 planes
+    bool x3, planes, merge_far, g6;
+    float* at(int64_t r, int64_t c) const { return Wk + r * K + c; }
+    float* V(int c0) const { return Vbuf + (size_t)(c0 / NB) * NB * NB; }
+    static SgemmArgs one(int M, int N, int Kd, int epilogue) {
+        SgemmArgs g{};
+        g.M = g.M_last = M; g.N = g.N_last = N; g.Kd = g.Kd_last = Kd; g.epilogue = epilogue; g.batch = 1;
+        return g;
+    }
+    // P = V^T P for P = rows [c0, c0 + nb), columns [col0, col1)  (op(A)[i][k] = V[k][i], lower triangular)
+    SgemmArgs panel_solve(int c0, int nb, int col0, int col1) const {
+        SgemmArgs g = one(nb, col1 - col0, nb, SG_SET);
+        g.A = V(c0); g.lda = NB; g.B = g.C = at(c0, col0); g.ldb = g.ldc = K; g.a_lower = 1;
+        return g;
+    }
+    // rows [c0 + nb, oend) of the trailing matrix, columns [col0, col1):  C -= P[:, rows]^T P[:, cols]
+    SgemmArgs inblock_update(int c0, int nb, int oend, int col0, int col1) const {
+        SgemmArgs u = one(oend - (c0 + nb), col1 - col0, nb, SG_SUB);
+        u.A = at(c0, c0 + nb); u.B = at(c0, col0); u.C = at(c0 + nb, col0); u.lda = u.ldb = u.ldc = K;
+        u.c_upper_only = col0 == c0 + nb ? 1 : 0;      // the far columns lie right of every row
+        return u;
+    }
+    // rows [r0, r1) of the far update T -= P^T P, P = rows [k0, oend), columns [oend, K): upper triangle, columns [r0, K)
+    SgemmArgs far(int k0, int oend, int r0, int r1, bool with_planes) const {
+        SgemmArgs u = one(r1 - r0, K - r0, oend - k0, SG_SUB);
+        u.A = u.B = at(k0, r0); u.C = at(r0, r0); u.lda = u.ldb = u.ldc = K; u.c_upper_only = 1;
+        if (with_planes) {
+            u.planesA = u.planesB = (const uint16_t*)Xbuf + (r0 - oend);
+            u.ldp = K - oend; u.plane_stride = (int64_t)(oend - k0) * (K - oend);
+        }
+        return u;
+    }
+    // the planes of P (in Xbuf, which otherwise only the inverse levels use) are worth it when the last piece would run on them
+    bool split_planes(int k0, int oend, int r0) const {
+        const int nfar = K - oend;
+        return x3 && planes && nfar % 8 == 0 && (size_t)3 * (oend - k0) * nfar * 2 <= xbuf_bytes && gemm3_uses_planes(far(k0, oend, r0, K, true));
+    }
+    // level h of V = U'^-1: pairs [[A, C], [0, B]] of h-blocks with a non-empty right block, C = -A^-1 C B^-1 through X = A^-1 C
+    Level level(int64_t h) const {
+        Level l{h, 2 * h * ((int64_t)K + 1), h, (int)((K - h + 2 * h - 1) / (2 * h)), 0, false, false};
+        if (l.npairs <= 0) return l;
+        const int64_t rest = K - (int64_t)(l.npairs - 1) * 2 * h - h;
+        l.n2_last = (int)(rest < h ? rest : h);
+        if (l.npairs == 1) l.ldX = ((l.n2_last + 3) / 4) * 4;      // X is [h x n2]: one pair keeps it within K^2 / 4 floats
+        l.x3 = x3 && h >= 512;      // small levels are latency-bound: the fp32 kernels stay
+        // large, deep levels: operands split once into stacked bf16 planes, product on the one-wave-per-SIMD GEMM
+        l.g6 = l.x3 && g6 && h >= GEMM6_MIN_H && h % 256 == 0 && l.n2_last % 256 == 0;
+        return l;
+    }
+    SgemmArgs level_x(const Level& l) const {      // X = A^-1 C: A^-1 at (o, o), upper, C at (o, o + h)
+        SgemmArgs x = one((int)l.h, (int)l.h, (int)l.h, SG_SET);
+        x.A = Wk; x.B = Wk + l.h; x.lda = x.ldb = K; x.sA = x.sB = l.stride; x.C = Xbuf; x.ldc = l.ldX; x.sC = l.h * l.h;
+        x.N_last = l.n2_last; x.a_upper = 1; x.batch = l.npairs;
+        return x;
+    }
+    SgemmArgs level_c(const Level& l) const {      // C = -X B^-1: B^-1 at (o + h, o + h), upper
+        SgemmArgs y = one((int)l.h, (int)l.h, (int)l.h, SG_NEG);
+        y.A = Xbuf; y.lda = l.ldX; y.sA = l.h * l.h; y.B = Wk + l.h * ((int64_t)K + 1); y.C = Wk + l.h; y.ldb = y.ldc = K; y.sB = y.sC = l.stride;
+        y.N_last = y.Kd_last = l.n2_last; y.b_upper = 1; y.batch = l.npairs;
+        return y;
+    }
+    static SgemmArgs problem(SgemmArgs g, int z) {      // the z-th problem of a batch on its own (gemm6 takes one at a time)
+        g.A += z * g.sA; g.B += z * g.sB; g.C += z * g.sC;
+        if (z == g.batch - 1) g.M = g.M_last, g.N = g.N_last, g.Kd = g.Kd_last;
+        g.batch = 1;
+        return g;
+    }
+};
+
+// One place that either launches or, for a plan, writes down what WOULD be launched: rows of CP_W int32 (include/llmc_hip_test.h),
+// every rectangle read back from the pointers and leading dimensions the launch gets.
+enum { CP_TRANSPOSE = 0, CP_POTRF = 1, CP_SOLVE = 2, CP_UPDATE = 3, CP_SPLIT = 4, CP_FAR = 7, CP_PLACE = 8, CP_ZERO = 9, CP_INV_X = 10,
+       CP_INV_C = 11, CP_W = 22 };
+enum { F_KERNEL = 0, F_SGEMM = 1, F_GEMM3 = 2, F_GEMM6 = 3 };
+struct Rect { int32_t buf, r0, r1, c0, c1; };      // buf: 0 working matrix, 1 V blocks, 2 X / planes, 3 gemm6 workspace, 4 the caller's other matrix
+static const int32_t CP_BLANK[CP_W] = {0, 0, -1, 0, 0, 0, 0, -1, 0, 0, 0, 0, -1, 0, 0, 0, 0, -1, 0, 0, 0, 0};
+static constexpr int POTRF_LDS = (NB * PLD + 32 * PLD + 64) * (int)sizeof(float);
+static int launched() { LLMC_LAUNCH_CHECK(); return LLMC_OK; }
+struct FactorSink {
+    const FactorCall& o; const Lanes& ln; PlanRec* rec; const float* other; const char* ws_end; int32_t* info;
+    // [rows x cols] floats at p: X and the gemm6 workspace as flat ranges of floats, a wrong leading dimension as buffer -2
+    Rect rect(const void* p, int64_t ld, int64_t rows, int64_t cols) const {
+        const float* f = (const float*)p;
+        if ((const char*)f >= (const char*)o.Xbuf && (const char*)f < ws_end) {
+            const bool x = (const void*)f < o.G6buf;
+            const int64_t off = f - (x ? o.Xbuf : (const float*)o.G6buf);
+            return Rect{x ? 2 : 3, 0, 1, (int32_t)off, (int32_t)(off + (rows - 1) * ld + cols)};
+        }
+        const bool v = f >= o.Vbuf && f < o.Xbuf, w = f >= o.Wk && f < o.Wk + (size_t)o.K * o.K;
+        const int64_t n = v ? NB : o.K, off = f - (v ? o.Vbuf : w ? o.Wk : other);
+        return Rect{ld != n ? -2 : v ? 1 : w ? 0 : 4, (int32_t)(off / n), (int32_t)(off / n + rows), (int32_t)(off % n), (int32_t)(off % n + cols)};
+    }
+    int add(int kind, int form, Lane lane, Rect w, Rect a = Rect{-1}, Rect b = Rect{-1}, Rect w2 = Rect{-1}) const {
+        int32_t v[CP_W] = {kind, form};
+        memcpy(v + 2, &w, sizeof w), memcpy(v + 7, &a, sizeof a), memcpy(v + 12, &b, sizeof b), memcpy(v + 17, &w2, sizeof w2);
+        rec->row(v, ln.lane_of(ln.s[lane]));
+        return LLMC_OK;
+    }
+    int transpose(const float* in, float* out, int upper_only) const {
+        if (rec) return add(CP_TRANSPOSE, F_KERNEL, CHAIN, rect(out, o.K, o.K, o.K), rect(in, o.K, o.K, o.K));
+        hipLaunchKernelGGL(k_antitranspose, dim3((o.K + 31) / 32, (o.K + 31) / 32), dim3(256), 0, ln.s[CHAIN], in, out, o.K, upper_only);
+        return launched();
+    }
+    int potrf(int c0, int nb) const {      // factors and inverts the diagonal block: rewrites it, writes its V block (and the failure flag)
+        float* Vb = o.V(c0);
+        if (rec) return add(CP_POTRF, F_KERNEL, CHAIN, rect(o.at(c0, c0), o.K, nb, nb), rect(o.at(c0, c0), o.K, nb, nb), Rect{-1}, rect(Vb, NB, nb, NB));
+        hipLaunchKernelGGL(k_potrf_inv, dim3(1), dim3(256), POTRF_LDS, ln.s[CHAIN], o.Wk, (int64_t)o.K, c0, nb, Vb, info);
+        return launched();
+    }
+    // a product: fp32 (sgemm_launch) or split-bf16; the rectangles of a batch are the hull of the first and the last problem
+    int product(int kind, const SgemmArgs& g, int form, bool TA, Lane lane) const {
+        if (g.M <= 0 || g.N <= 0) return LLMC_OK;
+        const hipStream_t st = ln.s[lane];
+        if (!rec) return form == F_SGEMM ? sgemm_launch(g, TA, false, st) : TA ? gemm3_tn_launch(g, st) : gemm3_launch(g, false, st);
+        auto hull = [&](const float* p, int64_t ld, int64_t s, int r, int c, int rl, int cl) {
+            const Rect a = rect(p, ld, r, c), b = rect(p + (g.batch - 1) * s, ld, rl, cl);
+            return Rect{a.buf, a.r0, b.r1, a.c0, b.c1};
+        };
+        auto planes = [&](const void* p, int n) { return rect(p, 1, 1, (2 * g.plane_stride + (g.Kd - 1) * g.ldp + n + 1) / 2); };
+        const bool pl = form == F_GEMM3 && TA && gemm3_uses_planes(g);
+        return add(kind, form, lane, hull(g.C, g.ldc, g.sC, g.M, g.N, g.M_last, g.N_last),
+                   pl ? planes(g.planesA, g.M) : TA ? hull(g.A, g.lda, g.sA, g.Kd, g.M, g.Kd_last, g.M_last) : hull(g.A, g.lda, g.sA, g.M, g.Kd, g.M_last, g.Kd_last),
+                   pl ? planes(g.planesB, g.N) : hull(g.B, g.ldb, g.sB, g.Kd, g.N, g.Kd_last, g.N_last));
+    }
+    int split(int k0, int oend) const {      // the hi | mid | lo bf16 planes of the far panel P into X
+        const int nbo = oend - k0, nfar = o.K - oend;
+        if (rec) return add(CP_SPLIT, F_KERNEL, CHAIN, rect(o.Xbuf, 1, 1, ((int64_t)3 * nbo * nfar + 1) / 2), rect(o.at(k0, oend), o.K, nbo, nfar));
+        return gemm3_split_planes(o.at(k0, oend), o.K, nbo, nfar, o.Xbuf, nfar, (int64_t)nbo * nfar, ln.s[CHAIN]);
+    }
+    int gemm6(int kind, const SgemmArgs& g) const {      // one problem: A row-major, B k-major, SG_SET or SG_NEG
+        if (rec) return add(kind, F_GEMM6, CHAIN, rect(g.C, g.ldc, g.M, g.N), rect(g.A, g.lda, g.M, g.Kd), rect(g.B, g.ldb, g.Kd, g.N),
+                            rect(o.G6buf, 1, 1, (int64_t)(gemm6_ws_bytes(g.M, g.N, g.Kd) / 4)));
+        return gemm6_launch(g.A, g.lda, g.B, g.ldb, g.C, g.ldc, g.M, g.N, g.Kd, g.a_upper, g.b_upper, g.epilogue == SG_NEG ? -1.0f : 1.0f,
+                            o.G6buf, ln.s[CHAIN]);
+    }
+    int place_diag() const {      // the inverted diagonal blocks into the working matrix
+        const int nblk = (o.K + NB - 1) / NB;
+        if (rec) return add(CP_PLACE, F_KERNEL, CHAIN, rect(o.Wk, o.K, o.K, o.K), rect(o.Vbuf, NB, (int64_t)nblk * NB, NB));
+        hipLaunchKernelGGL(k_place_diag_inv, dim3(nblk), dim3(256), 0, ln.s[CHAIN], o.Wk, (int64_t)o.K, o.K, (const float*)o.Vbuf, 0);
+        return launched();
+    }
+    int zero_subdiag() const {
+        if (rec) return add(CP_ZERO, F_KERNEL, CHAIN, rect(o.Wk, o.K, o.K, o.K));
+        hipLaunchKernelGGL(k_zero_subdiag, dim3((o.K + 255) / 256), dim3(256), 0, ln.s[CHAIN], o.Wk, (int64_t)o.K, o.K);
+        return launched();
+    }
+};
+
+static int chol_inv_upper_impl(float* A, float* Uout, int64_t K64, void* ws, int32_t* info_dev, llmc_stream_t stream, PlanRec* rec = nullptr) {
+    LLMC_REQUIRE(A && ws && info_dev && K64 > 0, "chol_inv_upper: null/empty argument");
+    LLMC_REQUIRE(K64 % 4 == 0 && K64 < (1 << 30), "chol_inv_upper: K must be a multiple of 4");
+    LLMC_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)ws & 255) == 0, "chol_inv_upper: alignment");
+    const int K = (int)K64;
+    const bool rev = Uout != nullptr;          // A already holds the reflected matrix: work in it
+    const FactorWs l = factor_ws(K);
+    char* const w = (char*)ws;
+    const FactorCall o{rev ? A : (float*)(w + l.work), (float*)(w + l.vbuf), (float*)(w + l.xbuf), w + l.g6, K, l.xbuf_bytes,
+                       !opt(OPT_K3_FP32), !opt(OPT_K3_NO_PLANES), !opt(OPT_K3_SPLIT_FAR), !opt(OPT_K3_NO_GEMM6)};
+    Lanes ln((hipStream_t)stream, rec);
+    const FactorSink sink{o, ln, rec, rev ? Uout : A, w + l.total, info_dev};
+    LLMC_TRY(ln.fork());
+    if (!rec) {
+        LLMC_HIP_CHECK(hipMemsetAsync(info_dev, 0, 4, ln.s[CHAIN]));
+        LLMC_TRY(ensure_dynamic_lds((const void*)k_potrf_inv, POTRF_LDS));
+    }
+    if (!rev) LLMC_TRY(sink.transpose(A, o.Wk, 0));
+    Piece pc[2];
+    Ev planes_read{};      // bulk: the far update that read the planes in X is complete (they may be rewritten)
+    for (int k0 = 0; k0 < K; k0 += NBO) {
+        const int oend = k0 + NBO < K ? k0 + NBO : K;
+        for (int c0 = k0; c0 < oend; c0 += NB) {
+            const int nb = K - c0 < NB ? K - c0 : NB;
+            LLMC_TRY(sink.potrf(c0, nb));
+            if (c0 + nb >= K) break;
+            // the chain piece's update goes last: the bulk piece is on its way before the chain goes on to the next step
+            const int np = step_pieces(c0 + nb, oend, K, ln.piped(), pc);
+            LLMC_TRY(sink.product(CP_SOLVE, o.panel_solve(c0, nb, pc[0].a0, pc[0].a1), F_SGEMM, true, CHAIN));
+            if (np > 1) {
+                LLMC_TRY(ln.order(CHAIN, BULK));      // this step's near panel is complete (the far update of the step reads it)
+                LLMC_TRY(sink.product(CP_SOLVE, o.panel_solve(c0, nb, pc[1].a0, pc[1].a1), F_SGEMM, true, BULK));
+                LLMC_TRY(sink.product(CP_UPDATE, o.inblock_update(c0, nb, oend, pc[1].a0, pc[1].a1), F_SGEMM, true, BULK));
+            }
+            LLMC_TRY(sink.product(CP_UPDATE, o.inblock_update(c0, nb, oend, pc[0].a0, pc[0].a1), F_SGEMM, true, CHAIN));
+        }
+        if (oend >= K) break;
+        // the block's far panels are complete (behind them on the in-order bulk lane: the previous block's update of these rows)
+        LLMC_TRY(ln.order(BULK, CHAIN));
+        const int np = far_pieces(oend, K, !ln.piped() && o.x3 && o.merge_far, pc);
+        const bool planes = o.split_planes(k0, oend, pc[np - 1].a0);
+        if (planes) {
+            // the planes the previous block's update reads are free (implied today by the wait above — stated all the same)
+            LLMC_TRY(ln.wait(CHAIN, planes_read));
+            LLMC_TRY(sink.split(k0, oend));
+        }
+        for (int i = 0; i < np; ++i) {
+            // the bulk piece goes behind the chain's: the planes are split there, and the rows the next block's steps need go first
+            if (pc[i].lane == BULK) LLMC_TRY(ln.order(CHAIN, BULK));
+            LLMC_TRY(sink.product(CP_FAR, o.far(k0, oend, pc[i].a0, pc[i].a1, planes), o.x3 ? F_GEMM3 : F_SGEMM, true, pc[i].lane));
+            if (pc[i].lane == BULK) LLMC_TRY(ln.record(BULK, &planes_read));
+        }
+    }
+    // ---- V = U'^-1: inverted diagonal blocks, then doubling levels. Nothing is left on the bulk lane: the last block with a far
+    // update has no piece there
+    LLMC_TRY(sink.place_diag());
+    if (o.x3 && o.g6 && K > GEMM6_MIN_H) LLMC_TRY(sink.zero_subdiag());
+    for (int64_t h = NB; h < K; h *= 2) {
+        const Level lv = o.level(h);
+        if (lv.npairs <= 0) break;
+        for (int z = 0; lv.g6 && z < lv.npairs; ++z) {
+            LLMC_TRY(sink.gemm6(CP_INV_X, o.problem(o.level_x(lv), z)));
+            LLMC_TRY(sink.gemm6(CP_INV_C, o.problem(o.level_c(lv), z)));
+        }
+        if (lv.g6) continue;
+        LLMC_TRY(sink.product(CP_INV_X, o.level_x(lv), lv.x3 ? F_GEMM3 : F_SGEMM, false, CHAIN));
+        LLMC_TRY(sink.product(CP_INV_C, o.level_c(lv), lv.x3 ? F_GEMM3 : F_SGEMM, false, CHAIN));
+    }
+    LLMC_TRY(sink.transpose(o.Wk, rev ? Uout : A, 1));
+    return ln.join();
+}
 
 extern "C" int llmc_chol_inv_upper(float* A, int64_t K64, void* ws, int32_t* info_dev, llmc_stream_t stream) {
     return chol_inv_upper_impl(A, nullptr, K64, ws, info_dev, stream);
@@ -664,222 +911,13 @@ extern "C" int llmc_chol_inv_upper_rev(float* Arev, float* Uout, int64_t K64, vo
     return chol_inv_upper_impl(Arev, Uout, K64, ws, info_dev, stream);
 }
 
-static int chol_inv_upper_impl(float* A, float* Uout, int64_t K64, void* ws, int32_t* info_dev, llmc_stream_t stream) {
-    LLMC_REQUIRE(A && ws && info_dev && K64 > 0, "chol_inv_upper: null/empty argument");
-    LLMC_REQUIRE(K64 % 4 == 0 && K64 < (1 << 30), "chol_inv_upper: K must be a multiple of 4");
-    LLMC_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)ws & 255) == 0, "chol_inv_upper: alignment");
-    hipStream_t st = (hipStream_t)stream;
-    const int K = (int)K64;
-    const bool rev = Uout != nullptr;          // A already holds the reflected matrix: work in it
-    float* Wk = rev ? A : (float*)ws;
-    float* Vbuf = (float*)((char*)ws + align256((size_t)K * K * 4));
-    float* Xbuf = (float*)((char*)Vbuf + align256((size_t)ceil_div64(K, NB) * NB * NB * 4));
-    void* G6buf = (char*)Xbuf + align256((size_t)(K / 2 + NB) * (K / 2 + NB) * 4);
-    const bool use_g6 = !opt(OPT_K3_NO_GEMM6);
-    LLMC_HIP_CHECK(hipMemsetAsync(info_dev, 0, 4, st));
-    if (int rc = ensure_dynamic_lds((const void*)k_potrf_inv, (NB * PLD + 32 * PLD + 64) * (int)sizeof(float))) return rc;
-
-    dim3 tgrid((K + 31) / 32, (K + 31) / 32);
-    if (!rev) {
-        hipLaunchKernelGGL(k_antitranspose, tgrid, dim3(256), 0, st, (const float*)A, Wk, K, 0);
-        LLMC_LAUNCH_CHECK();
-    }
-
-    const int nblk = (K + NB - 1) / NB;
-    // ---- blocked upper Cholesky Wk = U'^T U', two-level: 128-wide factor steps inside 512-wide outer blocks.
-    // Inside an outer block every step updates only the rows of that block (Kd = 128, few rows); the rows
-    // beyond it receive ONE symmetric update with Kd = 512 per outer block, which is where the flops are and
-    // runs the fp32-MFMA GEMM at its long-K efficiency instead of its short-K one (tools/bench_sgemm.py).
-    const int NBO = 4 * NB;
-    SideStream* side = (!helper_streams_enabled()) ? nullptr : side_stream_for(st);
-    bool pending_side = false;
-    // The large products of K3 (far updates, triangular-inverse levels >= 512) run as split-bf16 products on the 16-bit
-    // MFMA pipe (gemm3.hip: fp32-level accuracy, 1.3-1.5x the fp32-MFMA kernel). option k3_fp32 keeps everything on
-    // the fp32 MFMA path.
-    const bool k3_x3 = !opt(OPT_K3_FP32);
-    const bool use_x3u = k3_x3, use_x3 = k3_x3, use_x3t = k3_x3;
-    const bool use_planes = !opt(OPT_K3_NO_PLANES);
-    const bool merge_far = !opt(OPT_K3_SPLIT_FAR);
-    const size_t xbuf_bytes = (size_t)(K / 2 + NB) * (K / 2 + NB) * 4;
-    // Inside an outer block the columns split into NEAR (the block's own, which the next factor step needs) and FAR (all
-    // the columns to its right, needed by the later far panel solves and by the block's far update). The near panel solve
-    // and near update stay on the caller's stream between the diagonal factorisations — three small latency-bound
-    // kernels per step; the far panel solve and far in-block update of the same step (128 x nfar products: the bulk of a
-    // step's work) run on the helper stream behind an event, concurrently with the next steps' chain. Same kernels, same
-    // arithmetic per element and the same order of the updates an element receives (all of step c before step c + 1 on
-    // either stream), so the factor is bit-identical with or without the helper stream.
-    auto panel_solve = [&](const float* Vb, int c0, int nb, int col0, int ncols, hipStream_t s_) -> int {
-        if (ncols <= 0) return LLMC_OK;
-        float* P = Wk + (size_t)c0 * K + col0;     // rows c0..c0+nb, cols col0..col0+ncols
-        SgemmArgs g{};
-        // P = V^T P  (op(A)[i][k] = V[k][i], lower triangular)
-        g.A = Vb; g.lda = NB; g.B = P; g.ldb = K; g.C = P; g.ldc = K;
-        g.M = g.M_last = nb; g.N = g.N_last = ncols; g.Kd = g.Kd_last = nb;
-        g.epilogue = SG_SET; g.a_lower = 1; g.batch = 1;
-        return sgemm_launch(g, true, false, s_);
-    };
-    // rows c0+nb .. oend of the trailing matrix, columns col0 .. col0+ncols:  C -= P[:, rows]^T P[:, cols]
-    auto inblock_update = [&](int c0, int nb, int oend, int col0, int ncols, hipStream_t s_) -> int {
-        const int mrows = oend - (c0 + nb);
-        if (mrows <= 0 || ncols <= 0) return LLMC_OK;
-        SgemmArgs u{};
-        u.A = Wk + (size_t)c0 * K + c0 + nb; u.lda = K;
-        u.B = Wk + (size_t)c0 * K + col0; u.ldb = K;
-        u.C = Wk + (size_t)(c0 + nb) * K + col0; u.ldc = K;
-        u.M = u.M_last = mrows; u.N = u.N_last = ncols; u.Kd = u.Kd_last = nb;
-        u.epilogue = SG_SUB; u.c_upper_only = col0 == c0 + nb ? 1 : 0; u.batch = 1;   // the far columns lie right of every row
-        return sgemm_launch(u, true, false, s_);
-    };
-    for (int k0 = 0; k0 < K; k0 += NBO) {
-        const int nbo = K - k0 < NBO ? K - k0 : NBO;
-        const int oend = k0 + nbo;
-        const int nfar = K - oend;
-        for (int c0 = k0; c0 < oend; c0 += NB) {
-            const int b = c0 / NB;
-            const int nb = K - c0 < NB ? K - c0 : NB;
-            float* Vb = Vbuf + (size_t)b * NB * NB;
-            hipLaunchKernelGGL(k_potrf_inv, dim3(1), dim3(256), (NB * PLD + 32 * PLD + 64) * sizeof(float), st, Wk, (int64_t)K, c0,
-                               nb, Vb, info_dev);
-            LLMC_LAUNCH_CHECK();
-            if (K - c0 - nb <= 0) break;
-            const int nnear = oend - (c0 + nb);
-            if (!side || nfar <= 0) {
-                // one stream: near and far columns in ONE panel solve and ONE update per step (the split costs two more
-                // launches per step, 1.3 ms over a K = 14336 factorisation, and buys nothing without a second stream)
-                int rc = panel_solve(Vb, c0, nb, c0 + nb, K - c0 - nb, st);
-                if (rc) return rc;
-                rc = inblock_update(c0, nb, oend, c0 + nb, K - c0 - nb, st);
-                if (rc) return rc;
-                continue;
-            }
-            int rc = panel_solve(Vb, c0, nb, c0 + nb, nnear, st);
-            if (rc) return rc;
-            rc = fork_to_side(side, st);      // the far part of this step: behind the near panel, beside the rest of the chain
-            if (rc) return rc;
-            pending_side = true;
-            rc = panel_solve(Vb, c0, nb, oend, nfar, side->side);
-            if (rc) return rc;
-            rc = inblock_update(c0, nb, oend, oend, nfar, side->side);
-            if (rc) return rc;
-            rc = inblock_update(c0, nb, oend, c0 + nb, nnear, st);
-            if (rc) return rc;
-        }
-        if (nfar > 0) {
-            // far trailing update T -= P^T P with P = rows k0..oend, cols oend..K (Kd = nbo), in two parts: the rows
-            // of the NEXT outer block on the main stream (its factor steps need them), the rows below on the side
-            // stream, overlapped with the next outer block's latency-bound diagonal / panel kernels.
-            float* P = Wk + (size_t)k0 * K + oend;
-            const int m1 = nfar < NBO ? nfar : NBO;
-            if (side && pending_side) {          // the block's far panels (and the previous block's side update) are complete
-                int rc = join_from_side(side, st);
-                if (rc) return rc;
-                pending_side = false;
-            }
-            SgemmArgs u{};
-            u.A = P; u.lda = K; u.B = P; u.ldb = K;
-            u.C = Wk + (size_t)oend * K + oend; u.ldc = K;
-            u.M = u.M_last = m1; u.N = u.N_last = nfar; u.Kd = u.Kd_last = nbo;
-            u.epilogue = SG_SUB; u.c_upper_only = 1; u.batch = 1;
-            const int m2 = nfar - m1;
-            SgemmArgs v{};
-            v.A = P + m1; v.lda = K; v.B = P + m1; v.ldb = K;
-            v.C = Wk + (size_t)(oend + m1) * K + oend + m1; v.ldc = K;
-            v.M = v.M_last = m2; v.N = v.N_last = m2; v.Kd = v.Kd_last = nbo;
-            v.epilogue = SG_SUB; v.c_upper_only = 1; v.batch = 1;
-            // Large far updates: the panel P is split ONCE into its three bf16 planes (in Xbuf, which only the inverse
-            // levels use) and the products copy planes instead of splitting P again in every tile (gemm3.hip, k_gemm3s).
-            // Same planes, same MFMA order: the factor is bit-identical either way. The previous block's side update
-            // (which reads the previous planes) was joined above.
-            // Without a helper stream the two parts are ONE product: the upper triangle of the whole trailing matrix (u's tiles
-            // are the first two tile rows of it, v's start at row and column 512 = whole tiles): one launch less per outer block
-            // and u's 216 tiles no longer run as a round of their own. Same tiles, same arithmetic.
-            const bool merged = !side && use_x3 && use_x3u && m2 > 0 && merge_far;
-            if (merged) u.M = u.M_last = nfar;
-            if (use_x3 && use_planes && nfar % 8 == 0 && (size_t)3 * nbo * nfar * 2 <= xbuf_bytes) {
-                SgemmArgs w = merged ? u : (m2 > 0 ? v : u);
-                w.planesA = w.planesB = Xbuf; w.ldp = nfar; w.plane_stride = (int64_t)nbo * nfar;
-                if (gemm3_uses_planes(w)) {
-                    int rc = gemm3_split_planes(P, K, nbo, nfar, Xbuf, nfar, (int64_t)nbo * nfar, st);
-                    if (rc) return rc;
-                    u.planesA = u.planesB = Xbuf;
-                    v.planesA = v.planesB = (const uint16_t*)Xbuf + m1;
-                    u.ldp = v.ldp = nfar;
-                    u.plane_stride = v.plane_stride = (int64_t)nbo * nfar;
-                }
-            }
-            int rc = use_x3u ? gemm3_tn_launch(u, st) : sgemm_launch(u, true, false, st);
-            if (rc) return rc;
-            if (m2 > 0 && !merged) {
-                if (side) {
-                    rc = fork_to_side(side, st);   // P is final on main at this point
-                    if (rc) return rc;
-                    rc = use_x3 ? gemm3_tn_launch(v, side->side) : sgemm_launch(v, true, false, side->side);
-                    if (rc) return rc;
-                    pending_side = true;
-                } else {
-                    rc = use_x3 ? gemm3_tn_launch(v, st) : sgemm_launch(v, true, false, st);
-                    if (rc) return rc;
-                }
-            }
-        }
-    }
-    if (side && pending_side) {
-        int rc = join_from_side(side, st);
-        if (rc) return rc;
-    }
-    (void)nblk;
-    // ---- V = U'^-1: inverted diagonal blocks, then doubling levels
-    hipLaunchKernelGGL(k_place_diag_inv, dim3((K + NB - 1) / NB), dim3(256), 0, st, Wk, (int64_t)K, K, (const float*)Vbuf, 0);
-    LLMC_LAUNCH_CHECK();
-    if (use_x3t && use_g6 && K > GEMM6_MIN_H) {
-        hipLaunchKernelGGL(k_zero_subdiag, dim3((K + 255) / 256), dim3(256), 0, st, Wk, (int64_t)K, K);
-        LLMC_LAUNCH_CHECK();
-    }
-    for (int64_t h = NB; h < K; h *= 2) {
-        const int npairs = (int)((K - h + 2 * h - 1) / (2 * h));  // pairs with a non-empty right block
-        if (npairs <= 0) break;
-        const int64_t o_last = (int64_t)(npairs - 1) * 2 * h;
-        const int n2_last = (int)((K - o_last - h) < h ? (K - o_last - h) : h);
-        const int64_t stride = 2 * h * ((int64_t)K + 1);
-        // X = A^-1 C
-        SgemmArgs x{};
-        x.A = Wk; x.lda = K; x.sA = stride;                 // A^-1 at (o, o), upper
-        x.B = Wk + h; x.ldb = K; x.sB = stride;             // C at (o, o+h)
-        // X is [h x n2]: with one pair its leading dimension shrinks to n2 (keeps X within K^2/4 floats)
-        const int64_t ldX = npairs == 1 ? ((n2_last + 3) / 4) * 4 : h;
-        x.C = Xbuf; x.ldc = ldX; x.sC = h * h;
-        x.M = x.M_last = (int)h; x.N = (int)h; x.N_last = n2_last; x.Kd = x.Kd_last = (int)h;
-        x.epilogue = SG_SET; x.a_upper = 1; x.batch = npairs;
-        const bool lvl_x3 = use_x3t && h >= 512;   // small levels are latency-bound: the fp32 kernels stay
-        // large, deep levels: operands split once into stacked bf16 planes, product on the one-wave-per-SIMD GEMM
-        const bool lvl_g6 = lvl_x3 && use_g6 && h >= GEMM6_MIN_H && h % 256 == 0 && n2_last % 256 == 0;
-        int rc = LLMC_OK;
-        if (lvl_g6) {
-            for (int z = 0; z < npairs && !rc; ++z) {
-                const int n2 = z == npairs - 1 ? n2_last : (int)h;
-                rc = gemm6_launch(x.A + z * stride, K, x.B + z * stride, K, Xbuf + (int64_t)z * h * h, ldX, (int)h, n2, (int)h,
-                                  1, 0, 1.0f, G6buf, st);
-                if (rc) return rc;
-                rc = gemm6_launch(Xbuf + (int64_t)z * h * h, ldX, Wk + h * ((int64_t)K + 1) + z * stride, K,
-                                  Wk + h + z * stride, K, (int)h, n2, n2, 0, 1, -1.0f, G6buf, st);
-            }
-            if (rc) return rc;
-            continue;
-        }
-        rc = lvl_x3 ? gemm3_launch(x, false, st) : sgemm_launch(x, false, false, st);
-        if (rc) return rc;
-        // C = -X B^-1
-        SgemmArgs y{};
-        y.A = Xbuf; y.lda = ldX; y.sA = h * h;
-        y.B = Wk + h * ((int64_t)K + 1); y.ldb = K; y.sB = stride;   // B^-1 at (o+h, o+h), upper
-        y.C = Wk + h; y.ldc = K; y.sC = stride;
-        y.M = y.M_last = (int)h; y.N = (int)h; y.N_last = n2_last; y.Kd = (int)h; y.Kd_last = n2_last;
-        y.epilogue = SG_NEG; y.b_upper = 1; y.batch = npairs;
-        rc = lvl_x3 ? gemm3_launch(y, false, st) : sgemm_launch(y, false, false, st);
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(k_antitranspose, tgrid, dim3(256), 0, st, (const float*)Wk, rev ? Uout : A, K, 1);
-    LLMC_LAUNCH_CHECK();
-    return LLMC_OK;
+// Test hook (include/llmc_hip_test.h): K3's launch plan for this K under the calling thread's options, without a device.
+extern "C" int llmc_test_chol_plan(int64_t K, int rev, int with_lanes, int32_t* out, int cap) {
+    LLMC_REQUIRE(out && cap >= 0, "chol plan: null output");
+    PlanRec rec{out, cap, 0, CP_W, with_lanes != 0, CP_BLANK};
+    // addresses that are only ever offset and compared, never read: 256-B aligned like device allocations, far apart
+    float* const base = (float*)(uintptr_t)((uint64_t)1 << 40);
+    const size_t span = (size_t)1 << 36;
+    const int rc = chol_inv_upper_impl(base, rev ? base + span : nullptr, K, base + 2 * span, (int32_t*)(base + 3 * span), nullptr, &rec);
+    return rc ? rc : rec.n;
 }
-

@@ -12,7 +12,7 @@
 // Trailing update W[:, i2:] -= Err1 @ U[i1:i2, i2:] runs on the fp32 MFMA pipe (sgemm.hip) with the
 // k-ordered fma chain that reproduces the reference's CPU sgemm bit for bit.
 #include "gptq_block_kernels.h"
-#include "pipe_streams.h"
+#include "pipe_lanes.h"
 
 using namespace llmc;
 
@@ -41,20 +41,14 @@ extern "C" int llmc_gptq_quantize(float* W, const float* Hinv, int64_t R, int64_
 // with, so each block's groups are searched on the running panel right before its in-block kernel, on the same stream.
 struct MseSearch { int round_zp, nsteps, grid; float norm; };
 
-#define LLMC_TRY(expr) do { if (int _rc = (expr)) return _rc; } while (0)
-
 // The host schedule (how it came about: DESIGN.md §3 "K4's host schedule"). Every weight receives the blocks' updates in the
 // reference's order (block 0, 1, 2, ...), each as "W -= chain over the block's 128 k" (gptq.py:244): columns of the current outer
 // group right after each block (near product), columns beyond it once per group (far product: GRP phases of 128 k, the C tile in
 // registers), cut into PIECES on lanes. Column tiles are independent and every kernel that may run a piece computes an element the
 // same way (one accumulator per phase from +0 in ascending k, one rounding C - acc): any cut on any lane gives the same bits as
 // long as per element the updates arrive in block order — which the waits in gptq_cols_impl state and tests replay from the plans.
-enum Lane {
-    CHAIN = 0,   // in-block kernel and near product per block, per group the far piece the next group needs. The caller's stream
-    BULK = 1,    // far pieces beyond the next group: a helper stream (pipe_streams.h), or without helper streams the chain stream
-    CALLER = 2,  // the caller's stream where the chain is not (NULL-stream caller with CU-masked helpers: pipe_chain_stream)
-    RIDE = 3     // no stream: on the in-block launches of the NEXT group (k_gptq_block_riders), one slice per launch
-};
+// The lanes (pipe_lanes.h): CHAIN carries the in-block kernel and near product per block and per group the far piece the next
+// group needs; BULK the far pieces beyond the next group; RIDE pieces go on the in-block launches of the NEXT group.
 struct Piece { int64_t c0, c1; int k0, k1; Lane lane; };    // columns [c0, c1), the group's err columns [k0, k1) (whole 128-k phases)
 static constexpr int CARRIERS = GRP;      // in-block launches of a whole group
 static_assert(CARRIERS % RIDER_PASSES == 0 && GRP % RIDER_PASSES == 0, "a group's carrying launches and phases divide into the passes");
@@ -137,70 +131,18 @@ struct ColCall {
 // The launches of one call in issue order, for tests: with a recorder the loop launches nothing and touches no device. The records
 // are laid out as include/llmc_hip_test.h says: PLAN_W int32 for the one-stream plan, one more (the lane) for the pipelined plan,
 // which also has event rows (the event's id where a launch has its group).
-enum { PLAN_BLOCK = 0, PLAN_NEAR = 1, PLAN_NEAR_FAR = 2, PLAN_FAR = 3, PLAN_FLUSH = 4, PLAN_RECORD = 5, PLAN_WAIT = 6, PLAN_W = 12 };
-struct PlanRec {
-    int32_t* out; int cap, n, width;      // width: PLAN_W, or PLAN_W + 1 with lanes and events
-    void add(int lane, int kind, int group, int64_t w0 = 0, int64_t w1 = 0, int err_rd = -1, int err_wr = -1, int rgroup = -1,
-             int64_t r0 = 0, int64_t r1 = 0, int rerr = -1, int k0 = 0, int k1 = 0) {
-        if (n < cap) {
-            const int32_t v[PLAN_W + 1] = {kind, group, (int32_t)w0, (int32_t)w1, err_rd, err_wr, rgroup, (int32_t)r0, (int32_t)r1, rerr, k0, k1, lane};
-            memcpy(out + (size_t)n * width, v, (size_t)width * sizeof(int32_t));
-        }
-        ++n;
-    }
-};
-
-// The chain and bulk streams of a call, and the events between them. Three forms: real helper streams (PipeStreams); one stream,
-// where both lanes are the caller's stream and record / wait do nothing; the pipelined plan, where an event is an integer id that
-// is written down. Either way the column loop states its dependencies once.
-struct Ev { hipEvent_t h; int id; };      // {}: nothing to wait for
-struct Lanes {
-    hipStream_t s[3];
-    PipeStreams* ps = nullptr; PlanRec* plan = nullptr; int ids = 0;
-    Lanes(hipStream_t st, PlanRec* rec) : s{st, st, st} {
-        if (rec && rec->width > PLAN_W) {
-            plan = rec;
-            s[BULK] = (hipStream_t)(uintptr_t)1;     // only ever compared (lane_of): a recorder launches nothing
-        } else if (!rec && helper_streams_enabled() && (ps = pipe_streams_for(st))) {
-            s[CHAIN] = pipe_chain_stream(ps, st);
-            s[BULK] = ps->bulk;
-        }
-    }
-    bool piped() const { return s[BULK] != s[CHAIN]; }
-    int lane_of(hipStream_t st) const { return st == s[CHAIN] ? CHAIN : BULK; }
-    int record(Lane l, Ev* e) {
-        if (ps) return ps->record(s[l], &e->h);
-        if (plan) plan->add(lane_of(s[l]), PLAN_RECORD, e->id = ++ids);
-        return LLMC_OK;
-    }
-    int wait(Lane l, const Ev& e) {
-        if (ps) return pipe_wait(s[l], e.h);
-        if (plan && e.id) plan->add(lane_of(s[l]), PLAN_WAIT, e.id);
-        return LLMC_OK;
-    }
-    int order(Lane first, Lane then) {      // what `then` issues from here on comes after everything `first` has issued
-        Ev e{};
-        LLMC_TRY(record(first, &e));
-        return wait(then, e);
-    }
-    // Both lanes start behind the caller's earlier work, and everything is fenced back into the caller's stream before the entry
-    // point returns: the C ABI contract (complete, in stream order, on the stream passed in)
-    int fork() {
-        Ev e{};
-        LLMC_TRY(record(CALLER, &e));
-        if (s[CHAIN] != s[CALLER]) LLMC_TRY(wait(CHAIN, e));
-        return wait(BULK, e);
-    }
-    int join() {
-        LLMC_TRY(order(BULK, CHAIN));
-        return s[CHAIN] == s[CALLER] ? LLMC_OK : order(CHAIN, CALLER);
-    }
-};
+enum { PLAN_BLOCK = 0, PLAN_NEAR = 1, PLAN_NEAR_FAR = 2, PLAN_FAR = 3, PLAN_FLUSH = 4, PLAN_W = 12 };
+static const int32_t PLAN_BLANK[PLAN_W] = {0, 0, 0, 0, -1, -1, -1, 0, 0, -1, 0, 0};
 
 // One place that either launches or, for a plan, writes down what WOULD be launched — read back from the very arguments the
 // kernel gets (columns from C, k range from B's row, err buffer from A, lane from the stream), not from the loop's own bookkeeping.
 struct Sink {
     const ColCall& o; const Lanes& ln; PlanRec* rec;
+    void add(int lane, int kind, int group, int64_t w0, int64_t w1, int err_rd, int err_wr, int rgroup, int64_t r0, int64_t r1, int rerr,
+             int k0, int k1) const {
+        const int32_t v[PLAN_W] = {kind, group, (int32_t)w0, (int32_t)w1, err_rd, err_wr, rgroup, (int32_t)r0, (int32_t)r1, rerr, k0, k1};
+        rec->row(v, lane);
+    }
     int err_index(const float* pe) const { return (int)((size_t)(pe - o.ErrBuf[0]) / ((size_t)o.Rp * GW)); }
     void k_range(int group, const float* B, int64_t c0, int kd, int* k0, int* k1) const {
         *k0 = (int)((B - o.U - c0) / o.K - (int64_t)group * GW);
@@ -212,7 +154,7 @@ struct Sink {
         const int64_t c0 = g.C - o.W;
         int k0 = 0, k1 = 0;
         if (kind != PLAN_NEAR) k_range(group, g.B, c0, g.Kd, &k0, &k1);
-        rec->add(ln.lane_of(st), kind, group, c0, c0 + g.N, err_index(g.A), -1, -1, 0, 0, -1, k0, k1);
+        add(ln.lane_of(st), kind, group, c0, c0 + g.N, err_index(g.A), -1, -1, 0, 0, -1, k0, k1);
         return LLMC_OK;
     }
     // the in-block kernel of block a.i1 on the chain, with the rider tiles `ra` of group `rgroup` if any
@@ -225,7 +167,7 @@ struct Sink {
                 r0 = ra->w.C - o.W, r1 = r0 + (int64_t)ra->w.tn * 128, rerr = err_index(ra->w.A);
                 k_range(rgroup, ra->w.B, r0, ra->w.nst * wide::W_K, &k0, &k1);
             }
-            rec->add(CHAIN, PLAN_BLOCK, group, a.i1, a.i1 + a.count, -1, err_index(a.Err), rgroup, r0, r1, rerr, k0, k1);
+            add(CHAIN, PLAN_BLOCK, group, a.i1, a.i1 + a.count, -1, err_index(a.Err), rgroup, r0, r1, rerr, k0, k1);
             return LLMC_OK;
         }
         // one translation unit per quantizer kind holds its kernels (gptq_block_kernels.h)
@@ -388,9 +330,9 @@ extern "C" int llmc_gptq_quantize_mse(float* W, const float* Hinv, int64_t R, in
 
 // Test hooks (include/llmc_hip_test.h): the launch plan of the column loop for these shapes under the calling thread's options,
 // without a device — on one stream (width PLAN_W) or with helper streams (PLAN_W + 1: lanes and events).
-static int gptq_plan(int64_t R, int64_t K, int64_t n_quant, int64_t group_size, int static_groups, int32_t* out, int cap, int width) {
+static int gptq_plan(int64_t R, int64_t K, int64_t n_quant, int64_t group_size, int static_groups, int32_t* out, int cap, bool lanes) {
     LLMC_REQUIRE(out && cap >= 0, "gptq plan: null output");
-    PlanRec rec{out, cap, 0, width};
+    PlanRec rec{out, cap, 0, PLAN_W, lanes, PLAN_BLANK};
     // addresses that are only ever offset and compared, never read: 256-B aligned like device allocations, far apart
     float* const base = (float*)(uintptr_t)((uint64_t)1 << 40);
     const size_t span = (size_t)1 << 36;
@@ -400,8 +342,8 @@ static int gptq_plan(int64_t R, int64_t K, int64_t n_quant, int64_t group_size, 
     return rc ? rc : rec.n;
 }
 extern "C" int llmc_test_gptq_rider_plan(int64_t R, int64_t K, int64_t n_quant, int64_t group_size, int static_groups, int32_t* out, int cap) {
-    return gptq_plan(R, K, n_quant, group_size, static_groups, out, cap, PLAN_W);
+    return gptq_plan(R, K, n_quant, group_size, static_groups, out, cap, false);
 }
 extern "C" int llmc_test_gptq_pipe_plan(int64_t R, int64_t K, int64_t n_quant, int64_t group_size, int static_groups, int32_t* out, int cap) {
-    return gptq_plan(R, K, n_quant, group_size, static_groups, out, cap, PLAN_W + 1);
+    return gptq_plan(R, K, n_quant, group_size, static_groups, out, cap, true);
 }

@@ -1,12 +1,14 @@
-// pipe_streams.h — helper streams of the pipelined K4 schedule (round 4).
+// pipe_streams.h — the helper streams of the host-scheduled GPTQ phases K3 (cholesky.hip) and K4 (gptq_loop.hip), driven through
+// pipe_lanes.h. On one caller stream both share one set: they never overlap there, each entry point joins before it returns.
 //
 // K4 is a latency-bound CHAIN (the in-block column kernel and the update of its group's columns, per 128-column block) plus a
 // throughput-bound BULK product (the far update of everything beyond the next group) that depends on the chain only group
 // by group. The bulk product runs on a helper stream of its own, the columns the chain needs next first.
 // Measured on MI355X (gpurun_out/r04c, r04e; profiles/r04_stream_experiments.txt):
-//   * plain non-blocking helper streams: K4 of down_proj 12.1 -> 10.9-11.4 ms; the same structure for K3 (three helper
-//     streams, the inverse behind the factorisation) measured EQUAL to the single-stream schedule (21.9 ms) and was removed:
-//     K3's "latency-bound" steps are wide, inefficient kernels that already occupy every CU;
+//   * plain non-blocking helper streams: K4 of down_proj 12.1 -> 10.9-11.4 ms. K3 keeps ONE helper (the far columns of a factor
+//     step and the far update beyond the next outer block); three helpers with the inverse behind the factorisation measured
+//     EQUAL to the single-stream schedule (21.9 ms) and were removed: K3's "latency-bound" steps are wide, inefficient kernels
+//     that already occupy every CU;
 //   * CU-MASKED helpers (hipExtStreamCreateWithCUMask leaving two CUs per XCD to the chain; LLMC_SIDE_CU_MASK=1): the mask
 //     works (240 of 256 CUs used; a small kernel beside a saturating one starts in 10 us instead of 21 us) but buys nothing
 //     end to end, and masked streams are BLOCKING streams — their mere existence slows every launch on the NULL stream
@@ -27,7 +29,7 @@
 namespace llmc {
 
 struct PipeStreams {
-    hipStream_t bulk = nullptr;    // K4's far update beyond the next group
+    hipStream_t bulk = nullptr;    // K4's far update beyond the next group; K3's far columns of a step and far update beyond the next block
     hipStream_t chain = nullptr;   // stands in for the caller's stream when that is the NULL stream (see pipe_chain_stream)
     static constexpr int NEV = 512;
     hipEvent_t ev[NEV] = {};
@@ -35,9 +37,10 @@ struct PipeStreams {
     bool ok = false;
     bool masked = false;
 
-    // a fresh event recorded on `s`. The pool is a ring: an event is re-recorded NEV records later; every wait on it is
-    // enqueued within a few outer blocks (< 64 records per call: llmc_gptq_quantize records 3 per 512-column group and waits on
-    // each within three groups), and a wait captures the record that precedes it.
+    // a fresh event recorded on `s`. The pool is a ring: an event is re-recorded NEV records later, and a wait captures the record
+    // that precedes it. llmc_gptq_quantize records 3 per 512-column group and waits on each within three groups (9 records). K3
+    // records 7 per 512-row outer block — K = 28672: 56 blocks, 394 records per call with entry and exit — and enqueues every wait
+    // directly behind its record, but for planes_read, waited on one block (7 records) later: reusing a ring entry stays harmless.
     int record(hipStream_t s, hipEvent_t* out) {
         hipEvent_t e = ev[next.fetch_add(1u, std::memory_order_relaxed) % NEV];
         LLMC_HIP_CHECK(hipEventRecord(e, s));

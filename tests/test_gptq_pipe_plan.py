@@ -48,14 +48,15 @@ def conflict(a, b):
     return None
 
 
-def replay(recs):
-    """Vector clocks: clock[l][m] = how many of lane m's launches are ordered before the next launch of lane l."""
+def replay(recs, footprint=footprint, lane_col=12):
+    """Vector clocks: clock[l][m] = how many of lane m's launches are ordered before the next launch of lane l. (The footprint
+    function and the lane's column are parameters for tests/test_chol_plan.py, which replays K3's plans the same way.)"""
     issued = [0, 0]
     clock = [[0, 0], [0, 0]]
     events = {}
     launches = []            # (lane, index on its lane, clock at issue, footprint)
     for row in recs.tolist():
-        kind, lane = row[0], row[12]
+        kind, lane = row[0], row[lane_col]
         assert lane in (CHAIN, BULK)
         if kind == RECORD:
             assert row[1] not in events and row[1] > 0, 'an event id recorded twice'
@@ -71,7 +72,7 @@ def replay(recs):
     return launches, issued, clock
 
 
-def unordered_conflicts(launches):
+def unordered_conflicts(launches, conflict=conflict):
     bad = []
     for j, (lj, _, cj, fj) in enumerate(launches):
         for i in range(j):

@@ -25,7 +25,9 @@ int llmc_test_gemm3(const float* A, const float* B, float* C, int64_t lda, int64
 /* The k-major product (TA) of llmc_test_gemm3 in the form K3's large far updates use: both operands are first split into
  * their three bf16 planes in `ws` (6 * Kd * roundup8(max(M, N)) * 2 bytes, 16-B aligned), then multiplied by the
  * producer / MFMA-wave kernel (gemm3.hip, k_gemm3s). M % 8 == 0, N % 8 == 0, Kd a multiple of 64 and >= 128. Returns
- * LLMC_ENOTSUP when the shape is not eligible (too few tiles unless LLMC_GEMM3S_MIN_TILES lowers the bar). */
+ * LLMC_ENOTSUP when the product would not run on the planes: the shape is not eligible (too few tiles unless the option
+ * gemm3s_min_tiles lowers the bar), or the launcher would refuse the arguments (misaligned operands, N % 4 != 0); nothing is split
+ * or launched then. */
 int llmc_test_gemm3_planes(const float* A, const float* B, float* C, int64_t lda, int64_t ldb, int64_t ldc, int M, int N,
                            int Kd, int epilogue, int c_upper_only, void* ws, llmc_stream_t stream);
 /* tools/probes/gemm3s_probe.py: the s_memtime stamps (8 waves x 128 slots, int64) one workgroup of the last k_gemm3s
@@ -63,6 +65,19 @@ int llmc_test_gptq_pipe_plan(int64_t R, int64_t K, int64_t n_quant, int64_t grou
  * llmc_test_gptq_pipe_plan: kind 5 / 6, the event's id in [1], every buffer -1, the lane last. Pure host call. Returns the number
  * of records (only the first `cap` are written) or an error. */
 int llmc_test_chol_plan(int64_t K, int rev, int with_lanes, int32_t* out, int cap);
+/* tests/test_gemm_route.py: which kernel llmc_test_sgemm / llmc_test_gemm3 / K3 / K4 would launch for a product, and how, under the
+ * calling thread's options. Pure host call: the operands are fake addresses, 256-B aligned and far apart. in, 30 int64:
+ *   [0] family (0 sgemm, 1 gemm3), [1..3] M, N, Kd, [4..6] lda, ldb, ldc, [7] TA, [8] TB (sgemm only), [9] epilogue,
+ *   [10..13] a_upper, a_lower, b_upper, c_upper_only, [14] phase_len, [15] batch, [16..18] M_last, N_last, Kd_last, [19..21] sA, sB,
+ *   sC, [22] planes given, [23] ldp, [24] plane_stride, [25] aliasing (0 none, 1 C == B, 2 C == A), [26..29] bytes added to the
+ *   addresses of A, B, C, both planes.
+ * out, 18 int32: status (0 or the error the launcher would return), kernel (0 k_sgemm, 1 k_sgemm_shortk, 2 k_sgemm_shortk_phased,
+ *   3 / 4 k_sgemm_wide<2> / <4>, 5 k_gemm3, 6 k_gemm3s, 7 k_gemm3s on planes, 8 k_gemm3w), grid x, y, z, threads, dynamic LDS bytes,
+ *   ta, tb, phased, edge (k_sgemm's instantiation), effective phase_len, planes_dma, sm_log, sn_log, sbm, nsb (the wide kernels'
+ *   tile blocks), and the k_sgemm_wide form the arguments qualify for (0, 2, 4) whether or not a short-K kernel comes first.
+ *   Everything after status is meaningful only for status 0 and a launch. Returns 1 when nothing would be launched (M, N or
+ *   batch <= 0), else 0. */
+int llmc_test_gemm_route(const int64_t* in, int32_t* out);
 
 #ifdef __cplusplus
 }

@@ -713,7 +713,7 @@ struct FactorCall {
     // the planes of P (in Xbuf, which otherwise only the inverse levels use) are worth it when the last piece would run on them
     bool split_planes(int k0, int oend, int r0) const {
         const int nfar = K - oend;
-        return x3 && planes && nfar % 8 == 0 && (size_t)3 * (oend - k0) * nfar * 2 <= xbuf_bytes && gemm3_uses_planes(far(k0, oend, r0, K, true));
+        return x3 && planes && nfar % 8 == 0 && (size_t)3 * (oend - k0) * nfar * 2 <= xbuf_bytes && gemm3_route(far(k0, oend, r0, K, true), true).planes();
     }
     // level h of V = U'^-1: pairs [[A, C], [0, B]] of h-blocks with a non-empty right block, C = -A^-1 C B^-1 through X = A^-1 C
     Level level(int64_t h) const {
@@ -791,13 +791,13 @@ struct FactorSink {
     int product(int kind, const SgemmArgs& g, int form, bool TA, Lane lane) const {
         if (g.M <= 0 || g.N <= 0) return LLMC_OK;
         const hipStream_t st = ln.s[lane];
-        if (!rec) return form == F_SGEMM ? sgemm_launch(g, TA, false, st) : TA ? gemm3_tn_launch(g, st) : gemm3_launch(g, false, st);
+        if (!rec) return form == F_SGEMM ? sgemm_launch(g, TA, false, st) : gemm3_launch(g, TA, st);
         auto hull = [&](const float* p, int64_t ld, int64_t s, int r, int c, int rl, int cl) {
             const Rect a = rect(p, ld, r, c), b = rect(p + (g.batch - 1) * s, ld, rl, cl);
             return Rect{a.buf, a.r0, b.r1, a.c0, b.c1};
         };
         auto planes = [&](const void* p, int n) { return rect(p, 1, 1, (2 * g.plane_stride + (g.Kd - 1) * g.ldp + n + 1) / 2); };
-        const bool pl = form == F_GEMM3 && TA && gemm3_uses_planes(g);
+        const bool pl = form == F_GEMM3 && gemm3_route(g, TA).planes();
         return add(kind, form, lane, hull(g.C, g.ldc, g.sC, g.M, g.N, g.M_last, g.N_last),
                    pl ? planes(g.planesA, g.M) : TA ? hull(g.A, g.lda, g.sA, g.Kd, g.M, g.Kd_last, g.M_last) : hull(g.A, g.lda, g.sA, g.M, g.Kd, g.M_last, g.Kd_last),
                    pl ? planes(g.planesB, g.N) : hull(g.B, g.ldb, g.sB, g.Kd, g.N, g.Kd_last, g.N_last));

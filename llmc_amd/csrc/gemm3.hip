@@ -23,8 +23,7 @@
 
 namespace llmc {
 
-static constexpr int G3B = 128;               // tile edge
-static constexpr int G3K = 32;                // K-step
+// tile edge G3B = 128 and K-step G3K = 32: sgemm.h
 static constexpr int G3ROW = G3B * 2;         // bytes per k-row of one plane
 static constexpr int G3PLANE = G3K * G3ROW;   // 8 KiB
 static constexpr int G3PANEL = 3 * G3PLANE;   // hi | mid | lo
@@ -253,11 +252,11 @@ __global__ __launch_bounds__(256, 2) void k_gemm3(SgemmArgs a) {
 // strided 4-B loads and stores per lane, 30 us of a 78-us tile with nothing else resident on the CU.
 // No operand hints (a_upper / a_lower / b_upper): the far updates have none.
 // ---------------------------------------------------------------------------------------------
-static constexpr int S_BM = 256, S_BN = 128;
+// tile S_BM = 256 x S_BN = 128: sgemm.h
 static constexpr int S_AROW = S_BM * 2, S_BROW = S_BN * 2;                 // bytes per k-row of one plane
 static constexpr int S_APLANE = G3K * S_AROW, S_BPLANE = G3K * S_BROW;     // 16 KiB, 8 KiB
 static constexpr int S_BUF = 3 * S_APLANE + 3 * S_BPLANE;                  // 72 KiB
-static constexpr int S_LDS = 2 * S_BUF;
+static_assert(S_LDS == 2 * S_BUF, "two buffers");
 // LDS-DMA form of the planes kernel (round 6): a ring of FOUR 16-k slots instead of two 32-k buffers, so that a slot's copies are
 // requested three steps before its MFMAs (a DMA round trip is longer than one step's MFMAs)
 static constexpr int R_K = 16;
@@ -764,33 +763,6 @@ __global__ __launch_bounds__(512, 1) void k_gemm3s(SgemmArgs a) {
     G3S_STAMP(121);
 }
 
-// the specialised kernel for large k-major products without operand hints; everything else stays on k_gemm3
-static bool gemm3s_eligible(const SgemmArgs& a) {
-    if (opt(OPT_GEMM3_NOSPEC)) return false;
-    if (a.a_upper || a.a_lower || a.b_upper) return false;
-    if ((((uintptr_t)a.C) & 15) || a.ldc % 4 || a.sC % 4) return false;            // 16-B accesses to C
-    if ((int64_t)S_BM * a.ldc * 4 >= (int64_t)0x7fffff00) return false;             // 32-bit offsets inside a C tile
-    const int64_t kd = a.Kd > a.Kd_last ? a.Kd : a.Kd_last;
-    const bool pre = a.planesA != nullptr;
-    if (a.Kd % (2 * G3K) || a.Kd_last % (2 * G3K) || a.Kd < 4 * G3K || a.Kd_last < 4 * G3K) return false;   // an even number of K-steps, >= 4
-    if (pre) {
-        if (a.batch != 1) return false;                                             // the planes of ONE panel
-        if (a.ldp % 8 || a.plane_stride % 8 || (((uintptr_t)a.planesA | (uintptr_t)a.planesB) & 15)) return false;
-        if ((2 * a.plane_stride + (kd + G3K) * a.ldp) * 2 >= (int64_t)0x7fffff00) return false;
-    } else {
-        const int64_t ld = a.lda > a.ldb ? a.lda : a.ldb;
-        if ((kd + G3K) * ld * 4 >= (int64_t)0x7fffff00) return false;   // 32-bit offsets from the tile's first element
-    }
-    // one workgroup per CU: worth it once the tiles that do work come near filling the chip
-    const int64_t tm = (a.M + S_BM - 1) / S_BM, tn = (a.N + S_BN - 1) / S_BN;
-    const int64_t tiles = a.c_upper_only ? tm * tn - tm * (tm - 1) : tm * tn;      // row r of tiles skips its first 2r columns
-    const int mt = opt(OPT_GEMM3S_MIN_TILES);               // the tests lower it to reach the kernel with small shapes
-    const int min_tiles = mt > 0 ? mt : (pre ? 48 : 256);   // bench: 48 -> 93.75, 160 -> 93.98 / 94.20, 600 -> 94.48, never -> 95.14 ms per step
-    return tiles * a.batch >= min_tiles;
-}
-
-bool gemm3_uses_planes(const SgemmArgs& a) { return a.planesA != nullptr && gemm3s_eligible(a); }
-
 // planes of a k-major fp32 panel (rows x n, n % 8 == 0) for the PRE form: 3 * rows * ldp bf16 at `planes`
 int gemm3_split_planes(const float* P, int64_t ld, int rows, int n, void* planes, int64_t ldp, int64_t plane_stride, hipStream_t st) {
     LLMC_REQUIRE(n % 8 == 0 && ld % 4 == 0 && ldp % 8 == 0 && plane_stride % 8 == 0 && (((uintptr_t)P | (uintptr_t)planes) & 15) == 0,
@@ -803,44 +775,31 @@ int gemm3_split_planes(const float* P, int64_t ld, int rows, int n, void* planes
 }
 
 int gemm3_launch(const SgemmArgs& a, bool TA, hipStream_t st) {
-    if (a.M <= 0 || a.N <= 0 || a.batch <= 0) return LLMC_OK;
-    LLMC_REQUIRE(a.phase_len == 0, "gemm3: no phased mode");
-    LLMC_REQUIRE((a.lda % 4 == 0) && (a.ldb % 4 == 0) && (a.N % 4 == 0) && (a.N_last % 4 == 0) &&
-                     (!TA || (a.M % 4 == 0 && a.M_last % 4 == 0)) && (((uintptr_t)a.A & 15) == 0) &&
-                     (((uintptr_t)a.B & 15) == 0) && (a.sA % 4 == 0) && (a.sB % 4 == 0),
-                 "gemm3: operands must be 16-B aligned with ld and sizes multiples of 4");
-    LLMC_REQUIRE((const void*)a.C != (const void*)a.B && (const void*)a.C != (const void*)a.A, "gemm3: no in-place product");
-    if (TA && gemm3s_eligible(a) && gemm3w_eligible(a)) return gemm3w_launch(a, st);
-    if (TA && gemm3s_eligible(a)) {
-        SgemmArgs b = a;
-        b.planes_dma = opt(OPT_GEMM3S_NO_DMA) ? 0 : 1;
-        dim3 sgrid((a.N + S_BN - 1) / S_BN, (a.M + S_BM - 1) / S_BM, a.batch);
+    const GemmRoute r = gemm3_route(a, TA);
+    if (r.status != LLMC_OK) set_last_error_msg(r.msg);
+    if (r.status != LLMC_OK || r.empty) return r.status;
+    SgemmArgs b = a;
+    void (*k)(SgemmArgs) = nullptr;
+    const bool pre = r.kernel == GK_GEMM3S_PRE;
+    switch (r.kernel) {      // k_gemm3s before k_gemm3: the order the device code holds them
+    case GK_GEMM3W: return gemm3w_launch(a, r, st);
+    case GK_GEMM3S: case GK_GEMM3S_PRE: {
+        b.planes_dma = r.planes_dma;
+        k = pre ? k_gemm3s<0, true> : k_gemm3s<0, false>;
 #ifdef LLMC_LAB
         const char* dbg = lab_env("LLMC_GEMM3S_DBG");
         const int d = dbg ? atoi(dbg) : 0;
-#else
-        const int d = 0;
+        if (d == 2) k = pre ? k_gemm3s<2, true> : k_gemm3s<2, false>;
+        if (d == 4) k = pre ? k_gemm3s<4, true> : k_gemm3s<4, false>;
 #endif
-#define LLMC_G3S(D, PRE) do { if (int rc = ensure_dynamic_lds((const void*)k_gemm3s<D, PRE>, S_LDS)) return rc; \
-                              hipLaunchKernelGGL((k_gemm3s<D, PRE>), sgrid, dim3(512), S_LDS, st, b); } while (0)
-#ifdef LLMC_LAB
-        if (a.planesA) { if (d == 2) LLMC_G3S(2, true); else if (d == 4) LLMC_G3S(4, true); else LLMC_G3S(0, true); }
-        else { if (d == 2) LLMC_G3S(2, false); else if (d == 4) LLMC_G3S(4, false); else LLMC_G3S(0, false); }
-#else
-        (void)d;
-        if (a.planesA) LLMC_G3S(0, true); else LLMC_G3S(0, false);
-#endif
-#undef LLMC_G3S
-        LLMC_LAUNCH_CHECK();
-        return LLMC_OK;
+        if (int rc = ensure_dynamic_lds((const void*)k, r.lds)) return rc;
+    } break;
+    default: k = TA ? k_gemm3<true> : k_gemm3<false>;
     }
-    dim3 grid((a.N + G3B - 1) / G3B, (a.M + G3B - 1) / G3B, a.batch);
-    if (TA) hipLaunchKernelGGL((k_gemm3<true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((k_gemm3<false>), grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k, dim3(r.gx, r.gy, r.gz), dim3(r.threads), r.lds, st, b);
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;
 }
-int gemm3_tn_launch(const SgemmArgs& a, hipStream_t st) { return gemm3_launch(a, true, st); }
 
 }  // namespace llmc
 
@@ -860,7 +819,7 @@ extern "C" int llmc_test_gemm3_planes(const float* A, const float* B, float* C, 
     a.ldp = ldp; a.plane_stride = ps;
     a.planesA = ws;
     a.planesB = (const char*)ws + 3 * ps * 2;
-    if (!llmc::gemm3_uses_planes(a)) return LLMC_ENOTSUP;
+    if (!llmc::gemm3_route(a, true).planes()) return LLMC_ENOTSUP;
     if (int rc = llmc::gemm3_split_planes(A, lda, Kd, M, ws, ldp, ps, (hipStream_t)stream)) return rc;
     if (int rc = llmc::gemm3_split_planes(B, ldb, Kd, N, (char*)ws + 3 * ps * 2, ldp, ps, (hipStream_t)stream)) return rc;
     return llmc::gemm3_launch(a, true, (hipStream_t)stream);

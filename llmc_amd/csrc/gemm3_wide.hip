@@ -29,15 +29,14 @@
 namespace llmc {
 namespace {
 
-constexpr int G_B = 128;                      // tile edge
-constexpr int G_K = 16;                       // stage depth = one MFMA
+// tile edge G_B = 128 and stage depth G_K = 16 (one MFMA): sgemm.h
 constexpr int G_ROW = G_B * 2;                // bytes per k-row of a plane
 constexpr int G_PLANE = G_K * G_ROW;          // 4 KiB
 constexpr int G_OPND = 3 * G_PLANE;           // 12 KiB
 constexpr int G_SLOT = 2 * G_OPND;            // 24 KiB
 constexpr int G_SLOTS = 3;
-constexpr int G_LDS = G_SLOTS * G_SLOT;       // 72 KiB
-constexpr int G_PER_XCD = 64;                 // tiles an XCD runs at a time (32 CUs x 2)
+static_assert(G_LDS == G_SLOTS * G_SLOT, "72 KiB");
+constexpr int G_PER_XCD = 64;                 // tiles an XCD runs at a time (32 CUs x 2): the 2^6 of gemm3_route's tile blocks
 
 struct G3wArgs {
     const uint16_t* PA;
@@ -234,21 +233,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm3w(const G3wArgs a) {
 
 }  // namespace
 
-bool gemm3w_eligible(const SgemmArgs& a) {
-    if (opt(OPT_GEMM3_NO_WIDE) || opt(OPT_GEMM3_NOSPEC)) return false;
-    if (!a.planesA || !a.planesB || a.batch != 1 || a.epilogue != SG_SUB || a.phase_len != 0) return false;
-    if (a.a_upper || a.a_lower || a.b_upper) return false;
-    if (a.M <= 0 || a.N <= 0 || a.M % G_B || a.N % G_B || a.Kd % (2 * G_K) || a.Kd < 8 * G_K) return false;
-    if (a.ldp % 8 || a.plane_stride % 8 || (((uintptr_t)a.planesA | (uintptr_t)a.planesB) & 15) || ((uintptr_t)a.C & 3)) return false;
-    if ((2 * a.plane_stride + ((int64_t)a.Kd + G_K) * a.ldp) * 2 >= (int64_t)0x7fffff00) return false;
-    if ((int64_t)G_B * a.ldc * 4 >= (int64_t)0x7fffff00) return false;
-    const int64_t tm = a.M / G_B, tn = a.N / G_B;
-    const int64_t tiles = a.c_upper_only ? tm * tn - tm * (tm - 1) / 2 : tm * tn;
-    const int mt = opt(OPT_GEMM3S_MIN_TILES);
-    return tiles >= (mt > 0 ? mt : 1024);      // measured (profiles/r06_gemm3w_ab.txt): n = 3584 (406 tiles) 68 vs 54 us for k_gemm3s, n = 8192 (2080) 236-260 vs 268
-}
-
-int gemm3w_launch(const SgemmArgs& a, hipStream_t st) {
+int gemm3w_launch(const SgemmArgs& a, const GemmRoute& r, hipStream_t st) {
     G3wArgs w{};
     w.PA = (const uint16_t*)a.planesA; w.PB = (const uint16_t*)a.planesB; w.C = a.C; w.ldc = a.ldc;
     w.row2 = (uint32_t)(a.ldp * 2); w.ps2 = (uint32_t)(a.plane_stride * 2); w.rowC = (uint32_t)(a.ldc * 4);
@@ -257,32 +242,9 @@ int gemm3w_launch(const SgemmArgs& a, hipStream_t st) {
     w.nst = a.Kd / G_K;
     w.tm = a.M / G_B; w.tn = a.N / G_B;
     w.upper = a.c_upper_only ? 1 : 0;
-    // the tile-block shape whose busiest XCD has the fewest WORKING tiles (block g -> XCD g % 8), the squarest among equals
-    int best_cost = 1 << 30, best_sm = 3;
-    for (int sm = 1; sm < 6; ++sm) {
-        const int SM = 1 << sm, SN = 1 << (6 - sm);
-        const int sbm = (w.tm + SM - 1) / SM, sbn = (w.tn + SN - 1) / SN;
-        int load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int g = 0; g < sbm * sbn; ++g) {
-            const int i0 = (g % sbm) * SM, j0 = (g / sbm) * SN;
-            int n = 0;
-            for (int i = i0; i < i0 + SM && i < w.tm; ++i) {
-                const int jlo = w.upper && i > j0 ? i : j0, jhi = j0 + SN < w.tn ? j0 + SN : w.tn;
-                if (jhi > jlo) n += jhi - jlo;
-            }
-            load[g & 7] += n;
-        }
-        int mx = 0;
-        for (int x = 0; x < 8; ++x) mx = load[x] > mx ? load[x] : mx;
-        const int cost = mx * 64 + (SM + SN);
-        if (cost < best_cost) { best_cost = cost; best_sm = sm; }
-    }
-    w.sm_log = best_sm; w.sn_log = 6 - best_sm;
-    w.sbm = (w.tm + (1 << w.sm_log) - 1) >> w.sm_log;
-    w.nsb = w.sbm * ((w.tn + (1 << w.sn_log) - 1) >> w.sn_log);
-    const int rounds = (w.nsb + 7) / 8;
+    w.sm_log = r.sm_log; w.sn_log = r.sn_log; w.sbm = r.sbm; w.nsb = r.nsb;
     if (int rc = ensure_dynamic_lds((const void*)k_gemm3w, G_LDS)) return rc;
-    hipLaunchKernelGGL(k_gemm3w, dim3(rounds * 8 * G_PER_XCD), dim3(256), G_LDS, st, w);
+    hipLaunchKernelGGL(k_gemm3w, dim3(r.gx), dim3(r.threads), G_LDS, st, w);
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;
 }

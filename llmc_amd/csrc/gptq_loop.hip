@@ -184,7 +184,7 @@ static int rider_quota(const ColCall& o, bool merged, int nt, int grid) {
     if (!merged || opt(OPT_NO_RIDERS) || !o.ekm || nt != GBT || o.R % 128 || o.K % 128 || o.NQ <= GW || o.K <= 2 * (int64_t)GW) return 0;
     const int free_cus = device_cu_count() - grid;
     // the first group's far-far product: every later one has the same strides and alignment
-    if (sgemm_wide_form(o.far(0, 2 * GW, o.K, 0, GW), true, false) != 2 || free_cus <= 0 || 2 * grid < device_cu_count()) return 0;
+    if (sgemm_route(o.far(0, 2 * GW, o.K, 0, GW), true, false).wide_form != 2 || free_cus <= 0 || 2 * grid < device_cu_count()) return 0;
     return (int)(free_cus / (o.R / 128));
 }
 

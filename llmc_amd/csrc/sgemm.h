@@ -37,29 +37,38 @@ struct SgemmArgs {
     const void* planesA;
     const void* planesB;
     int64_t ldp, plane_stride;
-    int planes_dma;   // set by gemm3_launch: the planes form's producers copy by LDS-DMA (0: through registers, option gemm3s_no_dma)
+    int planes_dma;   // set by gemm3_launch from the route
 };
 
-// launches on `st`; returns LLMC_* status
+// Which kernel runs a product is data: a pure function of the arguments and the calling thread's options (gemm_route.hip; no device
+// is read, nothing is launched; table: DESIGN.md "The GEMM routes"). The launchers launch what it says; callers that must know ask it too.
+enum GemmKernel { GK_SGEMM, GK_SHORTK, GK_SHORTK_PHASED, GK_WIDE2, GK_WIDE4, GK_GEMM3, GK_GEMM3S, GK_GEMM3S_PRE, GK_GEMM3W };
+// tile geometry the routers share with the kernels. k_sgemm: tile edge, K-step; k_sgemm_shortk[_phased]: tile edge, max K / phase
+constexpr int GB = 128, GK = 16, SB = 64, SKD = 128;
+constexpr int G3B = 128, G3K = 32, S_BM = 256, S_BN = 128, S_LDS = 144 * 1024;      // k_gemm3: tile edge, K-step; k_gemm3s: tile, LDS bytes
+constexpr int G_B = 128, G_K = 16, G_LDS = 72 * 1024;     // k_gemm3w: tile edge, stage depth, LDS bytes
+struct GemmRoute {
+    int status; const char* msg;    // LLMC_OK, or the refusal and its message
+    int kernel;                     // GemmKernel; meaningless unless status == LLMC_OK and !empty
+    bool empty;                     // M, N or batch <= 0: nothing is launched, LLMC_OK
+    unsigned gx, gy, gz; int threads, lds;      // launch geometry, dynamic LDS bytes
+    bool ta, tb, phased, edge;      // k_sgemm's instantiation; ta / tb as given for the others
+    int phase_len;                  // effective: a plain C -= AB on k_sgemm is ONE phase over the whole K loop (1 << 30)
+    int planes_dma;                 // k_gemm3s: the planes form's producers copy by LDS-DMA (0: through registers, option gemm3s_no_dma)
+    int sm_log, sn_log, sbm, nsb;   // wide kernels: an XCD's tile block = 2^sm_log x 2^sn_log tiles; tile blocks along M; tile blocks
+    int wide_form;                  // sgemm: the k_sgemm_wide<MB> the arguments qualify for (0: none), even where a short-K kernel
+                                    // takes the product first: K4's riders run that kernel's tile function themselves
+    bool planes() const { return status == LLMC_OK && !empty && (kernel == GK_GEMM3S_PRE || kernel == GK_GEMM3W); }      // reads a.planesA / planesB
+};
+GemmRoute sgemm_route(const SgemmArgs& a, bool TA, bool TB);
+// C (op) op(A) B on the 16-bit MFMA pipe with three bf16 terms per fp32 operand (gemm3.hip, gemm3_wide.hip): fp32-level accuracy, NOT the
+// bitwise fma chain above — K3 only. op(B) = N; all hints, epilogues, batch; large k-major products read a.planesA / planesB where given
+GemmRoute gemm3_route(const SgemmArgs& a, bool TA);
+// launch on `st` what the router says, return LLMC_* status; below them the launch step of the routes whose kernels live in sgemm_wide.hip / gemm3_wide.hip
 int sgemm_launch(const SgemmArgs& a, bool TA, bool TB, hipStream_t st);
-
-// K4's phased far update (TA, op(B) = N, SG_SUB, phase_len = 128, whole 256 x 128 tiles) on the one-wave-per-SIMD kernel of
-// sgemm_wide.hip: same chain, same bits as sgemm_launch's other kernels
-bool sgemm_wide_eligible(const SgemmArgs& a, bool TA, bool TB);
-int sgemm_wide_launch(const SgemmArgs& a, hipStream_t st);
-// the form sgemm_wide_launch would run: 0 = not eligible, 2 = 128 x 128 tiles (two workgroups per CU), 4 = 256 x 128
-int sgemm_wide_form(const SgemmArgs& a, bool TA, bool TB);
-
-// C -= A^T B (A [Kd x M], B [Kd x N], both k-major) on the 16-bit MFMA pipe with three bf16 terms per fp32 operand
-// (gemm3.hip): fp32-level accuracy, NOT the bitwise fma chain above — K3 only.
-int gemm3_tn_launch(const SgemmArgs& a, hipStream_t st);
-// general form: TA as in sgemm_launch, op(B) = N; hints a_upper / a_lower / b_upper / c_upper_only, all epilogues, batch
 int gemm3_launch(const SgemmArgs& a, bool TA, hipStream_t st);
-// the planes form on 128 x 128 tiles with two workgroups per CU (gemm3_wide.hip): SG_SUB, whole tiles, planes given
-bool gemm3w_eligible(const SgemmArgs& a);
-int gemm3w_launch(const SgemmArgs& a, hipStream_t st);
-// true when gemm3_launch(a, true, ..) would run the planes form for these arguments (a.planesA set): split only then
-bool gemm3_uses_planes(const SgemmArgs& a);
+int sgemm_wide_launch(const SgemmArgs& a, const GemmRoute& r, hipStream_t st);
+int gemm3w_launch(const SgemmArgs& a, const GemmRoute& r, hipStream_t st);
 // hi | mid | lo bf16 planes of a k-major fp32 panel [rows x n] (n % 8 == 0): planes + t * plane_stride + r * ldp + c
 int gemm3_split_planes(const float* P, int64_t ld, int rows, int n, void* planes, int64_t ldp, int64_t plane_stride, hipStream_t st);
 

@@ -3,13 +3,13 @@
 // staged k-major in LDS ([k][row]) so that an MFMA operand read (32 consecutive rows at one k) is a
 // conflict-free ds_read_b32; a memory layout that is row-major along k is transposed by the staging
 // writes. Register-prefetched double buffering, one barrier per K-step.
+#include <assert.h>
 #include <stdlib.h>
 #include "sgemm.h"
 
 namespace llmc {
 
-static constexpr int GB = 128;   // tile edge
-static constexpr int GK = 16;    // K-step
+// tile edge GB = 128 and K-step GK = 16: sgemm.h
 static constexpr int GLD = 132;  // LDS row stride (floats): 16-B aligned rows, 2-way at most on transposing writes
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -271,8 +271,7 @@ __global__ __launch_bounds__(256, 2) void k_sgemm(SgemmArgs a) {
 // workgroup owns a 64x64 tile (4x the workgroups of the 128x128 kernel), fetches its WHOLE A and B panels with
 // every load in flight at once (64 KB of LDS, one barrier), and runs one 64-step MFMA chain per wave. Same
 // arithmetic as k_sgemm: one accumulator per element, ascending k from +0, then the epilogue's single rounding.
-static constexpr int SB = 64;     // tile edge
-static constexpr int SKD = 128;   // max K
+// tile edge SB = 64 and max K SKD = 128: sgemm.h
 static constexpr int SLB = 68;    // LDS row stride of k-major operands written as float4
 static constexpr int SLT = 65;    // LDS row stride of the transposed (row-major in memory) A operand
 
@@ -494,65 +493,30 @@ __global__ __launch_bounds__(256) void k_sgemm_shortk_phased(SgemmArgs a) {
 }
 
 int sgemm_launch(const SgemmArgs& a, bool TA, bool TB, hipStream_t st) {
-    if (a.M <= 0 || a.N <= 0 || a.batch <= 0) return LLMC_OK;
-    LLMC_REQUIRE((a.lda % 4 == 0) && (a.ldb % 4 == 0) && (((uintptr_t)a.A & 15) == 0) &&
-                     (((uintptr_t)a.B & 15) == 0) && (a.sA % 4 == 0) && (a.sB % 4 == 0),
-                 "sgemm: operands must be 16-B aligned with ld % 4 == 0");
-    if (!TB && a.batch == 1 && a.Kd <= SKD && !a.a_upper && !a.b_upper && (a.phase_len == 0 || a.phase_len >= a.Kd) &&
-        !opt(OPT_NO_SHORTK)) {
-        const bool in_place = (const void*)a.C == (const void*)a.B;
-        dim3 sgrid((a.N + SB - 1) / SB, in_place ? 1 : (a.M + SB - 1) / SB, 1);
-        if (TA) hipLaunchKernelGGL((k_sgemm_shortk<true>), sgrid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_sgemm_shortk<false>), sgrid, dim3(256), 0, st, a);
-        LLMC_LAUNCH_CHECK();
-        return LLMC_OK;
-    }
-    // few-tile phased products (phase = 128) on 64x64 tiles: the latency-critical slice of K4's far update
-    if (!TB && a.batch == 1 && a.epilogue == SG_SUB && a.phase_len == SKD && a.Kd % SKD == 0 && a.Kd > SKD &&
-        !a.a_upper && !a.a_lower && !a.b_upper && (TA || a.lda % 4 == 0) &&
-        (int64_t)((a.M + SB - 1) / SB) * ((a.N + SB - 1) / SB) <= 1024 && !opt(OPT_NO_SHORTK)) {
-        dim3 sgrid((a.N + SB - 1) / SB, (a.M + SB - 1) / SB, 1);
-        if (TA) hipLaunchKernelGGL((k_sgemm_shortk_phased<true>), sgrid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_sgemm_shortk_phased<false>), sgrid, dim3(256), 0, st, a);
-        LLMC_LAUNCH_CHECK();
-        return LLMC_OK;
-    }
-    if (sgemm_wide_eligible(a, TA, TB)) return sgemm_wide_launch(a, st);
-    LLMC_REQUIRE((const void*)a.C != (const void*)a.B || (a.M <= GB && a.batch == 1),
-                 "sgemm: in-place C = op(A) B needs a single row tile (M <= 128)");
-    dim3 grid((a.N + GB - 1) / GB, (a.M + GB - 1) / GB, a.batch);
-    if (a.phase_len == 0 && a.epilogue == SG_SUB && !a.a_upper && !TB) {
-        // plain C -= AB: one phase covering the whole K loop, i.e. the C tile is fetched while the first operand
-        // tiles are, and the epilogue is stores only (same single rounding C - acc)
-        SgemmArgs b = a;
-        b.phase_len = 1 << 30;
-        return sgemm_launch(b, TA, TB, st);
-    }
-    // interior-only instantiation when every tile and K range is whole (the shapes of the 128-aligned layers)
-    auto whole = [&](int M, int N, int Kd) { return M % GB == 0 && N % GB == 0 && Kd % GK == 0; };
-    const bool edge = !(whole(a.M, a.N, a.Kd) && whole(a.M_last, a.N_last, a.Kd_last));
-#define LLMC_SG(TA_, TB_, PH_)                                                                        \
-    do {                                                                                              \
-        if (edge) hipLaunchKernelGGL((k_sgemm<TA_, TB_, PH_, true>), grid, dim3(256), 0, st, a);      \
-        else hipLaunchKernelGGL((k_sgemm<TA_, TB_, PH_, false>), grid, dim3(256), 0, st, a);          \
-    } while (0)
-    if (a.phase_len > 0) {
-        LLMC_REQUIRE(a.phase_len % GK == 0 && a.epilogue == SG_SUB && !a.a_upper, "sgemm: bad phased configuration");
-        if (TA && !TB) LLMC_SG(true, false, true);
-        else if (!TA && !TB) LLMC_SG(false, false, true);
-        else { set_last_error_msg("sgemm: phased mode supports op(B) = N only"); return LLMC_ENOTSUP; }
-    } else if (TA && !TB) LLMC_SG(true, false, false);
-    else if (!TA && !TB) LLMC_SG(false, false, false);
-    else if (TA && TB) LLMC_SG(true, true, false);
-    else LLMC_SG(false, true, false);
-#undef LLMC_SG
+    const GemmRoute r = sgemm_route(a, TA, TB);
+    if (r.status != LLMC_OK) set_last_error_msg(r.msg);
+    if (r.status != LLMC_OK || r.empty) return r.status;
+    if (r.kernel == GK_WIDE2 || r.kernel == GK_WIDE4) return sgemm_wide_launch(a, r, st);
+    SgemmArgs b = a; b.phase_len = r.phase_len;
+    // k_sgemm_shortk[_phased]<TA>, k_sgemm<TA, TB, PHASED, EDGE>. The indices are negated so that the tables name the instantiations in the order
+    // the device code has always held them (another order permutes the functions in the object); no phased form with op(B) = T: the router refuses it
+    using Kernel = void (*)(SgemmArgs);
+    static const Kernel sk[2][2] = {{k_sgemm_shortk<true>, k_sgemm_shortk<false>}, {k_sgemm_shortk_phased<true>, k_sgemm_shortk_phased<false>}};
+    static const Kernel sg[2][2][2][2] = {      // [!phased][tb][!ta][!edge]
+        {{{k_sgemm<true, false, true, true>, k_sgemm<true, false, true, false>}, {k_sgemm<false, false, true, true>, k_sgemm<false, false, true, false>}},
+         {{nullptr, nullptr}, {nullptr, nullptr}}},
+        {{{k_sgemm<true, false, false, true>, k_sgemm<true, false, false, false>}, {k_sgemm<false, false, false, true>, k_sgemm<false, false, false, false>}},
+         {{k_sgemm<true, true, false, true>, k_sgemm<true, true, false, false>}, {k_sgemm<false, true, false, true>, k_sgemm<false, true, false, false>}}}};
+    const Kernel k = r.kernel == GK_SGEMM ? sg[!r.phased][r.tb][!r.ta][!r.edge] : sk[r.kernel == GK_SHORTK_PHASED][!r.ta];
+    assert(k && "sgemm_route refuses phased products with op(B) = T");
+    hipLaunchKernelGGL(k, dim3(r.gx, r.gy, r.gz), dim3(r.threads), 0, st, b);
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;
 }
 
 }  // namespace llmc
 
-// C ABI test hook (not part of the product surface: exercised by tests/test_sgemm_gpu.py only)
+// C ABI test hook (not part of the product surface: exercised by tests/test_gptq_gpu.py and tests/test_gemm_routes_gpu.py only)
 extern "C" int llmc_test_sgemm(const float* A, const float* B, float* C, int64_t lda, int64_t ldb, int64_t ldc,
                                int M, int N, int Kd, int TA, int TB, int epilogue, int a_upper, int a_lower,
                                int b_upper, int c_upper_only, llmc_stream_t stream) {

@@ -44,57 +44,16 @@ __global__ __launch_bounds__(256, MB == 4 ? 1 : 2) void k_sgemm_wide(const WideA
 
 }  // namespace
 
-// form: 0 = none, 4 = 256 x 128 tiles (one workgroup per CU), 2 = 128 x 128 tiles (two per CU)
-static int wide_form(const SgemmArgs& a, bool TA, bool TB) {
-    if (!TA || TB || a.batch != 1 || a.epilogue != SG_SUB || a.phase_len != 128) return 0;
-    if (a.a_upper || a.a_lower || a.b_upper || a.c_upper_only) return 0;
-    if (a.M <= 0 || a.N <= 0 || a.M % 128 || a.N % W_BN || a.Kd % 128 || a.Kd < 128) return 0;
-    if ((a.lda % 4) || (a.ldb % 4) || ((uintptr_t)a.A & 15) || ((uintptr_t)a.B & 15) || ((uintptr_t)a.C & 3)) return 0;
-    const int64_t lim = (int64_t)1 << 31;
-    if ((int64_t)a.Kd * a.lda * 4 >= lim || (int64_t)a.Kd * a.ldb * 4 >= lim || (int64_t)256 * a.ldc * 4 >= lim) return 0;
-    if ((const void*)a.C == (const void*)a.A || (const void*)a.C == (const void*)a.B) return 0;
-    const int v = opt(OPT_SGEMM_NO_WIDE);      // 0: the default form, 1: never, 2 / 4: that form where the shape allows it
-    if (v == 1) return 0;
-    if (v == 4) return a.M % 256 ? 2 : 4;
-    return 2;      // measured (profiles/r06_sgemm_wide_ab.txt): two 128 x 128 workgroups per CU beat one 256 x 128 on every shape of the column loop
-}
-bool sgemm_wide_eligible(const SgemmArgs& a, bool TA, bool TB) { return wide_form(a, TA, TB) != 0; }
-
-int sgemm_wide_form(const SgemmArgs& a, bool TA, bool TB) { return wide_form(a, TA, TB); }
-
-template <int MB> static int wide_launch(const SgemmArgs& a, hipStream_t st) {
-    using W = Wide<MB>;
+int sgemm_wide_launch(const SgemmArgs& a, const GemmRoute& r, hipStream_t st) {
+    static_assert(Wide<4>::PER_XCD == 1 << 5 && Wide<2>::PER_XCD == 1 << 6, "sgemm_route's tile blocks");
     WideArgs w{};
-    wide_operands<MB>(a, w);
-    // The shape of an XCD's tile block: the one whose busiest XCD has the fewest tiles (block g goes to XCD g % 8; a ragged last
-    // block column or a block count that is not a multiple of 8 leaves XCDs idle in the last round — the column loop's far updates
-    // shrink by four tile columns per launch, most of them are a few rounds long), the squarest among equals (fewest panels in L2).
-    int best_cost = 1 << 30, best_sm = 0;
-    constexpr int LOGT = MB == 4 ? 5 : 6;
-    for (int sm = 1; sm < LOGT; ++sm) {
-        const int SM = 1 << sm, SN = 1 << (LOGT - sm);
-        const int sbm = (w.tm + SM - 1) / SM, sbn = (w.tn + SN - 1) / SN;
-        int load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int g = 0; g < sbm * sbn; ++g) {
-            const int bi = g % sbm, bj = g / sbm;
-            load[g & 7] += (w.tm - bi * SM < SM ? w.tm - bi * SM : SM) * (w.tn - bj * SN < SN ? w.tn - bj * SN : SN);
-        }
-        int mx = 0;
-        for (int x = 0; x < 8; ++x) mx = load[x] > mx ? load[x] : mx;
-        const int cost = mx * 64 + (SM + SN);
-        if (cost < best_cost) { best_cost = cost; best_sm = sm; }
-    }
-    w.sm_log = best_sm; w.sn_log = LOGT - best_sm;
-    w.sbm = (w.tm + (1 << w.sm_log) - 1) >> w.sm_log;
-    w.nsb = w.sbm * ((w.tn + (1 << w.sn_log) - 1) >> w.sn_log);
-    const int rounds = (w.nsb + 7) / 8;
-    if (int rc = ensure_dynamic_lds((const void*)k_sgemm_wide<MB>, W::LDS)) return rc;
-    hipLaunchKernelGGL(k_sgemm_wide<MB>, dim3(rounds * 8 * W::PER_XCD), dim3(256), W::LDS, st, w);
+    if (r.kernel == GK_WIDE4) wide_operands<4>(a, w); else wide_operands<2>(a, w);
+    w.sm_log = r.sm_log; w.sn_log = r.sn_log; w.sbm = r.sbm; w.nsb = r.nsb;
+    void (*const k)(WideArgs) = r.kernel == GK_WIDE4 ? k_sgemm_wide<4> : k_sgemm_wide<2>;
+    if (int rc = ensure_dynamic_lds((const void*)k, r.lds)) return rc;
+    hipLaunchKernelGGL(k, dim3(r.gx), dim3(r.threads), r.lds, st, w);
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;
-}
-int sgemm_wide_launch(const SgemmArgs& a, hipStream_t st) {
-    return wide_form(a, true, false) == 4 ? wide_launch<4>(a, st) : wide_launch<2>(a, st);
 }
 
 }  // namespace llmc

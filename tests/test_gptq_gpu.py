@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from conftest import load_golden
+from gemm_routes import route, route_of
 from llmc_amd import _ffi
 from oracle import gptq_ref as G
 from oracle import quant_ref as Q
@@ -53,6 +54,8 @@ def test_sgemm_bitwise_chain(shape):
     Mp = (M + 3) // 4 * 4
     at = torch.zeros(Kd, Mp).cuda()
     at[:, :M] = a.t().cuda()
+    assert [route_of('sgemm', ad, bd, C, M, N, Kd).name, route_of('sgemm', at, bd, C, M, N, Kd, TA=True, epilogue=1).name] == \
+        ['GK_SHORTK' if Kd <= 128 else 'GK_SGEMM'] * 2
     C2 = torch.zeros(M, ldn).cuda()
     sgemm(at, bd, C2, M, N, Kd, True, False, 1)
     np.testing.assert_array_equal(bits(C2.cpu().numpy()[:, :N]), bits(ref))
@@ -84,9 +87,12 @@ def test_sgemm_wide_phased_far_update_bitwise(shape):
     else:
         exp = None
     res = {}
+    runs = dict(wide4='GK_WIDE4' if M % 256 == 0 else 'GK_WIDE2', wide2='GK_WIDE2', k_sgemm='GK_SGEMM',
+                default='GK_SHORTK' if Kd <= 128 else 'GK_SHORTK_PHASED' if (M // 64) * (N // 64) <= 1024 else 'GK_WIDE2')
     for name, opts in (('wide4', dict(no_shortk=1, sgemm_no_wide=4)), ('wide2', dict(no_shortk=1, sgemm_no_wide=2)),
                        ('k_sgemm', dict(no_shortk=1, sgemm_no_wide=1)), ('default', {})):
         with _ffi.option(**opts):
+            assert route('sgemm', M, N, Kd, TA=True, phase_len=128).name == runs[name]
             C = c0.cuda()
             sgemm_phased(at.cuda(), b.cuda(), C, M, N, Kd, True, 128)
             res[name] = C.cpu().numpy()
@@ -111,6 +117,7 @@ def test_sgemm_wide_strided_operands_and_zero_products():
                        ('k_sgemm', dict(no_shortk=1, sgemm_no_wide=1))):
         with _ffi.option(**opts):
             C = Cbig.cuda()
+            assert route_of('sgemm', Abig[:, 64:], Bbig[:, 128:], C[:, 128:], M, N, Kd, TA=True, phase_len=128).name == dict(wide4='GK_WIDE4', wide2='GK_WIDE2', k_sgemm='GK_SGEMM')[name]
             sgemm_phased(Abig[:, 64:], Bbig[:, 128:], C[:, 128:], M, N, Kd, True, 128)
             out[name] = C.cpu().numpy()
     for name in ('wide4', 'wide2'):
@@ -178,8 +185,10 @@ def test_gemm3_specialised_kernel_is_bit_identical(shape, monkeypatch):
         for hints in ((0, 0, 0), (0, 0, 1)) if M == N else ((0, 0, 0),):
             _ffi.set_option('gemm3_nospec', 0)
             c_new = gemm3(A, B, C0.clone(), M, N, Kd, True, epi, hints)
+            ran = route_of('gemm3', A, B, C0, M, N, Kd, TA=True, epilogue=epi, hints=(0, 0, 0, hints[2])).name
             _ffi.set_option('gemm3_nospec', 1)
             c_old = gemm3(A, B, C0.clone(), M, N, Kd, True, epi, hints)
+            assert (ran, route_of('gemm3', A, B, C0, M, N, Kd, TA=True, epilogue=epi, hints=(0, 0, 0, hints[2])).name) == ('GK_GEMM3S', 'GK_GEMM3')
             if hints[2]:
                 iu = torch.triu(torch.ones(M, N, dtype=torch.bool)).cuda()
                 assert torch.equal(c_new[iu], c_old[iu]), (epi, hints)
@@ -215,6 +224,9 @@ def test_gemm3_planes_form_is_bit_identical(shape, monkeypatch):
             c_new = C0.clone()
             _ffi.check(L.llmc_test_gemm3_planes(A.data_ptr(), B.data_ptr(), c_new.data_ptr(), A.stride(0), B.stride(0), c_new.stride(0),
                                                 M, N, Kd, epi, upper, ws.data_ptr(), _ffi.stream()), 'gemm3 planes')
+            # the planes form: C -= on whole 128 x 128 tiles goes to k_gemm3w, everything else to k_gemm3s
+            assert route_of('gemm3', A, B, c_new, M, N, Kd, TA=True, epilogue=epi, hints=(0, 0, 0, upper), planes=True).name == \
+                ('GK_GEMM3W' if epi == 0 and M % 128 == 0 and N % 128 == 0 else 'GK_GEMM3S_PRE')
             _ffi.set_option('gemm3_nospec', 1)
             c_old = gemm3(A, B, C0.clone(), M, N, Kd, True, epi, (0, 0, upper))
             if upper:
@@ -245,6 +257,7 @@ def test_gemm3w_two_workgroups_per_cu_is_bit_identical(shape):
         for name, opts in (('w', {}), ('s', dict(gemm3_no_wide=1))):
             with _ffi.option(**opts):
                 c = Cbig.clone()
+                assert route_of('gemm3', A, B, c[:, 64:], M, N, Kd, TA=True, hints=(0, 0, 0, upper), planes=True).name == dict(w='GK_GEMM3W', s='GK_GEMM3S_PRE')[name]
                 _ffi.check(L.llmc_test_gemm3_planes(A.data_ptr(), B.data_ptr(), c[:, 64:].data_ptr(), A.stride(0), B.stride(0), c.stride(0),
                                                     M, N, Kd, 0, upper, ws.data_ptr(), _ffi.stream()), 'gemm3 planes')
                 out[name] = c

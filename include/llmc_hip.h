@@ -224,6 +224,47 @@ size_t llmc_fp8_quant_ws_bytes(int64_t G, int64_t g);
 int llmc_fp8_quant(const void* W, int dt, int64_t G, int64_t g, int fake, void* out, void* scales, int sdt,
                    int static_scales, void* ws, llmc_stream_t stream);
 
+/* FloatQuantizer on the narrow float grids (quant.py:963-1003 with qmax = tensor(6) / tensor(28), 1061-1081), one pass:
+ * per row of the [G, g] view  absmax -> scale -> t = rnd_dt(w / scale) + 0 -> rounding onto the grid -> q * scale or a code.
+ *   e2m1 (FP4): s ee m, bias 1, OCP values 0, 0.5, 1, 1.5, 2, 3, 4, 6;   e3m2 (FP6): s eee mm, bias 3, OCP max 28, smallest
+ *   normal 0.25, subnormal step 0.0625. Neither has an infinity or a NaN.
+ * `mode` is a flag word:
+ *   bit 0      write dequantised q * scale in dt to `out` (fp32 product, one rounding) instead of one code per byte (the low
+ *              4 / 6 bits, sign on top, the rest zero)
+ *   bits 4-5   format: 2 = e2m1, 3 = e3m2 (0 / 1 are llmc_fp8_quant's; here they return LLMC_ENOTSUP)
+ *   bit 8      rounding semantics: 0 = qtorch.quant.float_quantize(x, 2, 1) / (x, 3, 2) as the reference calls it (restated
+ *              in csrc/fp8_math.h, see llmc_fp8_quant): ties away from zero, the top exponent code kept for infinity, so the
+ *              largest value is 3 / 14 although the scale maps the row to +-6 / +-28 — 11 of e2m1's 15 levels; a zero
+ *              result is +0. 1 = 'ocp': round to nearest even onto the OCP grid, subnormals included, saturating at +-6 /
+ *              +-28 (infinities too); a NaN gives the maximum with the input's sign; the sign survives on a zero result.
+ *   bit 9      scales are e8m0 bytes (OCP MX; with bit 8 only, else LLMC_ENOTSUP): code = clamp(floor(log2(absmax)) - emax
+ *              + 127, 0, 254) with emax = 2 (e2m1) / 4 (e3m2), 127 for an all-zero row; scale = 2^(code - 127); the division
+ *              is exact, so the quotient is not rounded to dt. `scales` is then uint8 [G] and sdt is ignored. Dynamic e8m0
+ *              scales need rows the resident kernels take (below), else LLMC_ENOTSUP.
+ *   bit 11     dynamic scales: write back get_qparams' own value (an underflowed scale stays 0), as in llmc_fp8_quant.
+ * Other bits: LLMC_ENOTSUP. Dtype scales: absmax.clamp(1e-5) / qmax rounded to sdt; a zero scale quantizes with 1. The
+ * reference's qmax is an INTEGER 0-dim tensor here, so the 0-dim per-tensor absmax / qmax keeps the tensor dtype (the FP8
+ * formats' float qmax promotes it to fp32): callers pass sdt = dt for every granularity.
+ * cols (may be null): [K] multipliers in dt for a 2-D weight [G * g / K, K] whose rows are split into groups (K % g == 0):
+ * the element is first rnd_dt(w * cols[k]) — bit for bit llmc_mul_cols followed by the call without cols; W is not written.
+ * Rows of at most 16384 elements (a multiple of the 16-byte vector, 16-B aligned W / out / cols) are read from HBM once:
+ * the row waits in registers (g = vector x a power of two <= 64 lanes) or LDS between the reduction and the rounding.
+ * Everything else takes llmc_minmax_qparams + a second read (ws of llmc_fpx_quant_ws_bytes, dynamic scales only; cols are
+ * then LLMC_ENOTSUP unless the scales are static). */
+size_t llmc_fpx_quant_ws_bytes(int64_t G, int64_t g);
+int llmc_fpx_quant(const void* W, int dt, int64_t G, int64_t g, const void* cols, int64_t K, int mode, void* out,
+                   void* scales, int sdt, int static_scales, void* ws, llmc_stream_t stream);
+
+/* e2m1 codes [R, K] (one per byte, K even) -> [R, K / 2] bytes: element 2i in the low nibble, 2i + 1 in the high one (the
+ * float4_e2m1fn_x2 / MX convention). */
+int llmc_fp4_pack(const void* codes, int64_t R, int64_t K, void* packed, llmc_stream_t stream);
+
+/* The stored form back to numbers: out[G, g] (odt) = decode(code) * scale[row] — an fp32 product rounded once, the
+ * arithmetic of llmc_fpx_quant's fake output. fmt 2 = e2m1 (packed != 0: two codes per byte as llmc_fp4_pack writes them),
+ * 3 = e3m2 (one code per byte only; dense FP6 packing is not provided). sdt: the scales' float dtype, or -1 for e8m0 bytes. */
+int llmc_fpx_dequant(const void* codes, int fmt, int packed, const void* scales, int sdt, int64_t G, int64_t g, void* out,
+                     int odt, llmc_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * GPTQ (llmc/compression/quantization/gptq.py)
  * ---------------------------------------------------------------------------------------------- */

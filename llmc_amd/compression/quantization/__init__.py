@@ -1,5 +1,5 @@
 from .quant import (BaseQuantizer, FloatQuantizer, IntegerQuantizer,  # noqa: F401
-                    pack_awq_gemm, pack_lsb)
+                    dequant_fpx, pack_awq_gemm, pack_fp4, pack_lsb)
 from .module_utils import (AutoawqRealQuantLinear, EffcientFakeQuantLinear,  # noqa: F401
                            FakeQuantLinear, LlmcFp8Linear, OriginFloatLinear, VllmRealQuantLinear)
 from .base_blockwise_quantization import BaseBlockwiseQuantization  # noqa: F401

@@ -21,7 +21,7 @@ from .awq_pipeline import search_scale_stacked
 from .base_blockwise_quantization import BaseBlockwiseQuantization, _world
 from .module_utils import (_LLMC_LINEAR_TYPES_, _LLMC_LN_TYPES_, _TRANSFORMERS_LINEAR_TYPES_,
                            _TRANSFORMERS_LN_TYPES_, FakeQuantLinear)
-from .quant import IntegerQuantizer
+from .quant import FloatQuantizer, IntegerQuantizer
 
 
 class _hip_linear_forward:
@@ -87,7 +87,15 @@ class Awq(BaseBlockwiseQuantization):
             return self._bf16_to_fp8(tmp)
         if self._fusable_wquantizer():
             return awq_ops.scale_fakequant(w0, cols, self.wquantizer)
-        return self.wquantizer.fake_quant_weight_dynamic(awq_ops.mul_cols_(w0.clone(), cols))
+        wq = self.wquantizer
+        if isinstance(wq, FloatQuantizer) and wq.narrow and wq.granularity in ('per_group', 'per_channel') and w0.dim() == 2:
+            # e2m1 / e3m2: the column multiplier rides on the quantizer's single pass (llmc_fpx_quant) — the bits of
+            # mul_cols + fake_quant_weight_dynamic without the scaled copy
+            t = wq.reshape_tensor(w0.contiguous())
+            if wq.fused_cols_ok(t) and cols.data_ptr() % 16 == 0:
+                out, _ = wq._run_narrow(t, True, cols=cols)
+                return out.reshape(w0.shape)
+        return wq.fake_quant_weight_dynamic(awq_ops.mul_cols_(w0.clone(), cols))
 
     @torch.no_grad()
     def scaling_weight(self, w, scales, is_gqa):

@@ -94,6 +94,9 @@ class GPTQ(BaseBlockwiseQuantization):
         grid for is refused here, at construction, instead of being quantized by some other rule."""
         if not isinstance(wq, FloatQuantizer):
             return None
+        if wq.narrow:
+            raise NotImplementedError(f'GPTQ with a float quantizer bit={wq.bit}: the column loop has the e4m3 and e5m2 grids '
+                                      '(llmc_gptq_quantize_fp8_cols); the FP4 / FP6 grids of e2m1 / e3m2 are not built into it')
         if wq.kwargs.get('fp8_semantics', 'qtorch') != 'qtorch':
             raise NotImplementedError("GPTQ with a float quantizer and fp8_semantics='cast': a compensated weight that rounds "
                                       'above the largest e4m3fn value is NaN under the dtype cast, and the NaN would enter the '

@@ -35,6 +35,11 @@ class OsPlus(BaseBlockwiseQuantization):
     def __init__(self, model, quant_config, input, padding_mask, config):
         torch.set_grad_enabled(False)
         super().__init__(model, quant_config, input, padding_mask, config)
+        for q, what in ((self.aquantizer, 'act'), (self.wquantizer, 'weight')):
+            if getattr(q, 'narrow', False):
+                raise NotImplementedError(f'OsPlus with a float {what} quantizer bit={q.bit}: the fused activation step of the '
+                                          'threshold search (llmc_osplus_act_step) knows the e4m3 and e5m2 formats only; the '
+                                          'e2m1 / e3m2 grids are not built into it')
         if self.w_only:
             raise NotImplementedError('OsPlus searches with the activation quantizer (osplus.py:157); the config has no '
                                       '`act` section')

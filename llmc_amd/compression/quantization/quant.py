@@ -5,6 +5,10 @@ argument meaning, return shapes/dtypes (BaseQuantizer :46-658, IntegerQuantizer 
 FloatQuantizer :963-1229).  In scope: calib_algo 'minmax' (the algorithm of every GPTQ/AWQ/RTN config
 named in BASELINE.json); granularity per_group / per_channel / per_token / per_tensor / per_head;
 FloatQuantizer e4m3 / e5m2 with qtorch.float_quantize restated (fp8_semantics='cast': torch's dtype cast).
+Also in scope: FloatQuantizer e2m1 / e3m2 (quant.py:985-987, qmax = tensor(6) / tensor(28)): one fused kernel (llmc_fpx_quant,
+csrc/fp4_quant.hip) for every granularity but per_block, calib_algo minmax and the static activation ranges; float_semantics='qtorch'
+(default: the reference's arithmetic, whose grid ends at 3 / 14) or 'ocp' (the OCP grid up to 6 / 28, round to nearest even),
+scale_format='dtype' or 'e8m0' (OCP MX block scales); real_quant_weight_* return packed e2m1 nibbles (pack_fp4, dequant_fpx).
 Also in scope: calib_algo 'mse' (get_mse_range, quant.py:145-203).
 Also in scope: calib_algo 'learnable' (get_learnable_range, quant.py:205-224: the range AutoClipper's clip v2 factors scale).
 Also in scope: calib_algo 'hqq' on IntegerQuantizer per_group weights with group sizes 16 / 32 / 64 / 128 (get_hqq_qparams,
@@ -627,25 +631,47 @@ class FloatQuantizer(BaseQuantizer):
     csrc/fp8_math.h and oracle/quant_ref.py: IEEE-style (e, m) formats with ties away from zero and saturation, so for
     e4m3 the largest code is 240 although qmax (finfo(float8_e4m3fn).max = 448) scales the tensor to +-448: every
     |x / scale| >= 248 lands on 240. `fp8_semantics='cast'` selects torch's own dtype cast instead (round to nearest even,
-    OCP e4m3fn up to 448): what the reference's Triton kernels and its final `.to(torch.float8_e4m3fn)` compute."""
+    OCP e4m3fn up to 448): what the reference's Triton kernels and its final `.to(torch.float8_e4m3fn)` compute.
+
+    bit 'e2m1' / 'e3m2' (FP4 / FP6; quant.py:985-987: qmin / qmax = -+6 / -+28 as integer 0-dim tensors, so `absmax / qmax`
+    keeps the tensor dtype for a 0-dim per_tensor absmax too): one fused kernel, llmc_fpx_quant. `float_semantics='qtorch'`
+    (default) is the reference bit for bit: float_quantize(x, 2, 1) keeps the top exponent code for infinity, so with qmax = 6
+    the grid is {0, +-0.5, 1, 1.5, 2, 3} — every |x / scale| >= 2.5 lands on 3 (e3m2: 14 inside +-28). `'ocp'` rounds to
+    nearest even onto the OCP grid ({..., 4, 6}: what the matrix cores consume), saturating; a NaN gives the signed maximum.
+    `scale_format='e8m0'` ('ocp' and per_group only) writes OCP MX block scales: uint8 exponents, 2^(floor(log2 absmax) - emax).
+    real_quant_weight_* (the reference asserts e4m3 / e5m2 there) return e2m1 codes packed two per byte, e3m2 one per byte."""
 
     _FMT = {'e4m3': (0, 4, 3, torch.float8_e4m3fn), 'e5m2': (1, 5, 2, torch.float8_e5m2)}
+    # the narrow grids (quant.py:985-987): no torch dtype to take the range from, the reference writes it down as integers
+    _NARROW = {'e2m1': (2, 2, 1, 6), 'e3m2': (3, 3, 2, 28)}
 
     def __init__(self, bit, symmetric, granularity, **kwargs):
         super().__init__(bit, symmetric, granularity, **kwargs)
         self.sym = True
         self.quant_type = 'float-quant'
-        if self.bit not in self._FMT:
-            raise NotImplementedError(f'FloatQuantizer bit={self.bit}: e4m3 and e5m2 are on the accelerated path '
-                                      '(e3m2 / e4m7 / e2m1 of quant.py:988-990 are not 8-bit storage formats)')
+        if self.bit not in self._FMT and self.bit not in self._NARROW:
+            raise NotImplementedError(f'FloatQuantizer bit={self.bit}: e4m3 and e5m2 are on the accelerated path, e2m1 and e3m2 on '
+                                      'the narrow-format one (e4m7 of quant.py:986 is not)')
+        self.narrow = self.bit in self._NARROW
         if self.granularity not in ('per_tensor', 'per_channel', 'per_token', 'per_group', 'per_block'):
             raise NotImplementedError(f'FloatQuantizer granularity={self.granularity}')
         if self.calib_algo == 'hqq':
             raise NotImplementedError('FloatQuantizer with calib_algo=hqq: the half-quadratic solver rounds to an integer '
                                       'grid (torch.round, quant.py:593); the reference has no FP8 form of it')
-        self._fmt, self.e_bits, self.m_bits, self._tdtype = self._FMT[self.bit]
+        if self.narrow:
+            self._fmt, self.e_bits, self.m_bits, imax = self._NARROW[self.bit]
+            self._tdtype = None
+        else:
+            self._fmt, self.e_bits, self.m_bits, self._tdtype = self._FMT[self.bit]
+        self.sign_bits = 1                                      # quant.py:970-973
+        self.num_bits = self.e_bits + self.m_bits + self.sign_bits
+        self.default_bias = 2 ** (self.e_bits - 1)
+        self.dst_nbins = 2 ** self.num_bits
         if self.granularity == 'per_block' and self.bit != 'e4m3':
-            raise NotImplementedError('FloatQuantizer per_block: e4m3 only (the DeepSeek-V3 checkpoint format)')
+            raise NotImplementedError(f'FloatQuantizer per_block with bit={self.bit}: e4m3 only (the DeepSeek-V3 checkpoint format)')
+        if self.narrow and self.calib_algo in ('mse', 'learnable'):
+            raise NotImplementedError(f'FloatQuantizer bit={self.bit} with calib_algo={self.calib_algo}: the narrow formats take '
+                                      'minmax and the static activation ranges')
         self.use_qtorch = self.kwargs.get('use_qtorch')       # quant.py:974: absent means False, like the reference
         if not self.use_qtorch:
             raise NotImplementedError('FloatQuantizer without use_qtorch: True (get_float_qparams, quant.py:1005-1041: hard-coded '
@@ -653,12 +679,31 @@ class FloatQuantizer(BaseQuantizer):
         sem = self.kwargs.get('fp8_semantics', 'qtorch')
         if sem not in ('qtorch', 'cast'):
             raise ValueError(f"fp8_semantics must be 'qtorch' or 'cast', got {sem!r}")
-        self._mode = (self._fmt << 4) | (0x100 if sem == 'qtorch' else 0)
-        fmax = float(torch.finfo(self._tdtype).max)             # quant.py:985-1003
-        self.qmax = torch.tensor(fmax)
-        self.qmin = torch.tensor(-fmax)
+        self.float_semantics = self.kwargs.get('float_semantics', 'qtorch')
+        self.scale_format = self.kwargs.get('scale_format', 'dtype')
+        if self.float_semantics not in ('qtorch', 'ocp'):
+            raise ValueError(f"float_semantics must be 'qtorch' or 'ocp', got {self.float_semantics!r}")
+        if self.scale_format not in ('dtype', 'e8m0'):
+            raise ValueError(f"scale_format must be 'dtype' or 'e8m0', got {self.scale_format!r}")
+        if self.scale_format == 'e8m0' and not (self.narrow and self.float_semantics == 'ocp' and self.granularity == 'per_group'):
+            raise ValueError("scale_format='e8m0' (OCP MX block scales) requires bit e2m1 / e3m2, float_semantics='ocp' and "
+                             "granularity per_group")
+        if not self.narrow and (self.float_semantics != 'qtorch'):
+            raise ValueError(f"float_semantics={self.float_semantics!r} belongs to e2m1 / e3m2; bit={self.bit} takes fp8_semantics")
+        if self.narrow:
+            # llmc_fpx_quant's flag word (include/llmc_hip.h)
+            self._mode = (self._fmt << 4) | (0x100 if self.float_semantics == 'ocp' else 0) | (0x200 if self.scale_format == 'e8m0' else 0)
+            self.qmax = torch.tensor(imax)                      # integer 0-dim tensors, as the reference makes them
+            self.qmin = torch.tensor(-imax)
+        else:
+            self._mode = (self._fmt << 4) | (0x100 if sem == 'qtorch' else 0)
+            fmax = float(torch.finfo(self._tdtype).max)             # quant.py:985-1003
+            self.qmax = torch.tensor(fmax)
+            self.qmin = torch.tensor(-fmax)
 
     def _run(self, tensor, fake, scales=None, raw_scales=False):
+        if self.narrow:
+            return self._run_narrow(tensor, fake, scales=scales, raw_scales=raw_scales)
         _ffi.require_gpu(tensor, scales)
         L = _ffi.lib()
         tensor = tensor.contiguous()
@@ -678,6 +723,59 @@ class FloatQuantizer(BaseQuantizer):
                                     _ffi.ptr(out), _ffi.ptr(s),
                                     _ffi.dt(sdtype), int(static), _ffi.ptr(ws), _ffi.stream()), 'llmc_fp8_quant')
         return out, s.reshape(self._qparam_shape(tensor))
+
+    # ---- e2m1 / e3m2: one fused kernel (llmc_fpx_quant, csrc/fp4_quant.hip) --------------------------------------------
+    def fused_cols_ok(self, tensor):
+        """Whether llmc_fpx_quant takes a column multiplier for this (reshaped, contiguous) tensor with dynamic scales: rows
+        the single-read kernels hold (16-byte vectors, at most 16384 elements, aligned)."""
+        _, g = self._geometry(tensor)
+        v = 16 // tensor.element_size()
+        return g % v == 0 and g <= 16384 and tensor.data_ptr() % 16 == 0
+
+    def _run_narrow(self, tensor, fake, scales=None, raw_scales=False, cols=None):
+        """(out, scales) of one llmc_fpx_quant call on the reshaped tensor. out: the fake-quantized tensor, or uint8 codes.
+        scales: tensor dtype (the reference's integer qmax does not promote a 0-dim absmax to fp32), or uint8 e8m0 bytes.
+        cols: [K] multipliers applied to the columns of the 2-D weight on the way in (the weight itself is not written)."""
+        _ffi.require_gpu(tensor, scales, cols)
+        L = _ffi.lib()
+        tensor = tensor.contiguous()
+        G, g = self._geometry(tensor)
+        e8m0 = self.scale_format == 'e8m0'
+        static = scales is not None
+        if static:
+            s = scales.reshape(-1).to(tensor.device).contiguous()
+            if s.numel() != G:
+                raise ValueError(f'FloatQuantizer: {s.numel()} scales for {G} rows')
+            if e8m0 and s.dtype != torch.uint8:
+                raise ValueError(f"FloatQuantizer scale_format='e8m0': static scales are uint8 exponent bytes, got {s.dtype}")
+            sdtype = s.dtype
+        else:
+            sdtype = torch.uint8 if e8m0 else tensor.dtype
+            s = torch.empty(G, dtype=sdtype, device=tensor.device)
+        K = 0
+        if cols is not None:
+            K = cols.numel()
+            cols = cols.reshape(-1).to(tensor.dtype).contiguous()
+            if K % g or (G * g) % K:
+                raise ValueError(f'FloatQuantizer: {K} column multipliers for rows of {g}')
+        out = torch.empty_like(tensor) if fake else torch.empty(tensor.shape, dtype=torch.uint8, device=tensor.device)
+        ws = None if static else _ffi.workspace(L.llmc_fpx_quant_ws_bytes(G, g), tensor.device)
+        _ffi.check(L.llmc_fpx_quant(_ffi.ptr(tensor), _ffi.dt(tensor), G, g, _ffi.ptr(cols), K,
+                                    int(bool(fake)) | self._mode | (0x800 if raw_scales else 0), _ffi.ptr(out), _ffi.ptr(s),
+                                    0 if e8m0 else _ffi.dt(sdtype), int(static), _ffi.ptr(ws), _ffi.stream()), 'llmc_fpx_quant')
+        return out, s.reshape(self._qparam_shape(tensor))
+
+    def _decode(self, codes):
+        """uint8 codes of a narrow format -> their values in fp32 (a 16- / 64-entry table: exact)."""
+        n = 1 << self.num_bits
+        c = torch.arange(n, dtype=torch.int32)
+        e, m = (c >> self.m_bits) & ((1 << self.e_bits) - 1), c & ((1 << self.m_bits) - 1)
+        bias = 2 ** (self.e_bits - 1) - 1
+        mag = torch.where(e == 0, m.double() * 2.0 ** (1 - bias - self.m_bits),
+                          (1 + m.double() * 2.0 ** -self.m_bits) * 2.0 ** (e.double() - bias))
+        sign = torch.where((c >> (self.e_bits + self.m_bits)) & 1 == 1, -1.0, 1.0).double()
+        table = (sign * mag).float().to(codes.device)         # -0.0 keeps its sign: (-1) * 0
+        return table[codes.long()]
 
     # ---- per_block (quant.py:132-143, 612-658): b x b tiles of a 2-D weight, fp32 scales [M/b, 1, N/b, 1] ----------
     def _run_block(self, weight, fake, scales=None):
@@ -726,9 +824,13 @@ class FloatQuantizer(BaseQuantizer):
             bits, _ = self._run_block(tensor.reshape(mb * b, nb * b), False, scales=scales)
             return bits.view(self._tdtype).float().view(mb, b, nb, b)
         bits, _ = self._run(tensor, False, scales=scales)
+        if self.narrow:
+            return self._decode(bits).reshape(tensor.shape)
         return bits.view(self._tdtype).float().reshape(tensor.shape)
 
     def dequant(self, tensor, scales, zeros):
+        if self.narrow and torch.is_tensor(scales) and scales.dtype == torch.uint8:        # e8m0 bytes: 2^(code - 127)
+            scales = torch.ldexp(torch.ones((), device=scales.device), scales.to(torch.int32) - 127)
         return (tensor - zeros.to(tensor.device) if torch.is_tensor(zeros) else tensor - zeros) * scales
 
     def quant_dequant(self, tensor, scales, zeros, qmax, qmin):
@@ -755,6 +857,12 @@ class FloatQuantizer(BaseQuantizer):
         return out.reshape(weight.shape)
 
     def _finish(self, bits, scales, shape):
+        if self.narrow:
+            # our extension (the reference asserts e4m3 / e5m2 here): e2m1 packed two per byte, e3m2 one code per byte
+            codes = bits.reshape(shape)
+            weight = pack_fp4(codes.reshape(-1, shape[-1])).reshape(*shape[:-1], shape[-1] // 2) if self.bit == 'e2m1' else codes
+            qshape = 1 if self.granularity == 'per_tensor' else (shape[0], -1)
+            return weight, scales.reshape(qshape), None
         weight = bits.view(self._tdtype).reshape(shape)
         qshape = 1 if self.granularity == 'per_tensor' else (shape[0], -1)
         return weight, scales.reshape(qshape), None
@@ -772,11 +880,57 @@ class FloatQuantizer(BaseQuantizer):
             return bits.view(torch.float8_e4m3fn), s, None
         bits, scales = self._run(self.reshape_tensor(weight), False, scales=args['scales'])
         # quant.py:1062: the scales the reference returns have been through `scales[scales == 0] = 1`
+        if self.narrow and scales.dtype == torch.uint8:
+            return self._finish(bits, scales, weight.shape)
         return self._finish(bits, torch.where(scales == 0, torch.ones_like(scales), scales), weight.shape)
 
     def __repr__(self):
         return (f'FloatQuantizer(bit={self.bit},e_bits={self.e_bits}, m_bits={self.m_bits},'
                 f'granularity={self.granularity},kwargs={self.kwargs}, qmin={self.qmin}, qmax={self.qmax})')
+
+
+_FPX_FMT = {'e2m1': 2, 'e3m2': 3}
+
+
+def pack_fp4(codes):
+    """e2m1 codes [R, K] (uint8, one per byte, K even) -> [R, K / 2] bytes, element 2i in the low nibble and 2i + 1 in the high
+    one (the float4_e2m1fn_x2 / MX convention)."""
+    _ffi.require_gpu(codes)
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.shape[1] % 2:
+        raise ValueError(f'pack_fp4: uint8 codes [R, K] with K even, got {codes.dtype} {tuple(codes.shape)}')
+    codes = codes.contiguous()
+    R, K = codes.shape
+    packed = torch.empty((R, K // 2), dtype=torch.uint8, device=codes.device)
+    _ffi.check(_ffi.lib().llmc_fp4_pack(_ffi.ptr(codes), R, K, _ffi.ptr(packed), _ffi.stream()), 'llmc_fp4_pack')
+    return packed
+
+
+def dequant_fpx(codes, scales, bit, group_size, dtype, packed=None):
+    """The stored form of a narrow-format weight back to numbers: decode(code) * scale in fp32, rounded once to `dtype` — the
+    value fake_quant_weight_* writes. codes [R, K] (one per byte) or, for e2m1 with packed=True (the default for e2m1),
+    [R, K / 2] as pack_fp4 leaves them; scales: one per group of group_size columns (per_channel: group_size = K; per_tensor:
+    one scale, group_size = R * K) in a float dtype, or uint8 e8m0 bytes."""
+    _ffi.require_gpu(codes, scales)
+    if bit not in _FPX_FMT:
+        raise NotImplementedError(f'dequant_fpx: bit={bit} (e2m1 and e3m2 have a stored form)')
+    packed = (bit == 'e2m1') if packed is None else bool(packed)
+    if packed and bit != 'e2m1':
+        raise NotImplementedError('dequant_fpx: only e2m1 has a packed form (dense FP6 packing is not provided)')
+    codes = codes.contiguous()
+    if codes.dtype != torch.uint8 or codes.dim() != 2:
+        raise ValueError(f'dequant_fpx: uint8 codes [R, K], got {codes.dtype} {tuple(codes.shape)}')
+    R, K = codes.shape[0], codes.shape[1] * (2 if packed else 1)
+    g = int(group_size)
+    if g <= 0 or (R * K) % g:
+        raise ValueError(f'dequant_fpx: group size {g} does not divide {R} x {K}')
+    s = scales.reshape(-1).contiguous()
+    if s.numel() != R * K // g:
+        raise ValueError(f'dequant_fpx: {s.numel()} scales for {R * K // g} groups')
+    sdt = -1 if s.dtype == torch.uint8 else _ffi.dt(s)
+    out = torch.empty((R, K), dtype=dtype, device=codes.device)
+    _ffi.check(_ffi.lib().llmc_fpx_dequant(_ffi.ptr(codes), _FPX_FMT[bit], int(packed), _ffi.ptr(s), sdt, R * K // g, g,
+                                           _ffi.ptr(out), _ffi.dt(dtype), _ffi.stream()), 'llmc_fpx_dequant')
+    return out
 
 
 def weight_cast_to_bf16(weight, scale, block_size):

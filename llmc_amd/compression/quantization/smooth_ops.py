@@ -107,6 +107,9 @@ def act_step(x, scales, aquantizer, force_two_kernels=False):
     """aquantizer.fake_quant_act_dynamic(x / scales.view(1, -1)) (osplus.py:156-157). One kernel where act_step_fused_ok, else
     awq_ops.div_cols followed by the quantizer (same bits)."""
     _ffi.require_gpu(x, scales)
+    if getattr(aquantizer, 'narrow', False):
+        raise NotImplementedError(f'act_step with a float quantizer bit={aquantizer.bit}: the fused activation step knows the e4m3 '
+                                  'and e5m2 formats only')
     if force_two_kernels or not act_step_fused_ok(x, aquantizer):
         return aquantizer.fake_quant_act_dynamic(awq_ops.div_cols(x, scales))
     L = _ffi.lib()

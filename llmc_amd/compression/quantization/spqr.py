@@ -133,6 +133,9 @@ class SpQR(GPTQ):
         if self.wquantizer.calib_algo == 'hqq':
             raise NotImplementedError('SpQR with calib_algo=hqq: the solver would run per group inside the column loop; '
                                       'not built. method: HQQ quantizes weights with it.')
+        if getattr(self.wquantizer, 'narrow', False):
+            raise NotImplementedError(f'SpQR with a float quantizer bit={self.wquantizer.bit}: the column loop rounds to an '
+                                      'integer grid with zero points; the e2m1 / e3m2 float grids are not built into it')
         self.true_sequential = special['true_sequential']
         self.actorder = special['actorder']
         self.percdamp = special['percdamp']

@@ -145,4 +145,55 @@ __device__ __forceinline__ uint8_t fp8_encode(float t, int fmt, int sem, float* 
 }
 __device__ __forceinline__ float fp8_format_max(int fmt) { return fmt ? 57344.0f : 448.0f; }
 
+// ---- the narrow OCP formats: e2m1 (FP4: s ee m, bias 1, max 6) and e3m2 (FP6: s eee mm, bias 3, max 28) -----------------
+// No infinity, no NaN: all 2^E exponent codes carry numbers. bias = 2^(E-1) - 1, smallest normal 2^(1 - bias), subnormal step
+// 2^(1 - bias - M), largest value (2 - 2^-M) 2^(2^E - 1 - bias). qtorch_quantize<E, M> above keeps the top exponent code for
+// infinity, so ITS largest value is half of that (3 / 14) — a subset of the OCP grid, with the same subnormals.
+template <int E, int M> struct fpx_fmt {
+    static constexpr int bias = (1 << (E - 1)) - 1, min_exp = 1 - bias, max_exp = (1 << E) - 1 - bias;
+    static constexpr uint32_t lo_bits = (uint32_t)(127 + min_exp) << 23;                                  // smallest normal
+    static constexpr uint32_t max_bits = ((uint32_t)(127 + max_exp) << 23) | (((1u << M) - 1u) << (23 - M));
+    static constexpr uint32_t sub_up = (uint32_t)(127 + M - min_exp) << 23, sub_dn = (uint32_t)(127 + min_exp - M) << 23;
+};
+
+// 'ocp' semantics: round to nearest even onto the OCP grid (subnormals included), saturate at +-max (inf too); a NaN gives
+// max with the input's sign (the formats have none; a documented choice); the sign survives on a zero result, like the e4m3
+// cast above. No control flow: both ranges are evaluated and one is selected.
+template <int E, int M> __device__ __forceinline__ float fpx_ocp_quantize(float x) {
+    typedef fpx_fmt<E, M> F;
+    constexpr uint32_t keep = ~((1u << (23 - M)) - 1u), half_m1 = (1u << (22 - M)) - 1u;
+    const uint32_t u = __float_as_uint(x), a = u & 0x7fffffffu;
+    uint32_t n = (a + half_m1 + ((a >> (23 - M)) & 1u)) & keep;            // RNE on the M-bit mantissa; inf / NaN stay above max
+    n = n > F::max_bits ? F::max_bits : n;
+    const float d = rintf(__uint_as_float(a) * __uint_as_float(F::sub_up)) * __uint_as_float(F::sub_dn);   // exact products
+    const uint32_t r = a < F::lo_bits ? __float_as_uint(d) : n;
+    return __uint_as_float(r | (u & 0x80000000u));
+}
+
+// value ON the OCP grid -> code (sign in bit E + M, the bits above it zero), and back. Exact both ways.
+template <int E, int M> __device__ __forceinline__ uint8_t fpx_encode(float v) {
+    typedef fpx_fmt<E, M> F;
+    const uint32_t u = __float_as_uint(v), a = u & 0x7fffffffu;
+    const uint32_t sub = (uint32_t)(__uint_as_float(a) * __uint_as_float(F::sub_up));
+    const uint32_t nrm = ((((a >> 23) - (uint32_t)(127 + F::min_exp - 1)) << M) | ((a >> (23 - M)) & ((1u << M) - 1u)));
+    return (uint8_t)(((u >> 31) << (E + M)) | (a < F::lo_bits ? sub : nrm));
+}
+template <int E, int M> __device__ __forceinline__ float fpx_decode(uint32_t c) {
+    typedef fpx_fmt<E, M> F;
+    const uint32_t e = (c >> M) & ((1u << E) - 1u), m = c & ((1u << M) - 1u);
+    const float sub = (float)m * __uint_as_float(F::sub_dn);
+    const float nrm = __uint_as_float(((e + (uint32_t)(127 + F::min_exp - 1)) << 23) | (m << (23 - M)));
+    return __uint_as_float(__float_as_uint(e ? nrm : sub) | (((c >> (E + M)) & 1u) << 31));
+}
+
+// One element of a narrow-format FloatQuantizer step. fmt: 2 = e2m1, 3 = e3m2 (0 / 1 are the 8-bit formats above); ocp: 0 =
+// qtorch.float_quantize (any input: the general template), 1 = the OCP rounding above. Returns the value on the grid.
+__device__ __forceinline__ float fpx_quantize(float t, int fmt, int ocp) {
+    if (fmt == 2) return ocp ? fpx_ocp_quantize<2, 1>(t) : qtorch_quantize<2, 1>(t);
+    return ocp ? fpx_ocp_quantize<3, 2>(t) : qtorch_quantize<3, 2>(t);
+}
+__device__ __forceinline__ uint8_t fpx_code(float v, int fmt) { return fmt == 2 ? fpx_encode<2, 1>(v) : fpx_encode<3, 2>(v); }
+__device__ __forceinline__ float fpx_value(uint32_t c, int fmt) { return fmt == 2 ? fpx_decode<2, 1>(c) : fpx_decode<3, 2>(c); }
+__device__ __forceinline__ float fpx_format_max(int fmt) { return fmt == 2 ? 6.0f : 28.0f; }
+
 }  // namespace llmc

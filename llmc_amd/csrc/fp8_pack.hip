@@ -419,6 +419,10 @@ extern "C" int llmc_fp8_quant(const void* W, int dt, int64_t G, int64_t g, int f
                               int sdt, int static_scales, void* ws, llmc_stream_t stream) {
     LLMC_REQUIRE(dtype_ok(dt) && dtype_ok(sdt) && W && out && scales && G > 0 && g > 0, "fp8_quant: bad argument");
     LLMC_REQUIRE(static_scales || ws, "fp8_quant: workspace required for dynamic scales");
+    if (((fake >> FP8_FMT_SHIFT) & 3) > 1) {
+        set_last_error_msg("fp8_quant: format is 0 (e4m3) or 1 (e5m2); e2m1 / e3m2 are llmc_fpx_quant's");
+        return LLMC_ENOTSUP;
+    }
     void* amax = ws;
     if (!static_scales) {
         void* ws2 = (char*)ws + (((size_t)G * 4 + 255) & ~(size_t)255);

@@ -35,6 +35,7 @@ extern "C" {
 #define LLMC_F16 0
 #define LLMC_BF16 1
 #define LLMC_F32 2
+#define LLMC_F64 3 /* llmc_hadamard only */
 /* OR-ed into the dtype code of llmc_quant_static's scales / zeros: the operand is a 0-dim tensor in the reference
  * (per_tensor qparams): it is used at its own precision but ATen leaves it out of type promotion, so every op still
  * rounds to the weight dtype (quant.py:699-717 with the 0-dim scales of quant.py:132-136,555-556). */
@@ -597,6 +598,18 @@ int llmc_osplus_scale(const float* cmx, const float* cmn, const void* thresholds
 int llmc_osplus_act_step_tier(int dt, int64_t K);
 int llmc_osplus_act_step(const void* X, const void* s, int dt, int64_t N, int64_t K, int kind, int sym, float qmin, float qmax,
                          int fp8_mode, void* out, llmc_stream_t stream);
+
+/* ---- Walsh-Hadamard transform (hadamard_utils.py:72-122 matmul_hadU / matmul_hadU_cuda, module_utils.py:460-503 Rotater) ------
+ * x, y: contiguous [outer, n, inner] of dt (F16 / BF16 / F32 / F64); y == x is allowed. Along the middle axis
+ *   y[o, a*m + j, c] = scale * sum_{b, i} hadK[a][b] * S_m[j][i] * x[o, b*m + i, c],   n = K0 * m,
+ * S_m the Sylvester matrix of order m (a power of two, >= 1) in natural order, hadK a device [K0, K0] fp32 matrix of +-1 (null
+ * when K0 == 1). Row transforms use inner = 1; transforms across heads or along a weight's output axis inner > 1. Additions and
+ * subtractions only, accumulated in fp32 (fp64 for F64); scale (rounded to fp32 on the fp32 path) is applied once at the end,
+ * then one rounding to dt. A row stays on chip between its load and its store. LLMC_ENOTSUP (llmc_hip_last_error names it):
+ * K0 > 64, n / K0 not a power of two, a row too long to stay resident (n * 4 bytes, 8 for F64, plus the factor matrix above
+ * 160 KiB, or n / K0 > 32768). Allocates nothing, runs in stream order. */
+int llmc_hadamard(const void* x, void* y, int dt, int64_t outer, int64_t n, int64_t inner, const float* hadK, int K0,
+                  double scale, llmc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'csrc', 'libllmc_hip.so')
 
 F16, BF16, F32 = 0, 1, 2
+F64 = 3               # LLMC_F64: llmc_hadamard only
 OUT_FAKE, OUT_I32, OUT_I8, OUT_U8 = 0, 1, 2, 3
 SCALAR_QPARAM = 16   # LLMC_SCALAR_QPARAM
 LINEAR_YBLOCKED = 4   # LLMC_LINEAR_YBLOCKED
@@ -117,6 +118,7 @@ SIGNATURES = {
     'llmc_osplus_scale': (_i32, [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp]),
     'llmc_osplus_act_step_tier': (_i32, [_i32, _i64]),
     'llmc_osplus_act_step': (_i32, [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _f32, _f32, _i32, _vp, _vp]),
+    'llmc_hadamard': (_i32, [_vp, _vp, _i32, _i64, _i64, _i64, _vp, _i32, _f64, _vp]),
     'llmc_test_sgemm': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                _i32, _i32, _vp]),
     'llmc_test_sgemm_phased': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),

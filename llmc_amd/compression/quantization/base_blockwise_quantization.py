@@ -5,8 +5,10 @@ subclasses registered in ALGO_REGISTRY ('GPTQ', 'Awq', 'RTN') drop into llmc's `
 In scope: quantizer selection, collect_block_qparams, the block / subset loop with
 true_sequential re-hooking and quant_out, apply_scale (LN->fc and fc->fc), scaling_input/update_input_feat,
 static per-tensor activation qparams, deploy to fake / real-quant wrappers. Out of scope and rejected loudly:
-rotations (QuaRot), KV-cache quantization, quantized attention / act-fn modules, token reduction, FP8
-block-wise checkpoints (DeepSeek). Mixed precision (`ignored_layers`) is in since round 4.
+KV-cache quantization, quantized attention / act-fn modules, token reduction, FP8
+block-wise checkpoints (DeepSeek). Mixed precision (`ignored_layers`) is in since round 4. QuaRot's rotations
+(rotate_* / fuse_ln_fcs / replace_rotate_linears, base_…:286-300, 780-874) run on the Walsh-Hadamard kernel
+(hadamard_utils.py); `special.online_rotate` is taken by the classes that set `supports_online_rotate` (Quarot, GPTQ).
 """
 import copy
 import functools
@@ -22,7 +24,8 @@ from ..blockwise_optimization import BlockwiseOpt
 from . import awq_ops
 from .module_utils import (_LLMC_LINEAR_TYPES_, _LLMC_LN_TYPES_, _REALQUANT_LINEAR_MAP_,
                            _TRANSFORMERS_LINEAR_TYPES_, _TRANSFORMERS_LN_TYPES_, EffcientFakeQuantLinear,
-                           FakeQuantLinear, OriginFloatLinear)
+                           FakeQuantLinear, OriginFloatLinear, RotateLinear)
+from .hadamard_utils import apply_exact_had_to_linear, get_hadK, rotate_left_t, rotate_right
 from .quant import FloatQuantizer, IntegerQuantizer
 
 
@@ -48,6 +51,10 @@ def _world():
 
 
 class BaseBlockwiseQuantization(BlockwiseOpt):
+    # `special.online_rotate` (online Hadamard transforms in front of down_proj / o_proj) is implemented by the subclasses that
+    # say so; every other algorithm keeps refusing it
+    supports_online_rotate = False
+
     def __init__(self, model, quant_config, input, padding_mask, config):
         super().__init__(model, quant_config, input, padding_mask, config)
         self.dev = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else None
@@ -104,6 +111,11 @@ class BaseBlockwiseQuantization(BlockwiseOpt):
             return {'w_q': partial(self.w_q, wquantizer=self.wquantizer), 'quant_config': self.quant_config}
         if mode == 'origin_float':
             return {}
+        if mode == 'online_rotate':                # base_…:98-111
+            full = 'down_proj' in name
+            had_K, K = get_hadK(self.intermediate_size if full else self.num_heads)
+            return {'had_K': had_K, 'K': K, 'online_full_had': full, 'online_partial_had': 'o_proj' in name,
+                    'had_dim': None if full else self.hidden_size // self.num_heads, 'fp32_had': self.fp32_had}
         raise NotImplementedError(f'replacement mode {mode} is outside the hot path')
 
     # ---- configuration (base_…:133-300) ------------------------------------------------------------
@@ -172,9 +184,10 @@ class BaseBlockwiseQuantization(BlockwiseOpt):
         if self.save_scale:
             self.scale_path = special['scale_path']
             self.act_scales = {}
-        if special.get('online_rotate', False):
-            raise NotImplementedError('online rotation is outside the hot path')
-        self.online_rotate = False
+        self.online_rotate = special.get('online_rotate', False)
+        if self.online_rotate and not self.supports_online_rotate:
+            raise NotImplementedError(f'online rotation is implemented for Quarot and GPTQ only, not for {type(self).__name__}')
+        self.fp32_had = special.get('fp32_had', False)
         self.modality = _get(qc, 'modality', 'language')
         # base_…:134-135: block size of a block-wise FP8 checkpoint (model.fp8_block_size; DeepSeek-V3: 128)
         self.fp8_block_size = getattr(self.model, 'fp8_block_size', None) or 128
@@ -188,6 +201,14 @@ class BaseBlockwiseQuantization(BlockwiseOpt):
             self.auto_clipper.bf16_to_fp8 = self._bf16_to_fp8
         self.do_gqa_trans = special.get('do_gqa_trans', False)
         self.set_model_config()
+        if self.online_rotate:
+            # the reference asserts model.type in ['Opt', 'Llama'] (base_…:251-253); here any adapter whose config has the sizes
+            # the Hadamard factors are chosen from will do. Unsupported sizes fail now, not in the middle of a block.
+            for k in ('hidden_size', 'num_heads', 'intermediate_size'):
+                if not getattr(self, k, None):
+                    raise NotImplementedError(f'online rotation needs model_config.{k}')
+            get_hadK(self.intermediate_size)
+            get_hadK(self.num_heads)
 
     def set_model_config(self):
         mc = getattr(self.model, 'model_config', None)
@@ -198,10 +219,19 @@ class BaseBlockwiseQuantization(BlockwiseOpt):
         self.num_heads = getattr(mc, 'num_attention_heads', None)
         if self.hidden_size and self.num_heads:
             self.head_dim = self.hidden_size // self.num_heads
+        if hasattr(mc, 'intermediate_size'):
+            self.intermediate_size = mc.intermediate_size
         if getattr(mc, 'num_key_value_heads', None):
             self.num_key_value_heads = mc.num_key_value_heads
             self.num_key_value_groups = self.num_heads // self.num_key_value_heads
             self.has_gqa = self.num_key_value_groups > 1
+
+    def replace_rotate_linears(self, block):
+        """base_…:286-300: down_proj / o_proj (fc2 / out_proj) become RotateLinears that transform their input online."""
+        for n, m in list(block.named_modules()):
+            if isinstance(m, torch.nn.Linear) and ('down_proj' in n or 'o_proj' in n or 'fc2' in n or 'out_proj' in n):
+                self.model.replace_module_subset(RotateLinear, block, {'layers': {n: m}}, None,
+                                                 self.get_replacement_params(mode='online_rotate', w_only=self.w_only, name=n))
 
     # ---- RTN qparams of every Linear (base_…:338-365) -------------------------------------------------
     @torch.no_grad()
@@ -436,6 +466,77 @@ class BaseBlockwiseQuantization(BlockwiseOpt):
             # (isnan has no float8 kernel: an e4m3fn NaN is the code 0x7f / 0xff)
             nan = ((p.view(torch.uint8) & 0x7f) == 0x7f) if p.dtype == torch.float8_e4m3fn else torch.isnan(p)
             assert nan.sum() == 0
+
+    # ---- QuaRot (base_…:780-874): the reference's order of casts — .double(), operate, .to(dtype) after every step. Q is a
+    # hadamard_utils.RandomHadamard (W Q = T(W o sigma) in fp64 on the kernel) or a dense float64 tensor (fp64 matmul).
+    def _no_fp8(self, layer):
+        if self._is_fp8(layer):
+            raise NotImplementedError('rotating a block-wise FP8 checkpoint is outside the hot path')
+
+    def _rot_dev(self, t):
+        return t.to(device=self.dev if self.dev is not None else 'cuda', dtype=torch.float64)
+
+    @torch.no_grad()
+    def rotate_pre_layers(self, pre_layers, Q):
+        for layer in pre_layers:
+            self._no_fp8(layer)
+            dtype, dev = layer.weight.dtype, layer.weight.device
+            layer.weight.data = rotate_right(self._rot_dev(layer.weight.data), Q).to(device=dev, dtype=dtype)
+
+    @torch.no_grad()
+    def rotate_post_layers(self, post_layers, Q, exact_had=False):
+        for layer in post_layers:
+            self._no_fp8(layer)
+            dtype, dev = layer.weight.dtype, layer.weight.device
+            layer.weight.data = rotate_left_t(self._rot_dev(layer.weight.data), Q).to(device=dev, dtype=dtype)
+            if exact_had and self.online_rotate:
+                apply_exact_had_to_linear(layer, had_dim=-1, output=False)
+            if hasattr(layer, 'bias') and layer.bias is not None:
+                layer.bias.data = rotate_left_t(self._rot_dev(layer.bias.data), Q).to(device=dev, dtype=dtype)
+
+    @torch.no_grad()
+    def rotate_embeddings(self, Q):
+        embeddings = self.model.get_embed_layers()
+        assert len(embeddings) == 1
+        for layer in embeddings:
+            dtype = layer.weight.data.dtype
+            layer.weight.data = rotate_right(self._rot_dev(layer.weight.data), Q).to(device='cpu', dtype=dtype)
+
+    @torch.no_grad()
+    def rotate_head(self, Q):
+        for layer in self.model.get_head_layers():
+            dtype = layer.weight.data.dtype
+            layer.weight.data = rotate_right(self._rot_dev(layer.weight.data), Q).to(device='cpu', dtype=dtype)
+
+    @torch.no_grad()
+    def fuse_ln_fcs(self, ln, fcs):
+        for fc in fcs:
+            self._no_fp8(fc)
+            fc_dtype = fc.weight.dtype
+            has_ln_bias = hasattr(ln, 'bias') and ln.bias is not None
+            if has_ln_bias:
+                W = fc.weight.data.double().clone()
+            fc.weight.data = (fc.weight.data.double() * ln.weight.double().to(fc.weight.device)).to(fc_dtype)
+            if has_ln_bias:
+                if fc.bias is None:
+                    fc.bias = torch.nn.Parameter(torch.zeros(fc.out_features, dtype=torch.float64, device=W.device))
+                fc.bias.data = fc.bias.data.double().to(device=W.device) + torch.matmul(W, ln.bias.double().to(W.device))
+                fc.bias.data = fc.bias.data.to(fc_dtype)
+
+    @torch.no_grad()
+    def remove_mean_from_embed(self):
+        for layer in self.model.get_embed_layers():
+            W = layer.weight.data.double()
+            layer.weight.data = (W - W.mean(dim=-1, keepdim=True)).to(layer.weight.data.dtype)
+
+    @torch.no_grad()
+    def bake_mean_into_fc(self, fc):
+        fc_dtype = fc.weight.dtype
+        W_ = fc.weight.data.double()
+        fc.weight.data = (W_ - W_.mean(dim=-2, keepdim=True)).to(fc_dtype)
+        if hasattr(fc, 'bias') and fc.bias is not None:
+            b_ = fc.bias.data.double()
+            fc.bias.data = (b_ - b_.mean()).to(fc_dtype)
 
     @torch.no_grad()
     def scaling_input(self, x, scales, is_gqa):

@@ -29,12 +29,14 @@ from .base_blockwise_quantization import BaseBlockwiseQuantization, _world
 from . import gptq_ops
 from .gptq_pipeline import GptqConfig, owq_permutation, quantize_owq, quantize_stacked
 from .hessian import HessianAccumulator
-from .module_utils import _LLMC_LINEAR_TYPES_, _TRANSFORMERS_LINEAR_TYPES_
+from .module_utils import _LLMC_LINEAR_TYPES_, _TRANSFORMERS_LINEAR_TYPES_, RotateLinear
 from .quant import FloatQuantizer
 
 
 @ALGO_REGISTRY
 class GPTQ(BaseBlockwiseQuantization):
+    supports_online_rotate = True      # step 2 of the QuaRot pipeline: o_proj / down_proj transform their input online
+
     def __init__(self, model, quant_config, input, padding_mask, config, modality='language'):
         super().__init__(model, quant_config, input, padding_mask, config)
         self.model_dtype = next(self.model.model.parameters()).dtype
@@ -50,6 +52,11 @@ class GPTQ(BaseBlockwiseQuantization):
             raise NotImplementedError('GPTQ with calib_algo=hqq: the solver would run per group inside the column loop '
                                       '(gptq.py:216-221); not built. method: HQQ quantizes weights with it.')
         self.true_sequential = special['true_sequential']
+        if getattr(self, 'online_rotate', False) and not self.true_sequential:
+            # o_proj / down_proj become RotateLinears in block_transform (gptq.py:87-88), after the first forward of the block:
+            # only the re-hooked forwards of true_sequential see them, a single-pass Hessian would be that of the unrotated input
+            raise NotImplementedError('GPTQ with online_rotate needs true_sequential=True: the Hessians of o_proj / down_proj '
+                                      'must be accumulated from their rotated inputs, after the RotateLinears are in place')
         self.static_groups = special['static_groups']
         self.actorder = special['actorder']
         self.percdamp = special['percdamp']
@@ -194,6 +201,8 @@ class GPTQ(BaseBlockwiseQuantization):
             # (base_blockwise_quantization.py:506-526, gptq.py:311-315) — accumulating them now is wasted work
             # (for a Llama block: 3 of the 4 distinct Hessians, the widest one included)
             return
+        if isinstance(layer, RotateLinear):
+            inp = layer.rotater.rotate(inp)          # gptq.py:262-264: the Hessian of what the product sees
         c = self.layers_cache[name]
         c['calls'] += 1
         g = self._groups[self._group_of[name]]
@@ -313,6 +322,8 @@ class GPTQ(BaseBlockwiseQuantization):
 
     @torch.no_grad()
     def block_transform(self, block, input_feat, block_kwargs):
+        if getattr(self, 'online_rotate', False):
+            self.replace_rotate_linears(block)
         if self.owq and not hasattr(self, 'n_out_dict'):       # gptq.py:89-93: n_outs follow get_block_linears' order
             self.n_out_dict = {n: self.n_outs[i] for i, n in enumerate(self.model.get_block_linears(block))}
         if not getattr(self, 'true_sequential', False) and _world() == 1:

@@ -38,6 +38,117 @@ def _copy_buf(dst, src):
             dst.register_buffer(name, p.data)
 
 
+def _keep_rotater(dst, ori_module):
+    """module_utils.py:408-411, 604-607, 694-697 of the reference: a wrapper of a RotateLinear (its `buf_rotate` buffer came
+    over with _copy_buf) keeps that module's rotater and rotates its input first; any other wrapper has buf_rotate = False.
+    (A copied buffer of that name cannot be overwritten by a plain attribute, hence the order.)"""
+    if bool(getattr(dst, 'buf_rotate', False)):
+        dst.rotater = ori_module.rotater
+    else:
+        dst.buf_rotate = False
+        dst.rotater = None
+
+
+class LlmcRMSNorm(nn.Module):
+    """module_utils.py:321-345: RMSNorm without a scale (QuaRot fuses the scale into the following Linears; `weight` is kept as
+    ones so that the module still looks like a norm)."""
+
+    def __init__(self, weight, eps=1e-6):
+        super().__init__()
+        self.variance_epsilon = eps
+        self.weight = nn.Parameter(torch.ones_like(weight))
+
+    def forward(self, hidden_states):
+        input_dtype = hidden_states.dtype
+        variance = hidden_states.to(torch.float32).pow(2).mean(-1, keepdim=True)
+        hidden_states = hidden_states * torch.rsqrt(variance + self.variance_epsilon)
+        return hidden_states.to(input_dtype)
+
+    @classmethod
+    @torch.no_grad()
+    def new(cls, module):
+        eps = module.eps if hasattr(module, 'eps') else module.variance_epsilon
+        return cls(module.weight, eps)
+
+    def __repr__(self):
+        return 'LlmcRMSNorm()'
+
+
+class Rotater:
+    """module_utils.py:460-503: the online Hadamard transform in front of down_proj (full: along the row, K / had_K the factor
+    of the intermediate size) and o_proj (partial: across the heads, [tokens, num_heads, had_dim] with the heads in the middle)
+    on llmc_hadamard. `fp32_had` decides the dtype handed to the kernel. One difference from the reference: with fp32_had False
+    and K > 1 it rounds to 16 bits between the fast transform and the had_K product; this rounds once, at the end (the kernel
+    accumulates in fp32 either way)."""
+
+    def __init__(self, online_full_had, online_partial_had, fp32_had, K, had_K=None, had_dim=None):
+        self.online_full_had = online_full_had
+        self.online_partial_had = online_partial_had
+        self.fp32_had = fp32_had
+        self.K = K
+        self.had_K = had_K
+        self.had_dim = had_dim
+
+    def rotate(self, x):
+        import math
+
+        from .hadamard_utils import hadamard_transform, matmul_hadU_cuda
+        x_dtype = x.dtype
+        if self.K > 1 and self.had_K.device != x.device:
+            self.had_K = self.had_K.to(x.device)
+        if self.online_full_had:
+            if self.fp32_had:
+                x = matmul_hadU_cuda(x.float(), self.had_K, self.K).to(x_dtype)
+            else:
+                x = matmul_hadU_cuda(x, self.had_K, self.K)
+        elif self.online_partial_had:
+            if self.fp32_had:
+                x = x.float()
+            heads = x.shape[-1] // self.had_dim
+            x = hadamard_transform(x, heads, self.had_dim, self.had_K, self.K, 1 / math.sqrt(heads))
+            if self.fp32_had:
+                x = x.to(x_dtype)
+        return x
+
+
+class RotateLinear(nn.Module):
+    """module_utils.py:506-583: rotate the input, then the product (hip_linear)."""
+
+    def __init__(self, weight, bias, ori_module, online_full_had, online_partial_had, fp32_had, K, had_K, had_dim):
+        super().__init__()
+        self.register_buffer('weight', weight)
+        if bias is not None:
+            self.register_buffer('bias', bias)
+        else:
+            self.bias = None
+        _copy_buf(self, ori_module)
+        self.rotater = Rotater(online_full_had, online_partial_had, fp32_had, K, had_K, had_dim)
+        self.register_buffer('buf_rotate', torch.tensor(True))
+
+    def forward(self, x):
+        return hip_linear(self.rotater.rotate(x), self.weight, self.bias)
+
+    @classmethod
+    @torch.no_grad()
+    def new(cls, module, online_full_had, online_partial_had, fp32_had, K, had_K, had_dim):
+        bias = module.bias.data if module.bias is not None else None
+        m = cls(module.weight.data, bias, ori_module=module, online_full_had=online_full_had,
+                online_partial_had=online_partial_had, fp32_had=fp32_had, K=K, had_K=had_K, had_dim=had_dim)
+        m.in_features, m.out_features = module.in_features, module.out_features
+        return m
+
+    @classmethod
+    def get_func_name(cls, any_callable):
+        return _func_name(any_callable)
+
+    def register_activation_parameters(self, named_parameters):
+        pass
+
+    def __repr__(self):
+        return (f'RotateLinear(in_features={self.in_features},out_features={self.out_features},'
+                f'bias={self.bias is not None},online_rotate={self.buf_rotate})')
+
+
 class OriginFloatLinear(nn.Module):
     """module_utils.py OriginFloatLinear: plain float forward, keeps buf_* (used by deploy('origin_float'))."""
 
@@ -49,9 +160,12 @@ class OriginFloatLinear(nn.Module):
         else:
             self.bias = None
         _copy_buf(self, ori_module)
+        _keep_rotater(self, ori_module)
 
     @torch.no_grad()
     def forward(self, x):
+        if self.rotater is not None:
+            x = self.rotater.rotate(x)
         return hip_linear(x, self.weight, self.bias)
 
     @classmethod
@@ -76,11 +190,13 @@ class FakeQuantLinear(nn.Module):
         self.a_qdq = a_qdq
         self.w_qdq = w_qdq
         _copy_buf(self, ori_module)
-        self.buf_rotate = False
+        _keep_rotater(self, ori_module)
         self.dynamic_quant_weight = False
         self.dynamic_quant_tmp_weight = False
 
     def forward(self, x):
+        if self.rotater is not None:
+            x = self.rotater.rotate(x)
         if self.a_qdq is not None:
             x = self.a_qdq(x, self)
         if not hasattr(self, 'tmp_weight'):
@@ -122,10 +238,12 @@ class EffcientFakeQuantLinear(nn.Module):
             self.bias = None
         self.a_qdq = a_qdq
         _copy_buf(self, ori_module)
-        self.buf_rotate = False
+        _keep_rotater(self, ori_module)
 
     @torch.no_grad()
     def forward(self, x):
+        if self.rotater is not None:
+            x = self.rotater.rotate(x)
         if self.a_qdq is not None:
             x = self.a_qdq(x, self)
         return hip_linear(x, self.weight, self.bias)
@@ -322,8 +440,8 @@ except Exception:  # pragma: no cover
 if hasattr(nn, 'RMSNorm') and nn.RMSNorm not in _TRANSFORMERS_LN_TYPES_:
     _TRANSFORMERS_LN_TYPES_.append(nn.RMSNorm)
 
-_LLMC_LN_TYPES_ = []
-_LLMC_LINEAR_TYPES_ = [LlmcFp8Linear, OriginFloatLinear, FakeQuantLinear, EffcientFakeQuantLinear, VllmRealQuantLinear,
+_LLMC_LN_TYPES_ = [LlmcRMSNorm]
+_LLMC_LINEAR_TYPES_ = [LlmcFp8Linear, RotateLinear, OriginFloatLinear, FakeQuantLinear, EffcientFakeQuantLinear, VllmRealQuantLinear,
                        SglRealQuantLinear, AutoawqRealQuantLinear, MlcllmRealQuantLinear, LightllmRealQuantLinear]
 _REALQUANT_LINEAR_MAP_ = {
     'vllm_quant': VllmRealQuantLinear,

@@ -5,7 +5,8 @@
 with S_m = scipy.linalg.hadamard(m) (Sylvester, natural order). `apply_M` uses S_m = S_a (x) S_b so that a 32768-long row needs
 no dense matrix; `dense_M` is the literal Kronecker product (the two are compared in tests/test_hadamard_utils.py). `paley` is a
 second construction of the factor matrices, independent of llmc_amd's (Euler's criterion instead of a table of squares, explicit
-loops instead of index arithmetic)."""
+loops instead of index arithmetic). `exact_scaled` is the value a scaled transform of small integers must have bit for bit
+(exact sums, one multiplication, one rounding)."""
 import numpy as np
 from scipy.linalg import hadamard
 
@@ -77,6 +78,18 @@ def transform(x, hadK=None, axis=-1, scale=None):
     x = np.asarray(x, dtype=np.float64)
     n = x.shape[axis]
     return apply_M(x, hadK, axis) * (1.0 / fl32_sqrt(n) if scale is None else scale)
+
+
+def exact_scaled(e, scale, dtype):
+    """What llmc_hadamard must return, bit for bit, when e = apply_M(integers) holds integers below 2^24: the sums are exact in
+    any order, so the result is one multiplication by the scale cast to the accumulator type and one rounding to `dtype`.
+    F32 / F16 / BF16: round_dtype(fl32(fl32(e) * fl32(scale))); F64: fl64(e * scale). Returns a torch tensor of `dtype`."""
+    import torch
+    e = np.asarray(e)
+    assert e.dtype.kind == 'i' and np.abs(e).max(initial=0) < 2 ** 24
+    if dtype == torch.float64:
+        return torch.from_numpy(np.ascontiguousarray(e.astype(np.float64) * np.float64(scale)))
+    return torch.from_numpy(np.ascontiguousarray(e.astype(np.float32) * np.float32(scale))).to(dtype)
 
 
 def dense_Q(sigma, hadK=None):

@@ -89,3 +89,76 @@ def test_cpu_tensors_are_refused():
     from llmc_amd.compression.quantization.hadamard_utils import matmul_hadU
     with pytest.raises(_ffi.LlmcHipError):
         matmul_hadU(torch.zeros(4, 64))
+
+
+# ---- the exact oracle of the scaled transforms and the case tables of the width tests (tests/hadamard_cases.py) ------------------
+_DTYPES = (torch.float32, torch.float64, torch.float16, torch.bfloat16)
+
+
+def test_exact_scaled_is_the_dense_product_rounded_the_same_way():
+    """fl32(e) * fl32(scale) has 48 significant bits at the most, so the float64 product is exact and its conversion to float32
+    is the single rounding of the fp32 multiplication; the F64 value is the correctly rounded rational product."""
+    from fractions import Fraction
+    rng = np.random.default_rng(1)
+    for n, K in ((2, 1), (8, 1), (64, 1), (20, 20), (24, 12), (112, 28), (72, 36), (60, 60)):
+        hk = None if K == 1 else O.paley(K)
+        x = rng.integers(-8, 9, size=(3, n), dtype=np.int64)
+        e = x @ O.dense_M(n, hk).T
+        scale = 1.0 / O.fl32_sqrt(n)
+        assert np.array_equal(O.apply_M(x, hk), e)
+        s32 = float(np.float32(scale))
+        p32 = (e.astype(np.float64) * s32).astype(np.float32)
+        for dt in (torch.float32, torch.float16, torch.bfloat16):
+            got = O.exact_scaled(e, scale, dt)
+            assert got.dtype == dt and torch.equal(got, torch.from_numpy(p32).to(dt)), (n, dt)
+        got = O.exact_scaled(e, scale, torch.float64)
+        want = np.array([[float(Fraction(int(v)) * Fraction(scale)) for v in row] for row in e])
+        assert got.dtype == torch.float64 and np.array_equal(got.numpy(), want), n
+        # scale 1 gives the integers back
+        assert torch.equal(O.exact_scaled(e, 1.0, torch.float64), torch.from_numpy(e).double())
+    with pytest.raises(AssertionError):
+        O.exact_scaled(np.array([2 ** 24]), 1.0, torch.float32)
+
+
+def test_every_width_case_keeps_its_sums_exact():
+    """integer inputs in [-8, 8]: every entry of M_n x (and every partial sum: at most 8 n < 2^19) is an integer below 2^24"""
+    import hadamard_cases as HC
+    worst = 0
+    for outer, n, inner, K0 in HC.KERNEL_CASES + [(r, n, 1, K0) for _, r, n, K0 in HC.UNALIGNED]:
+        assert 8 * n < 2 ** 19 and n <= 36864
+        hk = None if K0 == 1 else O.paley(K0)
+        xi = HC.ints((outer, n, inner), HC.seed(outer, n, inner))
+        assert np.abs(xi).max() <= 8
+        e = O.apply_M(xi, hk, axis=1)
+        assert e.dtype == np.int64 and np.abs(e).max() < 2 ** 24, (outer, n, inner, K0)
+        worst = max(worst, int(np.abs(e).max()))
+    print('largest |M_n x| over the cases:', worst)
+    assert len(set(HC.KERNEL_CASES)) == len(HC.KERNEL_CASES)
+
+
+def test_model_reachable_sizes_pick_the_tabulated_order():
+    import hadamard_cases as HC
+    from llmc_amd.compression.quantization.hadamard_utils import get_hadK
+    for n, K in HC.MODEL_REACHABLE:
+        H, k = get_hadK(n)
+        assert k == K and (H is None) == (K == 1), n
+        if K > 1:
+            assert np.array_equal(H.numpy().astype(np.int64), O.paley(K))
+    for out_f, in_f, had_dim, output in HC.LINEAR:
+        if had_dim == -1:
+            assert (out_f if output else in_f, get_hadK(out_f if output else in_f)[1]) in HC.MODEL_REACHABLE
+    # sizes that need a factor matrix the kernel does not take are refused when the rotation is set up, before any launch:
+    # 11008 = 172 * 64 (Llama-2-7B), 5120 = 40 * 128 and 13824 = 108 * 128 (Llama-2-13B), 40 heads (Llama-2-13B)
+    for n, K in HC.REFUSED_SIZES:
+        with pytest.raises(NotImplementedError, match=f'order-{K} '):
+            get_hadK(n)
+
+
+def test_a_partial_rotater_with_40_heads_is_refused_before_any_launch():
+    from llmc_amd.compression.quantization.base_blockwise_quantization import BaseBlockwiseQuantization
+
+    class Stub:
+        intermediate_size, num_heads, hidden_size, fp32_had = 13824, 40, 5120, True
+    for name in ('self_attn.o_proj', 'mlp.down_proj'):
+        with pytest.raises(NotImplementedError):
+            BaseBlockwiseQuantization.get_replacement_params(Stub(), mode='online_rotate', w_only=False, name=name)

@@ -161,13 +161,6 @@ __global__ __launch_bounds__(64) void k_minmax_samples_final(MinmaxSamplesArgs a
 
 using namespace llmc;
 
-#define DISPATCH_DT(dt, CALL)                 \
-    switch (dt) {                             \
-        case LLMC_F16: { using T = f16_t; CALL; break; }   \
-        case LLMC_BF16: { using T = bf16_t; CALL; break; } \
-        default: { using T = float; CALL; break; }         \
-    }
-
 extern "C" size_t llmc_histc_ws_bytes(int bins) { return bins > 0 ? (size_t)bins * sizeof(unsigned) : 0; }
 
 extern "C" int llmc_histc(const void* x, int dt, int64_t n, int bins, float lo, float hi, float* out, void* ws,

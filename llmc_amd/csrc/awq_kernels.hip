@@ -256,21 +256,9 @@ __global__ __launch_bounds__(AB) void k_clamp_groups(T* __restrict__ W, int64_t 
     }
 }
 
-static inline int grid1d(int64_t items) {
-    int64_t b = ceil_div64(items, AB);
-    return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
-}
-
 }  // namespace llmc
 
 using namespace llmc;
-
-#define DISPATCH_DT(dt, CALL)                 \
-    switch (dt) {                             \
-        case LLMC_F16: { using T = f16_t; CALL; break; }   \
-        case LLMC_BF16: { using T = bf16_t; CALL; break; } \
-        default: { using T = float; CALL; break; }         \
-    }
 
 extern "C" size_t llmc_awq_act_mean_ws_bytes(int64_t N, int64_t K) {
     if (N <= 0 || K <= 0) return 0;
@@ -350,7 +338,7 @@ extern "C" int llmc_div_cols(const void* X, const void* s, int dt, int64_t N, in
                      ((uintptr_t)s & 15) == 0, "div_cols: rows must be 16-B aligned");
     hipStream_t st = (hipStream_t)stream;
     const int V = 16 / dtype_size(dt);
-    DISPATCH_DT(dt, hipLaunchKernelGGL((k_cols_op<T, 0>), dim3(grid1d(N * (K / V))), dim3(AB), 0, st, (const T*)X,
+    DISPATCH_DT(dt, hipLaunchKernelGGL((k_cols_op<T, 0>), dim3(capped_grid(N * (K / V), AB, 8192)), dim3(AB), 0, st, (const T*)X,
                                        (const T*)s, N, K, (T*)out));
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;
@@ -376,7 +364,7 @@ extern "C" int llmc_mul_cols(void* W, const void* s, int dt, int64_t R, int64_t 
                  "mul_cols: rows must be 16-B aligned");
     hipStream_t st = (hipStream_t)stream;
     const int V = 16 / dtype_size(dt);
-    DISPATCH_DT(dt, hipLaunchKernelGGL((k_cols_op<T, 1>), dim3(grid1d(R * (K / V))), dim3(AB), 0, st, (const T*)W,
+    DISPATCH_DT(dt, hipLaunchKernelGGL((k_cols_op<T, 1>), dim3(capped_grid(R * (K / V), AB, 8192)), dim3(AB), 0, st, (const T*)W,
                                        (const T*)s, R, K, (T*)W));
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;
@@ -388,7 +376,7 @@ extern "C" int llmc_clamp_groups(void* W, int dt, int64_t R, int64_t K, int64_t 
     if (g <= 0) g = K;
     LLMC_REQUIRE(K % g == 0, "clamp_groups: K must be a multiple of the group size");
     hipStream_t st = (hipStream_t)stream;
-    DISPATCH_DT(dt, hipLaunchKernelGGL((k_clamp_groups<T>), dim3(grid1d(R * K)), dim3(AB), 0, st, (T*)W, R, K, g,
+    DISPATCH_DT(dt, hipLaunchKernelGGL((k_clamp_groups<T>), dim3(capped_grid(R * K, AB, 8192)), dim3(AB), 0, st, (T*)W, R, K, g,
                                        (const T*)min_val, (const T*)max_val));
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;

@@ -90,6 +90,15 @@ template <> struct dt_of<f16_t> { static constexpr int value = LLMC_F16; };
 template <> struct dt_of<bf16_t> { static constexpr int value = LLMC_BF16; };
 template <> struct dt_of<float> { static constexpr int value = LLMC_F32; };
 
+// Host dispatch on a checked dtype code: runs the statement(s) with T = f16_t / bf16_t / float (anything else was rejected by
+// dtype_ok). Variadic so that a template argument list with commas needs no extra parentheses.
+#define DISPATCH_DT(dt, ...)                                              \
+    switch (dt) {                                                         \
+        case LLMC_F16: { using T = ::llmc::f16_t; __VA_ARGS__; break; }   \
+        case LLMC_BF16: { using T = ::llmc::bf16_t; __VA_ARGS__; break; } \
+        default: { using T = float; __VA_ARGS__; break; }                 \
+    }
+
 __device__ __forceinline__ float f16_bits_to_f32(uint16_t u) {
     _Float16 h;
     __builtin_memcpy(&h, &u, 2);
@@ -185,6 +194,11 @@ __device__ __forceinline__ float wave_sum(float v, int width) {
 }
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// 1-D grid of a grid-stride kernel: one block per `per_block` items, at least one, at most `cap`
+static inline int capped_grid(int64_t items, int64_t per_block, int64_t cap) {
+    const int64_t b = ceil_div64(items, per_block);
+    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+}
 static inline int pow2_ceil(int64_t x) {
     int p = 1;
     while (p < x) p <<= 1;

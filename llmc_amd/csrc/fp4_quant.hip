@@ -334,11 +334,6 @@ __global__ __launch_bounds__(XB) void k_fpx_dequant(const uint8_t* __restrict__ 
     }
 }
 
-inline int fpx_grid(int64_t n) {
-    const int64_t b = ceil_div64(n, XB);
-    return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
-}
-
 template <typename T, int KIND>
 int fpx_launch(const FpxArgs& a, void* ws, hipStream_t st) {
     constexpr int V = 16 / sizeof(T);
@@ -349,7 +344,7 @@ int fpx_launch(const FpxArgs& a, void* ws, hipStream_t st) {
         if (L <= 64 && (L & (L - 1)) == 0) {
             int lshift = 0;
             while ((1 << lshift) < L) ++lshift;
-            hipLaunchKernelGGL((k_fpx_seg<T, KIND>), dim3(fpx_grid(a.G * L)), dim3(XB), 0, st, a, (int)L, lshift);
+            hipLaunchKernelGGL((k_fpx_seg<T, KIND>), dim3(capped_grid(a.G * L, XB, 8192)), dim3(XB), 0, st, a, (int)L, lshift);
         } else {
             const int lds = (int)(a.g * sizeof(T));
             if (int rc = ensure_dynamic_lds((const void*)k_fpx_row<T, KIND>, (int)(FPX_RESIDENT * sizeof(T)))) return rc;
@@ -374,7 +369,7 @@ int fpx_launch(const FpxArgs& a, void* ws, hipStream_t st) {
         if (int rc = llmc_minmax_qparams(a.W, dt_of<T>::value, a.G, a.g, /*sym*/ 1, 1, -1.0f, 1.0f, ws, nullptr, ws2, (llmc_stream_t)st)) return rc;
         b.amax = ws;
     }
-    hipLaunchKernelGGL((k_fpx_flat<T, KIND>), dim3(fpx_grid(a.G * a.g / (vec ? V : 1) + 1)), dim3(XB), 0, st, b, (int)vec);
+    hipLaunchKernelGGL((k_fpx_flat<T, KIND>), dim3(capped_grid(a.G * a.g / (vec ? V : 1) + 1, XB, 8192)), dim3(XB), 0, st, b, (int)vec);
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;
 }
@@ -420,16 +415,12 @@ extern "C" int llmc_fpx_quant(const void* W, int dt, int64_t G, int64_t g, const
     a.sdt = (mode & FPX_E8M0) ? LLMC_F32 : sdt, a.static_scales = static_scales, a.mode = mode;
     const int kind = 2 * (fmt - 2) + ((mode & FPX_OCP) ? 1 : 0);
     hipStream_t st = (hipStream_t)stream;
-    switch (dt) {
-        case LLMC_F16: return fpx_launch_kind<f16_t>(kind, a, ws, st);
-        case LLMC_BF16: return fpx_launch_kind<bf16_t>(kind, a, ws, st);
-        default: return fpx_launch_kind<float>(kind, a, ws, st);
-    }
+    DISPATCH_DT(dt, return fpx_launch_kind<T>(kind, a, ws, st));
 }
 
 extern "C" int llmc_fp4_pack(const void* codes, int64_t R, int64_t K, void* packed, llmc_stream_t stream) {
     LLMC_REQUIRE(codes && packed && R > 0 && K > 0 && K % 2 == 0, "fp4_pack: needs codes [R, K] with K even");
-    hipLaunchKernelGGL(k_fp4_pack, dim3(fpx_grid(R * K / 2)), dim3(XB), 0, (hipStream_t)stream, (const uint8_t*)codes, R * K / 2,
+    hipLaunchKernelGGL(k_fp4_pack, dim3(capped_grid(R * K / 2, XB, 8192)), dim3(XB), 0, (hipStream_t)stream, (const uint8_t*)codes, R * K / 2,
                        (uint8_t*)packed);
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;
@@ -446,19 +437,8 @@ extern "C" int llmc_fpx_dequant(const void* codes, int fmt, int packed, const vo
     LLMC_REQUIRE(!packed || (G * g) % 2 == 0, "fpx_dequant: packed codes need an even element count");
     hipStream_t st = (hipStream_t)stream;
     const int64_t total = G * g;
-    switch (odt) {
-        case LLMC_F16:
-            hipLaunchKernelGGL((k_fpx_dequant<f16_t>), dim3(fpx_grid(total)), dim3(XB), 0, st, (const uint8_t*)codes, packed, fmt, scales,
-                               sdt, total, g, (f16_t*)out);
-            break;
-        case LLMC_BF16:
-            hipLaunchKernelGGL((k_fpx_dequant<bf16_t>), dim3(fpx_grid(total)), dim3(XB), 0, st, (const uint8_t*)codes, packed, fmt,
-                               scales, sdt, total, g, (bf16_t*)out);
-            break;
-        default:
-            hipLaunchKernelGGL((k_fpx_dequant<float>), dim3(fpx_grid(total)), dim3(XB), 0, st, (const uint8_t*)codes, packed, fmt, scales,
-                               sdt, total, g, (float*)out);
-    }
+    DISPATCH_DT(odt, hipLaunchKernelGGL((k_fpx_dequant<T>), dim3(capped_grid(total, XB, 8192)), dim3(XB), 0, st, (const uint8_t*)codes,
+                                        packed, fmt, scales, sdt, total, g, (T*)out));
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;
 }

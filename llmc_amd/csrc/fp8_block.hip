@@ -799,11 +799,7 @@ extern "C" int llmc_fp8_block_quant(const void* W, int dt, int64_t M, int64_t N,
     LLMC_REQUIRE(block >= 16 && block <= 128, "fp8_block_quant: block size must be in [16, 128]");
     hipStream_t st = (hipStream_t)stream;
     const int z1 = clamp_min > 0.0f ? 1 : 0;   // FloatQuantizer semantics replace a zero scale, kernel.py's do not
-    switch (dt) {
-        case LLMC_F16: launch_block_quant<f16_t>(W, M, N, block, clamp_min, z1, fake, out, scales, st); break;
-        case LLMC_BF16: launch_block_quant<bf16_t>(W, M, N, block, clamp_min, z1, fake, out, scales, st); break;
-        default: launch_block_quant<float>(W, M, N, block, clamp_min, z1, fake, out, scales, st); break;
-    }
+    DISPATCH_DT(dt, launch_block_quant<T>(W, M, N, block, clamp_min, z1, fake, out, scales, st));
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;
 }
@@ -823,11 +819,7 @@ extern "C" int llmc_fp8_block_dequant(const void* W8, const float* scales, int64
     LLMC_REQUIRE(W8 && out && scales && M > 0 && N > 0, "fp8_block_dequant: null/empty argument");
     LLMC_REQUIRE(dtype_ok(out_dt) && block >= 1, "fp8_block_dequant: bad dtype / block");
     hipStream_t st = (hipStream_t)stream;
-    switch (out_dt) {
-        case LLMC_F16: launch_block_dequant<f16_t>(W8, scales, M, N, block, out, st); break;
-        case LLMC_BF16: launch_block_dequant<bf16_t>(W8, scales, M, N, block, out, st); break;
-        default: launch_block_dequant<float>(W8, scales, M, N, block, out, st); break;
-    }
+    DISPATCH_DT(out_dt, launch_block_dequant<T>(W8, scales, M, N, block, out, st));
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;
 }
@@ -850,11 +842,7 @@ extern "C" int llmc_fp8_act_quant(const void* X, int dt, int64_t n_elem, int blo
     LLMC_REQUIRE(dtype_ok(dt), "fp8_act_quant: bad dtype");
     LLMC_REQUIRE(block >= 8 && block <= 128 && n_elem % block == 0, "fp8_act_quant: last dim must be a multiple of block <= 128");
     hipStream_t st = (hipStream_t)stream;
-    switch (dt) {
-        case LLMC_F16: launch_act_quant<f16_t>(X, n_elem, block, out8, scales, st); break;
-        case LLMC_BF16: launch_act_quant<bf16_t>(X, n_elem, block, out8, scales, st); break;
-        default: launch_act_quant<float>(X, n_elem, block, out8, scales, st); break;
-    }
+    DISPATCH_DT(dt, launch_act_quant<T>(X, n_elem, block, out8, scales, st));
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;
 }

@@ -396,16 +396,6 @@ __global__ __launch_bounds__(FB) void k_pack_awq_z(const void* __restrict__ scal
     }
 }
 
-static inline int grid_fb(int64_t n) {
-    int64_t b = ceil_div64(n, FB);
-    return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
-}
-
-static inline int grid_cast(int64_t n) {
-    int64_t b = ceil_div64(n, FB);
-    return (int)(b > FP8_GRID_CAP ? FP8_GRID_CAP : (b < 1 ? 1 : b));
-}
-
 }  // namespace llmc
 
 using namespace llmc;
@@ -433,19 +423,10 @@ extern "C" int llmc_fp8_quant(const void* W, int dt, int64_t G, int64_t g, int f
     if (opt(OPT_FP8_EXACT_DIV)) fake |= FP8_EXACT_DIV;      // A/B switch, same results (include/llmc_hip.h)
     if (opt(OPT_FP8_NO_PACKED16)) fake |= FP8_NO_PACKED16;
     hipStream_t st = (hipStream_t)stream;
-    switch (dt) {
-        case LLMC_F16:
-            hipLaunchKernelGGL((k_fp8_cast<f16_t>), dim3(grid_cast(G * g / (8 * FP8_U) + 1)), dim3(FB), 0, st, (const f16_t*)W,
-                               (const f16_t*)amax, sdt, scales, static_scales, G, g, fake, out);
-            break;
-        case LLMC_BF16:
-            hipLaunchKernelGGL((k_fp8_cast<bf16_t>), dim3(grid_cast(G * g / (8 * FP8_U) + 1)), dim3(FB), 0, st, (const bf16_t*)W,
-                               (const bf16_t*)amax, sdt, scales, static_scales, G, g, fake, out);
-            break;
-        default:
-            hipLaunchKernelGGL((k_fp8_cast<float>), dim3(grid_cast(G * g / (4 * FP8_U) + 1)), dim3(FB), 0, st, (const float*)W,
-                               (const float*)amax, sdt, scales, static_scales, G, g, fake, out);
-    }
+    const int V = 16 / dtype_size(dt);
+    const int grid = capped_grid(G * g / (V * FP8_U) + 1, FB, FP8_GRID_CAP);
+    DISPATCH_DT(dt, hipLaunchKernelGGL((k_fp8_cast<T>), dim3(grid), dim3(FB), 0, st, (const T*)W, (const T*)amax, sdt, scales,
+                                       static_scales, G, g, fake, out));
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;
 }
@@ -458,22 +439,11 @@ extern "C" int llmc_pack_awq_gemm(const void* weight, int wdt, const void* scale
                  "pack_awq_gemm: null/empty argument (AutoAWQ needs asymmetric zeros)");
     LLMC_REQUIRE(R % 8 == 0 && K % g == 0, "pack_awq_gemm: R must be a multiple of 8 and K of the group size");
     hipStream_t st = (hipStream_t)stream;
-    const int grid = grid_fb(K * (R / 8));
-    switch (wdt) {
-        case LLMC_F16:
-            hipLaunchKernelGGL((k_pack_awq_w<f16_t>), dim3(grid), dim3(FB), 0, st, (const f16_t*)weight, scales, sdt,
-                               zeros, R, K, g, qweight);
-            break;
-        case LLMC_BF16:
-            hipLaunchKernelGGL((k_pack_awq_w<bf16_t>), dim3(grid), dim3(FB), 0, st, (const bf16_t*)weight, scales, sdt,
-                               zeros, R, K, g, qweight);
-            break;
-        default:
-            hipLaunchKernelGGL((k_pack_awq_w<float>), dim3(grid), dim3(FB), 0, st, (const float*)weight, scales, sdt,
-                               zeros, R, K, g, qweight);
-    }
+    const int grid = capped_grid(K * (R / 8), FB, 8192);
+    DISPATCH_DT(wdt, hipLaunchKernelGGL((k_pack_awq_w<T>), dim3(grid), dim3(FB), 0, st, (const T*)weight, scales, sdt, zeros, R,
+                                        K, g, qweight));
     LLMC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_pack_awq_z, dim3(grid_fb((K / g) * R)), dim3(FB), 0, st, scales, sdt, zeros, R, K / g, qzeros,
+    hipLaunchKernelGGL(k_pack_awq_z, dim3(capped_grid((K / g) * R, FB, 8192)), dim3(FB), 0, st, scales, sdt, zeros, R, K / g, qzeros,
                        (uint16_t*)scales_out_f16);
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;

@@ -497,9 +497,5 @@ extern "C" int llmc_hqq_optimize(const void* W, int dt, int64_t R, int64_t K, in
     a.kc = L.kc;
     a.iters = iters;
     hipStream_t st = (hipStream_t)stream;
-    switch (dt) {
-        case LLMC_F16: return hqq_by_lp<f16_t>(a, lp_norm_one, group_size, iters, errs, scales, zeros, t_out, st);
-        case LLMC_BF16: return hqq_by_lp<bf16_t>(a, lp_norm_one, group_size, iters, errs, scales, zeros, t_out, st);
-        default: return hqq_by_lp<float>(a, lp_norm_one, group_size, iters, errs, scales, zeros, t_out, st);
-    }
+    DISPATCH_DT(dt, return hqq_by_lp<T>(a, lp_norm_one, group_size, iters, errs, scales, zeros, t_out, st));
 }

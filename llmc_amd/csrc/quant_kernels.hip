@@ -3,6 +3,8 @@
 // Layout: W is a contiguous [G, g] view (one quantization group per row). A wave64 is cut into
 // 64/LPR sub-groups of LPR lanes, one row per sub-group, 16 B per lane per load (coalesced: a sub-group
 // reads LPR*16 contiguous bytes). Rows are distributed over a grid-stride of waves.
+// Row kernels: quant_rows behind k_quant_rows* (any g; qparams only, fake values or codes, optionally a column multiplier) and
+// k_quant_dynamic_small (g = LPR * 16 B exactly); launch_quant_rows is the one place that chooses between them.
 #include "common.h"
 #include "quant_math.h"
 
@@ -39,25 +41,100 @@ __device__ __forceinline__ void store_vec(T* p, const RowVec<T, VEC>& r) {
     }
 }
 
-template <int KIND> struct code_t;
-template <> struct code_t<LLMC_OUT_I32> { using type = int32_t; };
-template <> struct code_t<LLMC_OUT_I8> { using type = int8_t; };
-template <> struct code_t<LLMC_OUT_U8> { using type = uint8_t; };
+// what a kernel of output kind KIND writes per element: fake values in the tensor dtype, or codes in KIND's container
+template <int KIND, typename T> struct out_elem;
+template <typename T> struct out_elem<LLMC_OUT_FAKE, T> { using type = T; };
+template <typename T> struct out_elem<LLMC_OUT_I32, T> { using type = int32_t; };
+template <typename T> struct out_elem<LLMC_OUT_I8, T> { using type = int8_t; };
+template <typename T> struct out_elem<LLMC_OUT_U8, T> { using type = uint8_t; };
+
+// One vector of a group through quant (and dequant for LLMC_OUT_FAKE): fake values of T or codes in KIND's container.
+// dv divides by the scale; s, z, p2 are dequant's. FZ is k_quant_static's variant: where its run-time fz is set, dv is the
+// divisor of the clamped scale and the zero point is added before the rounding (quant_code_fz).
+template <int KIND, bool FZ = false, typename T, int VEC>
+__device__ __forceinline__ void quant_vec(RowVec<typename out_elem<KIND, T>::type, VEC>& o, const RowVec<T, VEC>& v,
+                                          const Divisor& dv, float s, float z, int p1, int p2, float qmin, float qmax,
+                                          bool fz = false) {
+    using O = typename out_elem<KIND, T>::type;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+        float q;
+        if constexpr (FZ)
+            q = fz ? quant_code_fz(to_f32<T>(v.v[k]), dv, z, p1, p2, qmin, qmax)
+                   : quant_code(to_f32<T>(v.v[k]), dv, z, p1, p2, qmin, qmax);
+        else
+            q = quant_code(to_f32<T>(v.v[k]), dv, z, p1, p2, qmin, qmax);
+        if constexpr (KIND == LLMC_OUT_FAKE) o.v[k] = from_f32<T>(dequant_code(q, s, z, p2));
+        else o.v[k] = (O)q;
+    }
+}
+// k_quant_static / quant_rows: fake values as store_vec writes them. Codes are written element by element in source, because
+// the hosts' vec_ok asks for a 16-B aligned `out` only where fake values go; the compiler is free to merge neighbouring element
+// stores of the vector into wider ones that need the element's alignment only (gfx950 global stores are unaligned-capable), and
+// it does: that is intended, k_quant_static has always been compiled this way.
+template <int KIND, typename O, int VEC>
+__device__ __forceinline__ void store_out(void* out, int64_t i, const RowVec<O, VEC>& o) {
+    O* op = (O*)out + i;
+    if constexpr (KIND == LLMC_OUT_FAKE) {
+        store_vec<O, VEC>(op, o);
+    } else {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) op[k] = o.v[k];
+    }
+}
+// k_quant_dynamic_small (its launch condition guarantees a 16-B aligned `out`): 32 / 16 / 8-byte stores
+template <typename O, int VEC>
+__device__ __forceinline__ void store_vec_aligned(O* op, const RowVec<O, VEC>& o) {
+    if constexpr (sizeof(O) * VEC == 32) {
+        uint4 lo, hi;
+        __builtin_memcpy(&lo, &o.v[0], 16);
+        __builtin_memcpy(&hi, &o.v[VEC / 2], 16);
+        reinterpret_cast<uint4*>(op)[0] = lo;
+        reinterpret_cast<uint4*>(op)[1] = hi;
+    } else if constexpr (sizeof(O) * VEC == 16) {
+        uint4 lo;
+        __builtin_memcpy(&lo, &o.v[0], 16);
+        reinterpret_cast<uint4*>(op)[0] = lo;
+    } else if constexpr (sizeof(O) * VEC == 8) {
+        uint2 lo;
+        __builtin_memcpy(&lo, &o.v[0], 8);
+        reinterpret_cast<uint2*>(op)[0] = lo;
+    } else {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) op[k] = o.v[k];
+    }
+}
 
 // --------------------------------------------------------------------------------------------
 // row scan: min/max of one row by LPR lanes
 // --------------------------------------------------------------------------------------------
-template <typename T, int VEC>
-__device__ __forceinline__ void row_minmax(const T* row, int g, int sl, int lpr, float& mn, float& mx,
-                                           RowVec<T, VEC>& first, bool& have_first) {
+// one vector of the row at column c; SCALE: times the column multiplier, w' = rnd(w * cs[col]) in the tensor dtype (from_f32
+// is that one rounding)
+template <typename T, int VEC, bool SCALE>
+__device__ __forceinline__ RowVec<T, VEC> load_row_vec(const T* row, const T* cs, int c) {
+    RowVec<T, VEC> v = load_vec<T, VEC>(row + c);
+    if constexpr (SCALE) {
+        const RowVec<T, VEC> sv = load_vec<T, VEC>(cs + c);
+#pragma unroll
+        for (int i = 0; i < VEC; ++i)
+            v.v[i] = from_f32<T>(to_f32<T>(v.v[i]) * to_f32<T>(sv.v[i]));
+    }
+    return v;
+}
+// KEEP_FIRST: `first` receives this lane's first vector, if the lane owns one (sl * VEC < g)
+template <typename T, int VEC, bool SCALE, bool KEEP_FIRST>
+__device__ __forceinline__ void row_minmax(const T* row, const T* cs, int g, int sl, int lpr, float& mn, float& mx,
+                                           RowVec<T, VEC>& first) {
     mn = INFINITY;
     mx = -INFINITY;
-    have_first = false;
+    bool have_first = false;
     for (int c = sl * VEC; c < g; c += lpr * VEC) {
-        RowVec<T, VEC> v = load_vec<T, VEC>(row + c);
-        if (!have_first) {
-            first = v;
-            have_first = true;
+        RowVec<T, VEC> v = load_row_vec<T, VEC, SCALE>(row, cs, c);
+        if constexpr (KEEP_FIRST) {
+            if (!have_first) {
+                first = v;
+                have_first = true;
+            }
         }
 #pragma unroll
         for (int i = 0; i < VEC; ++i) {
@@ -70,12 +147,19 @@ __device__ __forceinline__ void row_minmax(const T* row, int g, int sl, int lpr,
     mx = wave_max(mx, lpr);
 }
 
-// K5: [G, g] -> scales/zeros [G] (tensor dtype)
-template <typename T, int VEC>
-__global__ __launch_bounds__(kBlock) void k_minmax_qparams(const T* __restrict__ W, int64_t G, int g,
-                                                           int lpr, int sym, int round_zp, float qmin,
-                                                           float qmax, T* __restrict__ scales,
-                                                           T* __restrict__ zeros) {
+// K5 / K5+K6 fused / AWQ's scale + fake-quant, for rows of any length: one body.
+//   pass 1  min/max of the row (second row pass hits L1/L2; the first 16 B per lane stay in registers, which covers
+//           g <= LPR*VEC, i.e. every per_group case), then scales / zeros [G] in the tensor dtype where asked for
+//   pass 2  quantize and store: fake values or codes of KIND. KIND = OUT_NONE (file-local, not an LLMC_OUT_* of the ABI)
+//           compiles pass 2 out: llmc_minmax_qparams' instantiation carries no quantizer code.
+//   SCALE   fake_quantize_weight of AWQ's search (awq.py:147-164): every load is w' = rnd(w * cs[col]) (the in-place mul_ in
+//           the model dtype); cs is [gpr, g], one row of K multipliers cut like the weight rows (gpr groups per row).
+// A sub-group past the last row computes on row G - 1 (its lanes take part in the wave's shuffles) and stores nothing.
+static constexpr int OUT_NONE = -1;
+template <typename T, int VEC, int KIND, bool SCALE>
+__device__ __forceinline__ void quant_rows(const T* __restrict__ W, const T* __restrict__ cs, int64_t G, int g, int gpr,
+                                           int lpr, int sym, int round_zp, float qmin, float qmax, void* __restrict__ out,
+                                           T* __restrict__ scales, T* __restrict__ zeros) {
     constexpr int DT = dt_of<T>::value;
     const int lane = threadIdx.x & 63;
     const int rpw = 64 / lpr;
@@ -83,19 +167,58 @@ __global__ __launch_bounds__(kBlock) void k_minmax_qparams(const T* __restrict__
     const int64_t wave = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
     const int64_t nwaves = (int64_t)gridDim.x * (kBlock / 64);
     for (int64_t r0 = wave * rpw; r0 < G; r0 += nwaves * rpw) {
-        int64_t row = r0 + sub;
-        bool valid = row < G;
-        int64_t rr = valid ? row : G - 1;
+        const int64_t row = r0 + sub;
+        const bool valid = row < G;
+        const int64_t rr = valid ? row : G - 1;
+        const T* rp = W + rr * g;
+        const T* cp = SCALE ? cs + (rr % gpr) * g : nullptr;
         float mn, mx;
         RowVec<T, VEC> first;
-        bool hf;
-        row_minmax<T, VEC>(W + rr * g, g, sl, lpr, mn, mx, first, hf);
-        if (valid && sl == 0) {
-            QParams q = qparams_from_minmax(mn, mx, DT, sym, round_zp, qmin, qmax);
-            scales[row] = from_f32<T>(q.s);
-            if (zeros) zeros[row] = from_f32<T>(q.z);
+        row_minmax<T, VEC, SCALE, KIND != OUT_NONE>(rp, cp, g, sl, lpr, mn, mx, first);
+        const bool lead = valid && sl == 0;         // the lane that stores the row's qparams
+        if (KIND == OUT_NONE && !lead) continue;    // qparams only: no other lane needs them
+        const QParams q = qparams_from_minmax(mn, mx, DT, sym, SCALE ? 1 : round_zp, qmin, qmax);
+        if constexpr (!SCALE) {                     // SCALE serves llmc_awq_scale_fakequant: no qparams out, round_zp = 1
+            if (lead) {
+                if (KIND == OUT_NONE || scales) scales[row] = from_f32<T>(q.s);     // llmc_minmax_qparams requires scales
+                if (zeros) zeros[row] = from_f32<T>(q.z);
+            }
+        }
+        if constexpr (KIND != OUT_NONE) {
+            if (!valid) continue;
+            const Divisor dv = make_divisor(q.s, fmaxf(fabsf(mn), fabsf(mx)));
+            bool use_first = true;
+            for (int c = sl * VEC; c < g; c += lpr * VEC) {
+                const RowVec<T, VEC> v = use_first ? first : load_row_vec<T, VEC, SCALE>(rp, cp, c);
+                use_first = false;
+                RowVec<typename out_elem<KIND, T>::type, VEC> o;
+                quant_vec<KIND>(o, v, dv, q.s, q.z, DT, DT, qmin, qmax);
+                store_out<KIND>(out, rr * g + c, o);
+            }
         }
     }
+}
+
+// The kernels of quant_rows: one entry point per argument list, nothing else. An instantiation that carried the arguments of
+// the other two measured slower than the kernel it replaced (qparams only: 18.48 -> 18.74 us at 4096 x 14336 bf16) with the
+// same instructions; with its own argument list it does not (profiles/quant_rows_refactor.txt).
+template <typename T, int VEC>
+__global__ __launch_bounds__(kBlock) void k_quant_rows_qparams(const T* __restrict__ W, int64_t G, int g, int lpr, int sym,
+                                                               int round_zp, float qmin, float qmax,
+                                                               T* __restrict__ scales, T* __restrict__ zeros) {
+    quant_rows<T, VEC, OUT_NONE, false>(W, nullptr, G, g, 1, lpr, sym, round_zp, qmin, qmax, nullptr, scales, zeros);
+}
+template <typename T, int VEC, int KIND>
+__global__ __launch_bounds__(kBlock) void k_quant_rows(const T* __restrict__ W, int64_t G, int g, int lpr, int sym,
+                                                       int round_zp, float qmin, float qmax, void* __restrict__ out,
+                                                       T* __restrict__ scales, T* __restrict__ zeros) {
+    quant_rows<T, VEC, KIND, false>(W, nullptr, G, g, 1, lpr, sym, round_zp, qmin, qmax, out, scales, zeros);
+}
+template <typename T, int VEC>
+__global__ __launch_bounds__(kBlock) void k_quant_rows_scaled(const T* __restrict__ W, const T* __restrict__ cs, int64_t G,
+                                                              int g, int gpr, int lpr, int sym, float qmin, float qmax,
+                                                              T* __restrict__ out) {
+    quant_rows<T, VEC, LLMC_OUT_FAKE, true>(W, cs, G, g, gpr, lpr, sym, 1, qmin, qmax, out, nullptr, nullptr);
 }
 
 // two-stage variant for few, very long rows (per_tensor / huge per_channel)
@@ -193,78 +316,9 @@ __global__ __launch_bounds__(kBlock) void k_quant_static(const T* __restrict__ W
         // LLMC_FRACTIONAL_ZP (round_zp=False, quant.py:702-707): the divisor is s.clamp_min(1e-9) in the scale's dtype
         const float sdiv = fz ? fmaxf(s, rnd(1e-9f, sd)) : s;
         const Divisor dv = make_divisor(sdiv, am);
-        if constexpr (KIND == LLMC_OUT_FAKE) {
-            RowVec<T, VEC> o;
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) {
-                float q = fz ? quant_code_fz(to_f32<T>(v.v[k]), dv, z, p1, p2, qmin, qmax)
-                             : quant_code(to_f32<T>(v.v[k]), dv, z, p1, p2, qmin, qmax);
-                o.v[k] = from_f32<T>(dequant_code(q, s, z, p2));
-            }
-            store_vec<T, VEC>((T*)out + row * g + c, o);
-        } else {
-            using C = typename code_t<KIND>::type;
-            RowVec<C, VEC> o;
-#pragma unroll
-            for (int k = 0; k < VEC; ++k)
-                o.v[k] = (C)(fz ? quant_code_fz(to_f32<T>(v.v[k]), dv, z, p1, p2, qmin, qmax)
-                                : quant_code(to_f32<T>(v.v[k]), dv, z, p1, p2, qmin, qmax));
-            C* op = (C*)out + row * g + c;
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) op[k] = o.v[k];
-        }
-    }
-}
-
-// K5+K6 fused dynamic: one pass over W from HBM (second row pass hits L1/L2; the first 16 B per lane
-// stay in registers, which covers g <= LPR*VEC, i.e. every per_group case).
-template <typename T, int VEC, int KIND>
-__global__ __launch_bounds__(kBlock) void k_quant_dynamic(const T* __restrict__ W, int64_t G, int g,
-                                                          int lpr, int sym, int round_zp, float qmin,
-                                                          float qmax, void* __restrict__ out,
-                                                          T* __restrict__ scales, T* __restrict__ zeros) {
-    constexpr int DT = dt_of<T>::value;
-    const int lane = threadIdx.x & 63;
-    const int rpw = 64 / lpr;
-    const int sub = lane / lpr, sl = lane % lpr;
-    const int64_t wave = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-    const int64_t nwaves = (int64_t)gridDim.x * (kBlock / 64);
-    for (int64_t r0 = wave * rpw; r0 < G; r0 += nwaves * rpw) {
-        int64_t row = r0 + sub;
-        bool valid = row < G;
-        int64_t rr = valid ? row : G - 1;
-        const T* rp = W + rr * g;
-        float mn, mx;
-        RowVec<T, VEC> first;
-        bool hf;
-        row_minmax<T, VEC>(rp, g, sl, lpr, mn, mx, first, hf);
-        QParams q = qparams_from_minmax(mn, mx, DT, sym, round_zp, qmin, qmax);
-        if (valid && sl == 0) {
-            if (scales) scales[row] = from_f32<T>(q.s);
-            if (zeros) zeros[row] = from_f32<T>(q.z);
-        }
-        if (!valid) continue;
-        const Divisor dv = make_divisor(q.s, fmaxf(fabsf(mn), fabsf(mx)));
-        bool use_first = true;
-        for (int c = sl * VEC; c < g; c += lpr * VEC) {
-            RowVec<T, VEC> v = use_first ? first : load_vec<T, VEC>(rp + c);
-            use_first = false;
-            if constexpr (KIND == LLMC_OUT_FAKE) {
-                RowVec<T, VEC> o;
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) {
-                    float qq = quant_code(to_f32<T>(v.v[k]), dv, q.z, DT, DT, qmin, qmax);
-                    o.v[k] = from_f32<T>(dequant_code(qq, q.s, q.z, DT));
-                }
-                store_vec<T, VEC>((T*)out + rr * g + c, o);
-            } else {
-                using C = typename code_t<KIND>::type;
-                C* op = (C*)out + rr * g + c;
-#pragma unroll
-                for (int k = 0; k < VEC; ++k)
-                    op[k] = (C)quant_code(to_f32<T>(v.v[k]), dv, q.z, DT, DT, qmin, qmax);
-            }
-        }
+        RowVec<typename out_elem<KIND, T>::type, VEC> o;
+        quant_vec<KIND, true>(o, v, dv, s, z, p1, p2, qmin, qmax, fz);
+        store_out<KIND>(out, row * g + c, o);
     }
 }
 
@@ -322,40 +376,10 @@ __global__ __launch_bounds__(kBlock) void k_quant_dynamic_small(const T* __restr
             }
             if (!valid[u] || out == nullptr) continue;
             const Divisor dv = make_divisor(q.s, fmaxf(fabsf(mn), fabsf(mx)));
-            if constexpr (KIND == LLMC_OUT_FAKE) {
-                RowVec<T, VEC> o;
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) {
-                    const float qq = quant_code(to_f32<T>(v[u].v[k]), dv, q.z, DT, DT, qmin, qmax);
-                    o.v[k] = from_f32<T>(dequant_code(qq, q.s, q.z, DT));
-                }
-                store_vec<T, VEC>((T*)out + rows[u] * g + sl * VEC, o);
-            } else {
-                using C = typename code_t<KIND>::type;
-                RowVec<C, VEC> o;
-#pragma unroll
-                for (int k = 0; k < VEC; ++k)
-                    o.v[k] = (C)quant_code(to_f32<T>(v[u].v[k]), dv, q.z, DT, DT, qmin, qmax);
-                C* op = (C*)out + rows[u] * g + sl * VEC;
-                if constexpr (sizeof(C) * VEC == 32) {
-                    uint4 lo, hi;
-                    __builtin_memcpy(&lo, &o.v[0], 16);
-                    __builtin_memcpy(&hi, &o.v[VEC / 2], 16);
-                    reinterpret_cast<uint4*>(op)[0] = lo;
-                    reinterpret_cast<uint4*>(op)[1] = hi;
-                } else if constexpr (sizeof(C) * VEC == 16) {
-                    uint4 lo;
-                    __builtin_memcpy(&lo, &o.v[0], 16);
-                    reinterpret_cast<uint4*>(op)[0] = lo;
-                } else if constexpr (sizeof(C) * VEC == 8) {
-                    uint2 lo;
-                    __builtin_memcpy(&lo, &o.v[0], 8);
-                    reinterpret_cast<uint2*>(op)[0] = lo;
-                } else {
-#pragma unroll
-                    for (int k = 0; k < VEC; ++k) op[k] = o.v[k];
-                }
-            }
+            using O = typename out_elem<KIND, T>::type;
+            RowVec<O, VEC> o;
+            quant_vec<KIND>(o, v[u], dv, q.s, q.z, DT, DT, qmin, qmax);
+            store_vec_aligned<O, VEC>((O*)out + rows[u] * g + sl * VEC, o);
         }
     }
 }
@@ -399,12 +423,6 @@ __global__ __launch_bounds__(kBlock) void k_pack_lsb(const C* __restrict__ codes
     }
 }
 
-static inline int grid_for(int64_t work_items, int per_block) {
-    int64_t b = ceil_div64(work_items, per_block);
-    if (b < 1) b = 1;
-    return (int)(b > kMaxGrid ? kMaxGrid : b);
-}
-
 static inline int choose_lpr(int64_t g, int vec) {
     int lpr = pow2_ceil(ceil_div64(g, vec));
     if (lpr > 64) lpr = 64;
@@ -413,6 +431,46 @@ static inline int choose_lpr(int64_t g, int vec) {
 }
 
 static inline bool use_two_stage(int64_t G, int64_t g) { return g >= 4 * kChunk && G < 4096; }
+
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// The launch ladder of the row kernels for a contiguous [G, g] view with g < 2^31: small -> 16-byte vectors -> scalar.
+//   vector  rows of whole 16-B vectors; W, the multipliers cs (SCALE) and, for fake values, `out` 16-B aligned. Codes are
+//           stored element by element, so their `out` may lie anywhere; OUT_NONE has no `out`.
+//   small   vector, g = lpr * 16 B with lpr a power of two <= 64, and `out` 16-B aligned for codes too (k_quant_dynamic_small
+//           stores them 8 - 32 bytes at a time). It has no qparams-only instantiation: a null `out` says so at run time.
+template <typename T, int KIND, bool SCALE>
+static int launch_quant_rows(const void* W, const void* cs, int64_t G, int64_t g, int gpr, int sym, int round_zp, float qmin,
+                             float qmax, void* out, void* scales, void* zeros, hipStream_t st) {
+    constexpr int V16 = 16 / sizeof(T);
+    const bool vec_ok = g % V16 == 0 && aligned16(W) && (!SCALE || aligned16(cs)) &&
+                        (KIND != LLMC_OUT_FAKE || aligned16(out));
+    if (vec_ok && small_ok(g, V16) && aligned16(out)) {
+        constexpr int SK = KIND == OUT_NONE ? LLMC_OUT_FAKE : KIND;
+        const int lpr = (int)(g / V16);
+        const int grid = capped_grid(ceil_div64(G, (64 / lpr) * UNR), kBlock / 64, kMaxGrid);
+        hipLaunchKernelGGL((k_quant_dynamic_small<T, V16, SK, SCALE>), dim3(grid), dim3(kBlock), 0, st, (const T*)W,
+                           (const T*)cs, G, (int)g, gpr, lpr, sym, round_zp, qmin, qmax, out, (T*)scales, (T*)zeros);
+    } else {
+        const int lpr = choose_lpr(g, vec_ok ? V16 : 1);
+        const int grid = capped_grid(ceil_div64(G, 64 / lpr), kBlock / 64, kMaxGrid);
+        if constexpr (KIND == OUT_NONE) {
+            const auto kernel = vec_ok ? k_quant_rows_qparams<T, V16> : k_quant_rows_qparams<T, 1>;
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, st, (const T*)W, G, (int)g, lpr, sym, round_zp, qmin, qmax,
+                               (T*)scales, (T*)zeros);
+        } else if constexpr (SCALE) {
+            const auto kernel = vec_ok ? k_quant_rows_scaled<T, V16> : k_quant_rows_scaled<T, 1>;
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, st, (const T*)W, (const T*)cs, G, (int)g, gpr, lpr, sym, qmin,
+                               qmax, (T*)out);
+        } else {
+            const auto kernel = vec_ok ? k_quant_rows<T, V16, KIND> : k_quant_rows<T, 1, KIND>;
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, st, (const T*)W, G, (int)g, lpr, sym, round_zp, qmin, qmax, out,
+                               (T*)scales, (T*)zeros);
+        }
+    }
+    LLMC_LAUNCH_CHECK();
+    return LLMC_OK;
+}
 
 }  // namespace llmc
 
@@ -424,48 +482,23 @@ extern "C" size_t llmc_minmax_qparams_ws_bytes(int64_t G, int64_t g) {
     return (size_t)(G * ceil_div64(g, kChunk)) * sizeof(float2);
 }
 
+// few, very long rows: per-chunk partial min/max into the workspace, then one block per row
 template <typename T>
-static int minmax_qparams_t(const void* W, int64_t G, int64_t g, int sym, int round_zp, float qmin,
-                            float qmax, void* scales, void* zeros, void* ws, hipStream_t st) {
+static int minmax_two_stage_t(const void* W, int64_t G, int64_t g, int sym, int round_zp, float qmin, float qmax,
+                              void* scales, void* zeros, void* ws, hipStream_t st) {
     constexpr int V16 = 16 / sizeof(T);
-    bool vec_ok = (g % V16 == 0) && (((uintptr_t)W & 15) == 0);
-    if (use_two_stage(G, g)) {
-        LLMC_REQUIRE(ws != nullptr, "minmax_qparams: workspace required for long rows");
-        int64_t nch = ceil_div64(g, kChunk);
-        int grid = grid_for(G * nch, 1);
-        if (vec_ok)
-            hipLaunchKernelGGL((k_minmax_partial<T, V16>), dim3(grid), dim3(kBlock), 0, st, (const T*)W, G, g,
-                               nch, (float2*)ws);
-        else
-            hipLaunchKernelGGL((k_minmax_partial<T, 1>), dim3(grid), dim3(kBlock), 0, st, (const T*)W, G, g,
-                               nch, (float2*)ws);
-        LLMC_LAUNCH_CHECK();
-        hipLaunchKernelGGL((k_minmax_final<T>), dim3((unsigned)G), dim3(1024), 0, st, (const float2*)ws, G, nch,
-                           sym, round_zp, qmin, qmax, (T*)scales, (T*)zeros);
-        LLMC_LAUNCH_CHECK();
-        return LLMC_OK;
-    }
-    LLMC_REQUIRE(g < (1ll << 31), "minmax_qparams: row too long");
-    if (vec_ok && small_ok(g, V16)) {
-        int lpr = (int)(g / V16);
-        int grid = grid_for(ceil_div64(G, (64 / lpr) * UNR), kBlock / 64);
-        hipLaunchKernelGGL((k_quant_dynamic_small<T, V16, LLMC_OUT_FAKE, false>), dim3(grid), dim3(kBlock), 0, st,
-                           (const T*)W, (const T*)nullptr, G, (int)g, 1, lpr, sym, round_zp, qmin, qmax, (void*)nullptr,
-                           (T*)scales, (T*)zeros);
-        LLMC_LAUNCH_CHECK();
-        return LLMC_OK;
-    }
-    if (vec_ok) {
-        int lpr = choose_lpr(g, V16);
-        int grid = grid_for(ceil_div64(G, 64 / lpr), kBlock / 64);
-        hipLaunchKernelGGL((k_minmax_qparams<T, V16>), dim3(grid), dim3(kBlock), 0, st, (const T*)W, G, (int)g,
-                           lpr, sym, round_zp, qmin, qmax, (T*)scales, (T*)zeros);
-    } else {
-        int lpr = choose_lpr(g, 1);
-        int grid = grid_for(ceil_div64(G, 64 / lpr), kBlock / 64);
-        hipLaunchKernelGGL((k_minmax_qparams<T, 1>), dim3(grid), dim3(kBlock), 0, st, (const T*)W, G, (int)g,
-                           lpr, sym, round_zp, qmin, qmax, (T*)scales, (T*)zeros);
-    }
+    const bool vec_ok = g % V16 == 0 && aligned16(W);
+    const int64_t nch = ceil_div64(g, kChunk);
+    const int grid = capped_grid(G * nch, 1, kMaxGrid);
+    if (vec_ok)
+        hipLaunchKernelGGL((k_minmax_partial<T, V16>), dim3(grid), dim3(kBlock), 0, st, (const T*)W, G, g, nch,
+                           (float2*)ws);
+    else
+        hipLaunchKernelGGL((k_minmax_partial<T, 1>), dim3(grid), dim3(kBlock), 0, st, (const T*)W, G, g, nch,
+                           (float2*)ws);
+    LLMC_LAUNCH_CHECK();
+    hipLaunchKernelGGL((k_minmax_final<T>), dim3((unsigned)G), dim3(1024), 0, st, (const float2*)ws, G, nch, sym,
+                       round_zp, qmin, qmax, (T*)scales, (T*)zeros);
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;
 }
@@ -477,11 +510,13 @@ extern "C" int llmc_minmax_qparams(const void* W, int dt, int64_t G, int64_t g, 
     LLMC_REQUIRE(W && scales && G > 0 && g > 0, "minmax_qparams: null/empty argument");
     LLMC_REQUIRE(sym || zeros, "minmax_qparams: zeros required for asymmetric");
     hipStream_t st = (hipStream_t)stream;
-    switch (dt) {
-        case LLMC_F16: return minmax_qparams_t<f16_t>(W, G, g, sym, round_zp, qmin, qmax, scales, zeros, ws, st);
-        case LLMC_BF16: return minmax_qparams_t<bf16_t>(W, G, g, sym, round_zp, qmin, qmax, scales, zeros, ws, st);
-        default: return minmax_qparams_t<float>(W, G, g, sym, round_zp, qmin, qmax, scales, zeros, ws, st);
+    if (use_two_stage(G, g)) {
+        LLMC_REQUIRE(ws != nullptr, "minmax_qparams: workspace required for long rows");
+        DISPATCH_DT(dt, return minmax_two_stage_t<T>(W, G, g, sym, round_zp, qmin, qmax, scales, zeros, ws, st));
     }
+    LLMC_REQUIRE(g < (1ll << 31), "minmax_qparams: row too long");
+    DISPATCH_DT(dt, return launch_quant_rows<T, OUT_NONE, false>(W, nullptr, G, g, 1, sym, round_zp, qmin, qmax, nullptr,
+                                                                 scales, zeros, st));
 }
 
 
@@ -586,20 +621,9 @@ extern "C" int llmc_mse_qparams(const void* W, int dt, int64_t G, int64_t g, int
     LLMC_REQUIRE(sym || zeros, "mse_qparams: zeros required for asymmetric");
     LLMC_REQUIRE(nsteps >= 1 && grid >= 1, "mse_qparams: nsteps and grid must be positive");
     hipStream_t st = (hipStream_t)stream;
-    const int nblk = grid_for(G, kBlock / 64);
-    switch (dt) {
-        case LLMC_F16:
-            hipLaunchKernelGGL((k_mse_qparams<f16_t>), dim3(nblk), dim3(kBlock), 0, st, (const f16_t*)W, G, (int)g, sym,
-                               round_zp, qmin, qmax, nsteps, grid, norm, scales, zeros, min_out, max_out);
-            break;
-        case LLMC_BF16:
-            hipLaunchKernelGGL((k_mse_qparams<bf16_t>), dim3(nblk), dim3(kBlock), 0, st, (const bf16_t*)W, G, (int)g, sym,
-                               round_zp, qmin, qmax, nsteps, grid, norm, scales, zeros, min_out, max_out);
-            break;
-        default:
-            hipLaunchKernelGGL((k_mse_qparams<float>), dim3(nblk), dim3(kBlock), 0, st, (const float*)W, G, (int)g, sym,
-                               round_zp, qmin, qmax, nsteps, grid, norm, scales, zeros, min_out, max_out);
-    }
+    const int nblk = capped_grid(G, kBlock / 64, kMaxGrid);
+    DISPATCH_DT(dt, hipLaunchKernelGGL((k_mse_qparams<T>), dim3(nblk), dim3(kBlock), 0, st, (const T*)W, G, (int)g, sym,
+                                       round_zp, qmin, qmax, nsteps, grid, norm, scales, zeros, min_out, max_out));
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;
 }
@@ -620,7 +644,7 @@ extern "C" int llmc_mse_qparams_panel(const float* W, int64_t R, int64_t ld, int
     const int64_t nb = ceil_div64(width, group_size);
     LLMC_REQUIRE(g0 >= 0 && ng >= g0 + nb && ng < (1ll << 31), "mse_qparams_panel: groups outside scales' row");
     hipStream_t st = (hipStream_t)stream;
-    const int nblk = grid_for(R * nb, kBlock / 64);
+    const int nblk = capped_grid(R * nb, kBlock / 64, kMaxGrid);
     hipLaunchKernelGGL(k_mse_panel, dim3(nblk), dim3(kBlock), 0, st, W, R, ld, c0, (int)width, (int)group_size, sym,
                        round_zp, qmin, qmax, nsteps, grid, norm, scales, zeros, (int)ng, (int)g0);
     LLMC_LAUNCH_CHECK();
@@ -635,27 +659,31 @@ static int quant_static_tk(const void* W, int64_t G, int64_t g, const void* scal
                   (KIND != LLMC_OUT_FAKE || ((uintptr_t)out & 15) == 0);
     LLMC_REQUIRE(g < (1ll << 31), "quant_static: row too long");
     if (vec_ok) {
-        int grid = grid_for(G * (g / V16), kBlock);
+        int grid = capped_grid(G * (g / V16), kBlock, kMaxGrid);
         hipLaunchKernelGGL((k_quant_static<T, V16, KIND>), dim3(grid), dim3(kBlock), 0, st, (const T*)W, G,
                            (int)g, scales, sdt, zeros, zdt, qmin, qmax, out);
     } else {
-        int grid = grid_for(G * g, kBlock);
+        int grid = capped_grid(G * g, kBlock, kMaxGrid);
         hipLaunchKernelGGL((k_quant_static<T, 1, KIND>), dim3(grid), dim3(kBlock), 0, st, (const T*)W, G,
                            (int)g, scales, sdt, zeros, zdt, qmin, qmax, out);
     }
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;
 }
+// out_kind -> KIND as a compile-time constant for the statement(s); an unknown kind runs nothing
+#define DISPATCH_OUT_KIND(kind, ...)                                                     \
+    switch (kind) {                                                                      \
+        case LLMC_OUT_FAKE: { constexpr int KIND = LLMC_OUT_FAKE; __VA_ARGS__; break; }  \
+        case LLMC_OUT_I32: { constexpr int KIND = LLMC_OUT_I32; __VA_ARGS__; break; }    \
+        case LLMC_OUT_I8: { constexpr int KIND = LLMC_OUT_I8; __VA_ARGS__; break; }      \
+        case LLMC_OUT_U8: { constexpr int KIND = LLMC_OUT_U8; __VA_ARGS__; break; }      \
+    }
+
 template <typename T>
 static int quant_static_t(const void* W, int64_t G, int64_t g, const void* scales, int sdt,
                           const void* zeros, int zdt, float qmin, float qmax, int kind, void* out,
                           hipStream_t st) {
-    switch (kind) {
-        case LLMC_OUT_FAKE: return quant_static_tk<T, LLMC_OUT_FAKE>(W, G, g, scales, sdt, zeros, zdt, qmin, qmax, out, st);
-        case LLMC_OUT_I32: return quant_static_tk<T, LLMC_OUT_I32>(W, G, g, scales, sdt, zeros, zdt, qmin, qmax, out, st);
-        case LLMC_OUT_I8: return quant_static_tk<T, LLMC_OUT_I8>(W, G, g, scales, sdt, zeros, zdt, qmin, qmax, out, st);
-        case LLMC_OUT_U8: return quant_static_tk<T, LLMC_OUT_U8>(W, G, g, scales, sdt, zeros, zdt, qmin, qmax, out, st);
-    }
+    DISPATCH_OUT_KIND(kind, return quant_static_tk<T, KIND>(W, G, g, scales, sdt, zeros, zdt, qmin, qmax, out, st));
     set_last_error_msg("quant_static: bad out_kind");
     return LLMC_EINVAL;
 }
@@ -667,11 +695,7 @@ extern "C" int llmc_quant_static(const void* W, int wdt, int64_t G, int64_t g, c
                  "quant_static: bad dtype");
     LLMC_REQUIRE(W && scales && out && G > 0 && g > 0, "quant_static: null/empty argument");
     hipStream_t st = (hipStream_t)stream;
-    switch (wdt) {
-        case LLMC_F16: return quant_static_t<f16_t>(W, G, g, scales, sdt, zeros, zdt, qmin, qmax, out_kind, out, st);
-        case LLMC_BF16: return quant_static_t<bf16_t>(W, G, g, scales, sdt, zeros, zdt, qmin, qmax, out_kind, out, st);
-        default: return quant_static_t<float>(W, G, g, scales, sdt, zeros, zdt, qmin, qmax, out_kind, out, st);
-    }
+    DISPATCH_DT(wdt, return quant_static_t<T>(W, G, g, scales, sdt, zeros, zdt, qmin, qmax, out_kind, out, st));
 }
 
 extern "C" size_t llmc_quant_dynamic_ws_bytes(int64_t G, int64_t g) {
@@ -681,44 +705,11 @@ extern "C" size_t llmc_quant_dynamic_ws_bytes(int64_t G, int64_t g) {
     return llmc_minmax_qparams_ws_bytes(G, g) + (size_t)G * 8 + 64;
 }
 
-template <typename T, int KIND>
-static int quant_dynamic_tk(const void* W, int64_t G, int64_t g, int sym, int round_zp, float qmin,
-                            float qmax, void* out, void* scales, void* zeros, hipStream_t st) {
-    constexpr int V16 = 16 / sizeof(T);
-    bool vec_ok = (g % V16 == 0) && (((uintptr_t)W & 15) == 0) &&
-                  (KIND != LLMC_OUT_FAKE || ((uintptr_t)out & 15) == 0);
-    LLMC_REQUIRE(g < (1ll << 31), "quant_dynamic: row too long");
-    if (vec_ok && small_ok(g, V16) && (((uintptr_t)out & 15) == 0)) {
-        int lpr = (int)(g / V16);
-        int grid = grid_for(ceil_div64(G, (64 / lpr) * UNR), kBlock / 64);
-        hipLaunchKernelGGL((k_quant_dynamic_small<T, V16, KIND, false>), dim3(grid), dim3(kBlock), 0, st, (const T*)W,
-                           (const T*)nullptr, G, (int)g, 1, lpr, sym, round_zp, qmin, qmax, out, (T*)scales, (T*)zeros);
-        LLMC_LAUNCH_CHECK();
-        return LLMC_OK;
-    }
-    if (vec_ok) {
-        int lpr = choose_lpr(g, V16);
-        int grid = grid_for(ceil_div64(G, 64 / lpr), kBlock / 64);
-        hipLaunchKernelGGL((k_quant_dynamic<T, V16, KIND>), dim3(grid), dim3(kBlock), 0, st, (const T*)W, G,
-                           (int)g, lpr, sym, round_zp, qmin, qmax, out, (T*)scales, (T*)zeros);
-    } else {
-        int lpr = choose_lpr(g, 1);
-        int grid = grid_for(ceil_div64(G, 64 / lpr), kBlock / 64);
-        hipLaunchKernelGGL((k_quant_dynamic<T, 1, KIND>), dim3(grid), dim3(kBlock), 0, st, (const T*)W, G,
-                           (int)g, lpr, sym, round_zp, qmin, qmax, out, (T*)scales, (T*)zeros);
-    }
-    LLMC_LAUNCH_CHECK();
-    return LLMC_OK;
-}
 template <typename T>
 static int quant_dynamic_t(const void* W, int64_t G, int64_t g, int sym, int round_zp, float qmin,
                            float qmax, int kind, void* out, void* scales, void* zeros, hipStream_t st) {
-    switch (kind) {
-        case LLMC_OUT_FAKE: return quant_dynamic_tk<T, LLMC_OUT_FAKE>(W, G, g, sym, round_zp, qmin, qmax, out, scales, zeros, st);
-        case LLMC_OUT_I32: return quant_dynamic_tk<T, LLMC_OUT_I32>(W, G, g, sym, round_zp, qmin, qmax, out, scales, zeros, st);
-        case LLMC_OUT_I8: return quant_dynamic_tk<T, LLMC_OUT_I8>(W, G, g, sym, round_zp, qmin, qmax, out, scales, zeros, st);
-        case LLMC_OUT_U8: return quant_dynamic_tk<T, LLMC_OUT_U8>(W, G, g, sym, round_zp, qmin, qmax, out, scales, zeros, st);
-    }
+    DISPATCH_OUT_KIND(kind, return launch_quant_rows<T, KIND, false>(W, nullptr, G, g, 1, sym, round_zp, qmin, qmax, out, scales,
+                                                                     zeros, st));
     set_last_error_msg("quant_dynamic: bad out_kind");
     return LLMC_EINVAL;
 }
@@ -741,114 +732,16 @@ extern "C" int llmc_quant_dynamic(const void* W, int dt, int64_t G, int64_t g, i
         if (rc) return rc;
         return llmc_quant_static(W, dt, G, g, s, dt, z, dt, qmin, qmax, out_kind, out, stream);
     }
+    LLMC_REQUIRE(g < (1ll << 31), "quant_dynamic: row too long");
     void* zo = sym ? nullptr : zeros_out;
     int rc;
-    switch (dt) {
-        case LLMC_F16: rc = quant_dynamic_t<f16_t>(W, G, g, sym, round_zp, qmin, qmax, out_kind, out, scales_out, zo, st); break;
-        case LLMC_BF16: rc = quant_dynamic_t<bf16_t>(W, G, g, sym, round_zp, qmin, qmax, out_kind, out, scales_out, zo, st); break;
-        default: rc = quant_dynamic_t<float>(W, G, g, sym, round_zp, qmin, qmax, out_kind, out, scales_out, zo, st); break;
-    }
+    DISPATCH_DT(dt, rc = quant_dynamic_t<T>(W, G, g, sym, round_zp, qmin, qmax, out_kind, out, scales_out, zo, st));
     if (rc) return rc;
     if (sym && zeros_out) LLMC_HIP_CHECK(hipMemsetAsync(zeros_out, 0, (size_t)G * dtype_size(dt), st));
     return LLMC_OK;
 }
 
-// fake_quantize_weight of AWQ's search (awq.py:147-164): w' = rnd(w * s[col]) (the in-place mul_ in the
-// model dtype), then the dynamic fake-quant of the scaled row group. One pass over W.
-namespace llmc {
-template <typename T, int VEC>
-__global__ __launch_bounds__(kBlock) void k_scale_fakequant(const T* __restrict__ W, const T* __restrict__ cs,
-                                                            int64_t G, int g, int gpr /*groups per row*/,
-                                                            int lpr, int sym, float qmin, float qmax,
-                                                            T* __restrict__ out) {
-    constexpr int DT = dt_of<T>::value;
-    const int lane = threadIdx.x & 63;
-    const int rpw = 64 / lpr;
-    const int sub = lane / lpr, sl = lane % lpr;
-    const int64_t wave = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-    const int64_t nwaves = (int64_t)gridDim.x * (kBlock / 64);
-    for (int64_t r0 = wave * rpw; r0 < G; r0 += nwaves * rpw) {
-        int64_t row = r0 + sub;
-        const bool valid = row < G;
-        const int64_t rr = valid ? row : G - 1;
-        const T* rp = W + rr * g;
-        const T* cp = cs + (rr % gpr) * g;
-        float mn = INFINITY, mx = -INFINITY;
-        RowVec<T, VEC> first;
-        bool hf = false;
-        for (int c = sl * VEC; c < g; c += lpr * VEC) {
-            RowVec<T, VEC> v = load_vec<T, VEC>(rp + c);
-            RowVec<T, VEC> sv = load_vec<T, VEC>(cp + c);
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                float f = rndc<DT>(to_f32<T>(v.v[i]) * to_f32<T>(sv.v[i]));
-                v.v[i] = from_f32<T>(f);
-                mn = fminf(mn, f);
-                mx = fmaxf(mx, f);
-            }
-            if (!hf) {
-                first = v;
-                hf = true;
-            }
-        }
-        mn = wave_min(mn, lpr);
-        mx = wave_max(mx, lpr);
-        QParams q = qparams_from_minmax(mn, mx, DT, sym, 1, qmin, qmax);
-        if (!valid) continue;
-        const Divisor dv = make_divisor(q.s, fmaxf(fabsf(mn), fabsf(mx)));
-        bool use_first = true;
-        for (int c = sl * VEC; c < g; c += lpr * VEC) {
-            RowVec<T, VEC> v;
-            if (use_first) {
-                v = first;
-            } else {
-                v = load_vec<T, VEC>(rp + c);
-                RowVec<T, VEC> sv = load_vec<T, VEC>(cp + c);
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) v.v[i] = from_f32<T>(rndc<DT>(to_f32<T>(v.v[i]) * to_f32<T>(sv.v[i])));
-            }
-            use_first = false;
-            RowVec<T, VEC> o;
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) {
-                float qq = quant_code(to_f32<T>(v.v[k]), dv, q.z, DT, DT, qmin, qmax);
-                o.v[k] = from_f32<T>(dequant_code(qq, q.s, q.z, DT));
-            }
-            store_vec<T, VEC>(out + rr * g + c, o);
-        }
-    }
-}
-
-template <typename T>
-static int scale_fakequant_t(const void* W, const void* s, int64_t R, int64_t K, int64_t g, int sym, float qmin,
-                             float qmax, void* out, hipStream_t st) {
-    constexpr int V16 = 16 / sizeof(T);
-    const int64_t G = R * (K / g);
-    const int gpr = (int)(K / g);
-    bool vec_ok = (g % V16 == 0) && (((uintptr_t)W & 15) == 0) && (((uintptr_t)out & 15) == 0) &&
-                  (((uintptr_t)s & 15) == 0);
-    if (vec_ok && small_ok(g, V16)) {
-        int lpr = (int)(g / V16);
-        int grid = grid_for(ceil_div64(G, (64 / lpr) * UNR), kBlock / 64);
-        hipLaunchKernelGGL((k_quant_dynamic_small<T, V16, LLMC_OUT_FAKE, true>), dim3(grid), dim3(kBlock), 0, st,
-                           (const T*)W, (const T*)s, G, (int)g, gpr, lpr, sym, 1, qmin, qmax, out, (T*)nullptr,
-                           (T*)nullptr);
-    } else if (vec_ok) {
-        int lpr = choose_lpr(g, V16);
-        int grid = grid_for(ceil_div64(G, 64 / lpr), kBlock / 64);
-        hipLaunchKernelGGL((k_scale_fakequant<T, V16>), dim3(grid), dim3(kBlock), 0, st, (const T*)W, (const T*)s, G,
-                           (int)g, gpr, lpr, sym, qmin, qmax, (T*)out);
-    } else {
-        int lpr = choose_lpr(g, 1);
-        int grid = grid_for(ceil_div64(G, 64 / lpr), kBlock / 64);
-        hipLaunchKernelGGL((k_scale_fakequant<T, 1>), dim3(grid), dim3(kBlock), 0, st, (const T*)W, (const T*)s, G,
-                           (int)g, gpr, lpr, sym, qmin, qmax, (T*)out);
-    }
-    LLMC_LAUNCH_CHECK();
-    return LLMC_OK;
-}
-}  // namespace llmc
-
+// fake_quantize_weight of AWQ's search: k_quant_rows_scaled / k_quant_dynamic_small with the column multiplier, fake values only
 extern "C" int llmc_awq_scale_fakequant(const void* W, const void* s, int dt, int64_t R, int64_t K, int64_t g,
                                         int sym, float qmin, float qmax, void* out, llmc_stream_t stream) {
     LLMC_REQUIRE(dtype_ok(dt), "awq_scale_fakequant: bad dtype");
@@ -856,11 +749,9 @@ extern "C" int llmc_awq_scale_fakequant(const void* W, const void* s, int dt, in
     if (g <= 0) g = K;
     LLMC_REQUIRE(K % g == 0 && g < (1ll << 31), "awq_scale_fakequant: K must be a multiple of the group size");
     hipStream_t st = (hipStream_t)stream;
-    switch (dt) {
-        case LLMC_F16: return scale_fakequant_t<f16_t>(W, s, R, K, g, sym, qmin, qmax, out, st);
-        case LLMC_BF16: return scale_fakequant_t<bf16_t>(W, s, R, K, g, sym, qmin, qmax, out, st);
-        default: return scale_fakequant_t<float>(W, s, R, K, g, sym, qmin, qmax, out, st);
-    }
+    const int64_t gpr = K / g;      // groups per weight row: group r of the [R * gpr, g] view takes the multipliers s[(r % gpr) * g ...]
+    DISPATCH_DT(dt, return launch_quant_rows<T, LLMC_OUT_FAKE, true>(W, s, R * gpr, g, (int)gpr, sym, 1, qmin, qmax, out, nullptr,
+                                                                     nullptr, st));
 }
 
 extern "C" int llmc_pack_lsb(const void* codes, int code_kind, int64_t R, int64_t K, int bits,
@@ -871,7 +762,7 @@ extern "C" int llmc_pack_lsb(const void* codes, int code_kind, int64_t R, int64_
     hipStream_t st = (hipStream_t)stream;
     int pf = 32 / bits;
     int64_t Kp = ceil_div64(K, pf);
-    int grid = grid_for(R * Kp, kBlock);
+    int grid = capped_grid(R * Kp, kBlock, kMaxGrid);
     if (code_kind == LLMC_OUT_I32) {
         bool vec_ok = (K % 4 == 0) && (((uintptr_t)codes & 15) == 0);  // 16-B loads need aligned rows
         if (vec_ok)

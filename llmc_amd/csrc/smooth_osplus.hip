@@ -410,15 +410,7 @@ extern "C" int llmc_osplus_act_step(const void* X, const void* s, int dt, int64_
     hipStream_t st = (hipStream_t)stream;
     const int mode = fp8_mode & 0x130;
     if (kind == ACT_INT) {
-        switch (dt) {
-            case LLMC_F16: return act_step_launch<f16_t, ACT_INT>(tier, X, s, N, K, sym, qmin, qmax, mode, out, st);
-            case LLMC_BF16: return act_step_launch<bf16_t, ACT_INT>(tier, X, s, N, K, sym, qmin, qmax, mode, out, st);
-            default: return act_step_launch<float, ACT_INT>(tier, X, s, N, K, sym, qmin, qmax, mode, out, st);
-        }
+        DISPATCH_DT(dt, return act_step_launch<T, ACT_INT>(tier, X, s, N, K, sym, qmin, qmax, mode, out, st));
     }
-    switch (dt) {
-        case LLMC_F16: return act_step_launch<f16_t, ACT_FP8>(tier, X, s, N, K, sym, qmin, qmax, mode, out, st);
-        case LLMC_BF16: return act_step_launch<bf16_t, ACT_FP8>(tier, X, s, N, K, sym, qmin, qmax, mode, out, st);
-        default: return act_step_launch<float, ACT_FP8>(tier, X, s, N, K, sym, qmin, qmax, mode, out, st);
-    }
+    DISPATCH_DT(dt, return act_step_launch<T, ACT_FP8>(tier, X, s, N, K, sym, qmin, qmax, mode, out, st));
 }

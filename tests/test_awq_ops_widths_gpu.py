@@ -1,4 +1,5 @@
-"""AWQ's reductions and elementwise kernels (awq_kernels.hip, scale_fakequant in quant_kernels.hip) at model widths.
+"""AWQ's reductions and elementwise kernels (awq_kernels.hip; llmc_awq_scale_fakequant on k_quant_rows_scaled / k_quant_dynamic_small
+of quant_kernels.hip) at model widths.
 
 The goldens of test_awq_gpu.py stop at K = 256, 96 weight rows and 192 tokens; the branches that only run at real sizes are
 pinned here: several 512-token chunks of the activation mean, weight rows wider than one 256-thread column step, whole-row
@@ -233,10 +234,13 @@ def test_awq_scales_vs_oracle(dt, K):
 @pytest.mark.parametrize('dt', DTS)
 @pytest.mark.parametrize('bit', [3, 4, 8])
 def test_scale_fakequant_vs_oracle(dt, bit):
-    """per-channel rows of 4096 .. 28672 (the large-group kernel), groups of 64 and 128 (the small-group kernel), and a
-    weight view that is not 16-B aligned (the scalar kernel): bit-exact"""
+    """per-channel rows of 4096 .. 28672 (k_quant_rows_scaled: quant_rows with the column multiplier), groups of 64 and 128
+    (k_quant_dynamic_small with it), and a weight view that is not 16-B aligned (the scalar k_quant_rows_scaled): bit-exact.
+    The last three are quant_rows' tails: 15 groups of 96 at 4 per wave (sub-groups past the last row), rows of 3
+    vectors on 4 lanes (a lane that owns none), and, through the unaligned view, 13 scalar rows of 40 on 64 lanes"""
     from llmc_amd.compression.quantization import awq_ops
-    cases = [(24, 4096, 0), (16, 14336, 0), (8, 28672, 0), (40, 4096, 64), (40, 4096, 128)]
+    cases = [(24, 4096, 0), (16, 14336, 0), (8, 28672, 0), (40, 4096, 64), (40, 4096, 128),
+             (5, 288, 96), (9, 24, 0), (13, 40, 0)]
     for R, K, g in cases:
         w = cpu_weights(R, K, R * K + bit, dt)
         gen = torch.Generator().manual_seed(K + g)
@@ -250,7 +254,7 @@ def test_scale_fakequant_vs_oracle(dt, bit):
             ref = A.fake_quantize_weight(wn, sn, dt, sym, float(q.qmin), float(q.qmax), g)
             out = awq_ops.scale_fakequant(wd, sd, q)
             np.testing.assert_array_equal(bits(host(out)), bits(ref), err_msg=str((dt, bit, sym, R, K, g)))
-            if g == 0 and K == 4096 or g == 128:
+            if g == 0 and K in (4096, 40) or g == 128:
                 base = torch.empty(R * K + 1, dtype=TD[dt], device='cuda')
                 wu = base[1:].view(R, K)
                 wu.copy_(wd)

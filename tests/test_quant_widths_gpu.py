@@ -7,10 +7,15 @@ the shape, the dtype and the alignment; each case below asserts the branch it wa
 A  IntegerQuantizer dynamic (llmc_quant_dynamic / llmc_minmax_qparams):
    small   k_quant_dynamic_small: g = lpr * V16 with lpr a power of two <= 64 (g <= 512 for 16-bit types, <= 256 for fp32);
            per_group 32 / 128 / 256 at 4096 x 4096, per_group 128 at 14336 x 4096 (several grid-stride passes of kMaxGrid)
-   vector  k_quant_dynamic<V16>: fp32 per_group 512; per_channel rows of 11008 / 14336 / 28672 (lpr = 64); per_group 96
-   scalar  k_quant_dynamic<1>: a view one element into its storage; per_channel K = 4100 (K % V16 != 0)
+   vector  k_quant_rows<V16>: fp32 per_group 512; per_channel rows of 11008 / 14336 / 28672 (lpr = 64); per_group 96
+   scalar  k_quant_rows<1>: a view one element into its storage; per_channel K = 4100 (K % V16 != 0)
+   tails   of both (a few rows, whole tensor compared): G no multiple of the 64 / lpr rows of a wave (sub-groups past the last
+           row), lpr rounded up to a power of two (a lane that owns no vector of its row), a second stride that only some lanes
+           take (5 x 520, 3 x 37)
    two     k_minmax_partial + k_minmax_final + k_quant_static (g >= 32768 and G < 4096): per_tensor 14336 x 4096,
            per_channel 1024 x 32776 (partial last chunk), 1024 x 32771 (scalar loads); 4096 x 32768 is the G = 4096 boundary
+   every case also through get_tensor_qparams (llmc_minmax_qparams: k_quant_rows_qparams, quant_rows without its second
+   pass, or the branch's own)
    per_tensor asymmetric: _per_tensor_asym_qparams + k_quant_static with SCALAR_QPARAM;  activations per_token / per_tensor
 B  k_quant_static with given qparams: fp32 scales on 16-bit weights, integer zeros, 0-dim scale / zero (SCALAR_QPARAM),
    round_zp=False (FRACTIONAL_ZP), vector and scalar (unaligned) kernels
@@ -162,9 +167,12 @@ def plant_int(w, gw, bit, sym):
     qmin, qmax = Q.int_range(bit, sym)
     f = w.view(-1)
     s0 = 2.0 ** -6
+    G = f.numel() // gw                      # a tensor of fewer than 5 groups gets the groups it has
     f[0:gw] = 0.0
-    f[gw:2 * gw] = 0.0123
-    f[2 * gw:3 * gw] = -f[2 * gw:3 * gw].abs() - 1e-3
+    if G > 1:
+        f[gw:2 * gw] = 0.0123
+    if G > 2:
+        f[2 * gw:3 * gw] = -f[2 * gw:3 * gw].abs() - 1e-3
     if sym:
         pat = [(m + 0.5) * s0 for m in range(int(qmin), int(qmax))]
         head = [qmax * s0, -qmax * s0]
@@ -173,10 +181,11 @@ def plant_int(w, gw, bit, sym):
         pat = [mn + m * s0 for m in range(int(qmax - qmin) + 1)]
         head = [mn, mn + (qmax - qmin) * s0]
     vals = torch.tensor(head + pat * (-(-gw // len(pat))), dtype=torch.float32)[:gw]
-    G = f.numel() // gw
     for gi in (3, G - 1):
-        f[gi * gw:(gi + 1) * gw] = vals
-    f[4 * gw + gw - 1] = 1.5 * f[4 * gw:5 * gw].abs().max() + 0.05
+        if gi < G:
+            f[gi * gw:(gi + 1) * gw] = vals
+    if G > 4:
+        f[4 * gw + gw - 1] = 1.5 * f[4 * gw:5 * gw].abs().max() + 0.05
     return w
 
 
@@ -225,6 +234,12 @@ A_CASES = [
     ('vector_g96', 'f32', 1024, 4608, 'per_group', 96, 2, True, 'vector'),
     ('scalar_k4100', 'f16', 1024, 4100, 'per_channel', 0, 4, False, 'scalar'),
     ('scalar_k4100', 'bf16', 1024, 4100, 'per_channel', 0, 8, True, 'scalar'),
+    ('vector_tail_g96', 'bf16', 5, 288, 'per_group', 96, 4, False, 'vector'),       # G = 15, lpr = 16: 4 rows per wave
+    ('vector_idle_lane', 'bf16', 9, 24, 'per_channel', 0, 8, True, 'vector'),       # lpr 3 -> 4, 16 rows per wave
+    ('vector_tail_lpr8', 'f32', 13, 20, 'per_channel', 0, 8, False, 'vector'),      # lpr 5 -> 8, 8 rows per wave
+    ('vector_stride2', 'f16', 5, 520, 'per_channel', 0, 3, True, 'vector'),         # lpr = 64, 65 vectors: lane 0 reloads
+    ('scalar_tail_lpr8', 'f16', 13, 5, 'per_channel', 0, 8, True, 'scalar'),        # lpr = 8, 8 rows per wave
+    ('scalar_stride2', 'bf16', 3, 37, 'per_channel', 0, 2, False, 'scalar'),        # lpr = 64, a partial stride
     ('two_stage_tensor', 'bf16', 14336, 4096, 'per_tensor', 0, 8, True, 'two_stage'),
     ('two_stage_tensor', 'f16', 14336, 4096, 'per_tensor', 0, 4, True, 'two_stage'),
     ('two_stage_tensor', 'f32', 4096, 4096, 'per_tensor', 0, 3, True, 'two_stage'),
@@ -237,7 +252,8 @@ A_CASES = [
 
 
 def _check_int_dynamic(q, wd, wn, dt, bit, sym, gran, g, rows, tag):
-    """fake (fake_quant_weight_dynamic), codes / scales / zeros (real_quant_weight_dynamic) on the sampled weight rows"""
+    """fake (fake_quant_weight_dynamic), codes / scales / zeros (real_quant_weight_dynamic), scales / zeros alone
+    (get_tensor_qparams) on the sampled weight rows"""
     R, K = wn.shape
     qmin, qmax = Q.int_range(bit, sym)
     gw = R * K if gran == 'per_tensor' else (g or K)
@@ -246,6 +262,8 @@ def _check_int_dynamic(q, wd, wn, dt, bit, sym, gran, g, rows, tag):
     assert fq.dtype == TD[dt] and fq.shape == wd.shape, tag
     assert codes.dtype == code_dtype(bit, sym) and codes.shape == wd.shape, tag
     assert rs.dtype == TD[dt] and (rz is None) == sym, tag
+    _, qs, qz, _, _ = q.get_tensor_qparams(wd)
+    assert qs.dtype == TD[dt] and qs.numel() == rs.numel() and (qz.dim() == 0) == sym, tag
     if gran == 'per_tensor':
         s, z = Q.minmax_qparams(wn.reshape(1, -1), dt, sym, qmin, qmax)
         s, z = s.reshape(()), z.reshape(())
@@ -256,17 +274,22 @@ def _check_int_dynamic(q, wd, wn, dt, bit, sym, gran, g, rows, tag):
             ref_fake, ref_codes, _, _ = int_reference(wn[rows], dt, bit, sym, s, z)
         ref_s, ref_z = s.reshape(1), z.reshape(1)
         got_s, got_z = host(rs).reshape(-1), (None if sym else host(rz).reshape(-1))
+        got_qs, got_qz = host(qs).reshape(-1), (None if sym else host(qz).reshape(-1))
     else:
         gpr = K // gw
         ref_fake, ref_codes, ref_s, ref_z = int_reference(wn[rows].reshape(-1, gw), dt, bit, sym)
         ref_fake, ref_codes = ref_fake.reshape(len(rows), K), ref_codes.reshape(len(rows), K)
         got_s = host(rs).reshape(R, gpr)[rows].reshape(-1)
         got_z = None if sym else host(rz).reshape(R, gpr)[rows].reshape(-1)
+        got_qs = host(qs).reshape(R, gpr)[rows].reshape(-1)
+        got_qz = None if sym else host(qz).reshape(R, gpr)[rows].reshape(-1)
     eq_bits(host(fq[torch.from_numpy(rows).cuda()]), ref_fake, tag + ' fake')
     eq_int(codes[torch.from_numpy(rows).cuda()].cpu().numpy(), ref_codes, tag + ' codes')
     eq_bits(got_s, ref_s.reshape(-1), tag + ' scales')
+    eq_bits(got_qs, ref_s.reshape(-1), tag + ' qparams scales')
     if not sym:
         eq_bits(got_z, ref_z.reshape(-1), tag + ' zeros')
+        eq_bits(got_qz, ref_z.reshape(-1), tag + ' qparams zeros')
 
 
 @pytest.mark.parametrize('case', A_CASES, ids=[f'{c[0]}-{c[1]}-{c[2]}x{c[3]}-b{c[6]}{"s" if c[7] else "a"}' for c in A_CASES])
@@ -298,7 +321,7 @@ def test_dynamic_integer_quantizer(case):
 
 @pytest.mark.parametrize('dt,bit', [('bf16', 4), ('f16', 8), ('f32', 2)])
 def test_dynamic_integer_quantizer_unaligned_view(dt, bit):
-    """a contiguous view one element into its storage: the scalar k_quant_dynamic (per_group 128 at 1024 x 4096)"""
+    """a contiguous view one element into its storage: the scalar k_quant_rows (per_group 128 at 1024 x 4096)"""
     R, K, g = 1024, 4096, 128
     for sym in (False, True):
         w = plant_int(cpu_weights(R, K, 77 + bit), g, bit, sym)

@@ -55,8 +55,12 @@ def spqr_quantize(W, U, cfg, threshold):
     """spqr.py:185-254. W [R, K] fp32 (overwritten: running weights), U [K, K] fp32 upper factor.
     Returns (tmp, losses, mask uint8, scales [R, K/g], zeros)."""
     _ffi.require_gpu(W, U)
+    if W.dtype != torch.float32 or U.dtype != torch.float32 or not W.is_contiguous() or not U.is_contiguous():
+        raise ValueError('spqr_quantize: W and U must be contiguous fp32 (the kernel reads row-major [R, K] and [K, K])')
     L = _ffi.lib()
     R, K = W.shape
+    if tuple(U.shape) != (K, K):
+        raise ValueError(f'spqr_quantize: U is {tuple(U.shape)}, W has {K} columns')
     dev = W.device
     ng = K // cfg.group_size
     tmp, losses = torch.empty_like(W), torch.empty_like(W)

@@ -599,6 +599,26 @@ int llmc_osplus_act_step_tier(int dt, int64_t K);
 int llmc_osplus_act_step(const void* X, const void* s, int dt, int64_t N, int64_t K, int kind, int sym, float qmin, float qmax,
                          int fp8_mode, void* out, llmc_stream_t stream);
 
+/* ---- mixed int / fp columns (quant.py:754-783, 833-869 with int_indices / fp_indices: QUIK, LLM.int8()) ----------------------
+ * Fake-quantize some columns of X [N, K] (contiguous, dtype dt) dynamically and leave the others alone, in one pass: a row is
+ * read once, waits in LDS, is written once. role [K] says what becomes of a column: 0 = +0 is written (the reference's
+ * zeros_like), 1 = integer column, 2 = X's own bits pass through (NaN payloads, infinities, -0 survive), 3 = passes through but
+ * still counts in its group's min / max (a column named in both index lists: the reference's fp scatter comes second). The
+ * integer columns are cut into n_int / g groups in the order of int_idx (int32 [n_int], values in [0, K); entries outside are
+ * ignored): group j of a row is the columns int_idx[j * g .. (j + 1) * g). Each group gets get_minmax_range + get_qparams +
+ * quant_dequant in dt: bit for bit llmc_quant_dynamic (LLMC_OUT_FAKE) on the contiguous gathered copy X[:, int_idx], written
+ * back to the columns it came from; with round_zp = 0 bit for bit llmc_minmax_qparams + llmc_quant_static with
+ * LLMC_FRACTIONAL_ZP on that copy. With g == n_int (one group per row) int_idx may be NULL: the group is then every column
+ * whose role is 1 or 3. Duplicate entries in int_idx are undefined (as for torch's scatter); n_int > K is LLMC_EINVAL, as are
+ * n_int <= 0 and n_int % g != 0. out == X is allowed. Only fake values: the reference has no real-quant path for mixed
+ * columns. No workspace, no atomics, stream-ordered. Rows that do not fit the LDS of a CU (llmc_quant_dynamic_mixed_fits
+ * answers 0: above about 81900 16-bit or 40950 fp32 columns; a pure host call) return LLMC_ENOTSUP: callers compose
+ * llmc_quant_dynamic with gathers and scatters. */
+int llmc_quant_dynamic_mixed_fits(int dt, int64_t K);
+int llmc_quant_dynamic_mixed(const void* X, int dt, int64_t N, int64_t K, const uint8_t* role, const int32_t* int_idx,
+                             int64_t n_int, int64_t g, int sym, int round_zp, float qmin, float qmax, void* out,
+                             llmc_stream_t stream);
+
 /* ---- Walsh-Hadamard transform (hadamard_utils.py:72-122 matmul_hadU / matmul_hadU_cuda, module_utils.py:460-503 Rotater) ------
  * x, y: contiguous [outer, n, inner] of dt (F16 / BF16 / F32 / F64); y == x is allowed. Along the middle axis
  *   y[o, a*m + j, c] = scale * sum_{b, i} hadK[a][b] * S_m[j][i] * x[o, b*m + i, c],   n = K0 * m,

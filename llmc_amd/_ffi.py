@@ -118,6 +118,8 @@ SIGNATURES = {
     'llmc_osplus_scale': (_i32, [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp]),
     'llmc_osplus_act_step_tier': (_i32, [_i32, _i64]),
     'llmc_osplus_act_step': (_i32, [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _f32, _f32, _i32, _vp, _vp]),
+    'llmc_quant_dynamic_mixed_fits': (_i32, [_i32, _i64]),
+    'llmc_quant_dynamic_mixed': (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _f32, _f32, _vp, _vp]),
     'llmc_hadamard': (_i32, [_vp, _vp, _i32, _i64, _i64, _i64, _vp, _i32, _f64, _vp]),
     'llmc_test_sgemm': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                _i32, _i32, _vp]),

@@ -13,3 +13,5 @@ from .hqq import HQQ  # noqa: F401
 from .smoothquant import SmoothQuant  # noqa: F401
 from .osplus import OsPlus  # noqa: F401
 from .quarot import Quarot  # noqa: F401
+from .quik import QUIK  # noqa: F401
+from .llmint8 import LlmInt8  # noqa: F401

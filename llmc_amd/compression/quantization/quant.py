@@ -16,6 +16,10 @@ optimize_weights_proximal, quant.py:588-610, 680-697: the half-quadratic zero-po
 HQQ (hqq.py) runs the same solver. FloatQuantizer refuses hqq: the reference's solver rounds to an integer grid.
 FloatQuantizer under GPTQ: the column loop rounds to the quantizer's own grid (gptq.py, llmc_gptq_quantize_fp8_cols) for
 per_channel and per_group weights with fp8_semantics='qtorch' and calib_algo 'minmax'; GPTQ refuses the rest at construction.
+Also in scope: IntegerQuantizer.fake_quant_act_dynamic / fake_quant_weight_dynamic with args['int_indices'] / args['fp_indices']
+(quant.py:754-783, 833-869; QUIK, LLM.int8()): mixed int / fp columns in one kernel (mixed_ops.py, csrc/mixed_quant.hip), calib_algo
+'minmax', per_token / per_channel / per_group; args['current_bit'] is accepted. The two *_static functions and the other
+calib_algos keep refusing int_indices.
 Out of scope (raise NotImplementedError): W48; calib_algo 'hqq' inside GPTQ's column loop, AWQ's search, AutoClipper and
 SpQR (the algorithms refuse it).
 
@@ -504,10 +508,38 @@ class IntegerQuantizer(BaseQuantizer):
             _ffi.stream()), 'llmc_quant_dynamic')
         return out, scales, zeros
 
+    def _fake_quant_mixed(self, tensor, args):
+        """quant.py:754-783, 833-869 with int_indices: the columns args['int_indices'] of the last dimension are gathered in
+        that order, fake-quantized like a tensor of their own (per_group: consecutive runs of group_size entries of the list;
+        per_channel / per_token: one group per row), and written back; the columns args['fp_indices'] keep their bits; every
+        other column is zero. One kernel (mixed_ops.fake_quant_mixed)."""
+        from . import mixed_ops
+        if self.calib_algo != 'minmax':
+            raise NotImplementedError(f'int_indices with calib_algo={self.calib_algo}: no shipped method reaches it')
+        int_indices, fp_indices = args['int_indices'], args.get('fp_indices')
+        n_int = int(int_indices.numel())
+        if n_int == 0:
+            raise ValueError('int_indices is empty: nothing to quantize (the reference fails in amax on an empty dimension)')
+        if self.granularity == 'per_group':
+            g = int(self.group_size)
+            if n_int % g:
+                raise ValueError(f'len(int_indices) = {n_int} is not divisible by group size {g}')
+        elif self.granularity in ('per_channel', 'per_token'):
+            g = n_int
+        else:
+            raise NotImplementedError(f'int_indices with granularity {self.granularity}: no shipped method reaches it')
+        x2d = tensor.reshape(-1, tensor.shape[-1])
+        out = mixed_ops.fake_quant_mixed(x2d, int_indices, fp_indices, g, self.sym, self.round_zp, float(self.qmin),
+                                         float(self.qmax))
+        return out.reshape(tensor.shape)
+
     def fake_quant_weight_dynamic(self, weight, args={}):
-        """quant.py:833-869"""
-        if 'int_indices' in args or 'current_bit' in args:
-            raise NotImplementedError('mixed int/fp columns and current_bit are outside the hot path')
+        """quant.py:833-869. With args['int_indices'] / args['fp_indices'] (QUIK, LLM.int8()) the weight is cut along its last
+        dimension: see _fake_quant_mixed. args['current_bit'] is accepted and has no arithmetic effect: the reference swaps
+        self.bit for the call, but qmin / qmax were fixed in __init__ (quant.py:665-677) and only the real-quant dtype choice
+        reads self.bit."""
+        if 'int_indices' in args:
+            return self._fake_quant_mixed(weight, args)
         transpose = 'dim' in args and 'ic' in args['dim']
         q_weight = weight.T if transpose else weight
         org_w_shape = q_weight.shape
@@ -539,9 +571,10 @@ class IntegerQuantizer(BaseQuantizer):
         return q_weight.T if transpose else q_weight
 
     def fake_quant_act_dynamic(self, act, args={}):
-        """quant.py:753-783"""
-        if 'int_indices' in args or 'current_bit' in args:
-            raise NotImplementedError('mixed int/fp columns and current_bit are outside the hot path')
+        """quant.py:753-783; act is [B, T, K] or [T, K]. args['int_indices'] / args['fp_indices']: see _fake_quant_mixed.
+        args['current_bit'] is accepted and has no arithmetic effect (see fake_quant_weight_dynamic)."""
+        if 'int_indices' in args:
+            return self._fake_quant_mixed(act, args)
         org_shape = act.shape
         q_act = self.reshape_tensor(act)
         q_act, _, _ = self._dynamic(q_act, _ffi.OUT_FAKE, False)
@@ -549,6 +582,8 @@ class IntegerQuantizer(BaseQuantizer):
 
     def fake_quant_act_static(self, act, args={}):
         """quant.py:719-751"""
+        if 'int_indices' in args:
+            raise NotImplementedError('int_indices with static activation qparams: no shipped method reaches it')
         org_shape, org_dtype = act.shape, act.dtype
         q_act = self.reshape_tensor(act)
         q_act = self.quant_dequant(q_act, args['scales'], args['zeros'], args['qmax'], args['qmin'])

@@ -93,7 +93,7 @@ class Awq(BaseBlockwiseQuantization):
             # mul_cols + fake_quant_weight_dynamic without the scaled copy
             t = wq.reshape_tensor(w0.contiguous())
             if wq.fused_cols_ok(t) and cols.data_ptr() % 16 == 0:
-                out, _ = wq._run_narrow(t, True, cols=cols)
+                out, _ = wq._run(t, True, cols=cols)
                 return out.reshape(w0.shape)
         return wq.fake_quant_weight_dynamic(awq_ops.mul_cols_(w0.clone(), cols))
 

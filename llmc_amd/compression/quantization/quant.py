@@ -736,41 +736,13 @@ class FloatQuantizer(BaseQuantizer):
             self.qmax = torch.tensor(fmax)
             self.qmin = torch.tensor(-fmax)
 
-    def _run(self, tensor, fake, scales=None, raw_scales=False):
-        if self.narrow:
-            return self._run_narrow(tensor, fake, scales=scales, raw_scales=raw_scales)
-        _ffi.require_gpu(tensor, scales)
-        L = _ffi.lib()
-        tensor = tensor.contiguous()
-        G, g = self._geometry(tensor)
-        sdtype = torch.float32 if self.granularity == 'per_tensor' else tensor.dtype
-        static = scales is not None
-        if static:
-            s = scales.reshape(-1).to(tensor.device).contiguous()
-            if s.numel() != G:
-                raise ValueError(f'FloatQuantizer: {s.numel()} scales for {G} rows')
-            sdtype = s.dtype
-        else:
-            s = torch.empty(G, dtype=sdtype, device=tensor.device)
-        out = torch.empty_like(tensor) if fake else torch.empty(tensor.shape, dtype=torch.uint8, device=tensor.device)
-        ws = None if static else _ffi.workspace(L.llmc_fp8_quant_ws_bytes(G, g), tensor.device)
-        _ffi.check(L.llmc_fp8_quant(_ffi.ptr(tensor), _ffi.dt(tensor), G, g, int(bool(fake)) | self._mode | (0x800 if raw_scales else 0),
-                                    _ffi.ptr(out), _ffi.ptr(s),
-                                    _ffi.dt(sdtype), int(static), _ffi.ptr(ws), _ffi.stream()), 'llmc_fp8_quant')
-        return out, s.reshape(self._qparam_shape(tensor))
-
-    # ---- e2m1 / e3m2: one fused kernel (llmc_fpx_quant, csrc/fp4_quant.hip) --------------------------------------------
-    def fused_cols_ok(self, tensor):
-        """Whether llmc_fpx_quant takes a column multiplier for this (reshaped, contiguous) tensor with dynamic scales: rows
-        the single-read kernels hold (16-byte vectors, at most 16384 elements, aligned)."""
-        _, g = self._geometry(tensor)
-        v = 16 // tensor.element_size()
-        return g % v == 0 and g <= 16384 and tensor.data_ptr() % 16 == 0
-
-    def _run_narrow(self, tensor, fake, scales=None, raw_scales=False, cols=None):
-        """(out, scales) of one llmc_fpx_quant call on the reshaped tensor. out: the fake-quantized tensor, or uint8 codes.
-        scales: tensor dtype (the reference's integer qmax does not promote a 0-dim absmax to fp32), or uint8 e8m0 bytes.
-        cols: [K] multipliers applied to the columns of the 2-D weight on the way in (the weight itself is not written)."""
+    def _run(self, tensor, fake, scales=None, raw_scales=False, cols=None):
+        """(out, scales) of one llmc_fp8_quant (e4m3 / e5m2) or llmc_fpx_quant (e2m1 / e3m2) call on the reshaped tensor. out:
+        the fake-quantized tensor, or uint8 codes. scales: fp32 for an 8-bit per_tensor absmax and the tensor dtype otherwise
+        (the narrow formats' integer qmax does not promote a 0-dim absmax to fp32), or uint8 e8m0 bytes. cols (narrow formats):
+        [K] multipliers applied to the columns of the 2-D weight on the way in (the weight itself is not written)."""
+        if cols is not None and not self.narrow:
+            raise NotImplementedError(f'FloatQuantizer bit={self.bit}: llmc_fp8_quant takes no column multiplier')
         _ffi.require_gpu(tensor, scales, cols)
         L = _ffi.lib()
         tensor = tensor.contiguous()
@@ -785,7 +757,8 @@ class FloatQuantizer(BaseQuantizer):
                 raise ValueError(f"FloatQuantizer scale_format='e8m0': static scales are uint8 exponent bytes, got {s.dtype}")
             sdtype = s.dtype
         else:
-            sdtype = torch.uint8 if e8m0 else tensor.dtype
+            sdtype = (torch.uint8 if e8m0 else torch.float32 if self.granularity == 'per_tensor' and not self.narrow
+                      else tensor.dtype)
             s = torch.empty(G, dtype=sdtype, device=tensor.device)
         K = 0
         if cols is not None:
@@ -794,11 +767,25 @@ class FloatQuantizer(BaseQuantizer):
             if K % g or (G * g) % K:
                 raise ValueError(f'FloatQuantizer: {K} column multipliers for rows of {g}')
         out = torch.empty_like(tensor) if fake else torch.empty(tensor.shape, dtype=torch.uint8, device=tensor.device)
-        ws = None if static else _ffi.workspace(L.llmc_fpx_quant_ws_bytes(G, g), tensor.device)
-        _ffi.check(L.llmc_fpx_quant(_ffi.ptr(tensor), _ffi.dt(tensor), G, g, _ffi.ptr(cols), K,
-                                    int(bool(fake)) | self._mode | (0x800 if raw_scales else 0), _ffi.ptr(out), _ffi.ptr(s),
-                                    0 if e8m0 else _ffi.dt(sdtype), int(static), _ffi.ptr(ws), _ffi.stream()), 'llmc_fpx_quant')
+        ws_bytes = L.llmc_fpx_quant_ws_bytes if self.narrow else L.llmc_fp8_quant_ws_bytes
+        ws = None if static else _ffi.workspace(ws_bytes(G, g), tensor.device)
+        mode = int(bool(fake)) | self._mode | (0x800 if raw_scales else 0)
+        tail = (mode, _ffi.ptr(out), _ffi.ptr(s), 0 if e8m0 else _ffi.dt(sdtype), int(static), _ffi.ptr(ws), _ffi.stream())
+        if self.narrow:
+            _ffi.check(L.llmc_fpx_quant(_ffi.ptr(tensor), _ffi.dt(tensor), G, g, _ffi.ptr(cols), K, *tail), 'llmc_fpx_quant')
+        else:
+            _ffi.check(L.llmc_fp8_quant(_ffi.ptr(tensor), _ffi.dt(tensor), G, g, *tail), 'llmc_fp8_quant')
         return out, s.reshape(self._qparam_shape(tensor))
+
+    _run_narrow = _run        # the name the narrow formats' half of this function had; callers written against it keep working
+
+    # ---- e2m1 / e3m2: one fused kernel (llmc_fpx_quant, csrc/fp4_quant.hip) --------------------------------------------
+    def fused_cols_ok(self, tensor):
+        """Whether llmc_fpx_quant takes a column multiplier for this (reshaped, contiguous) tensor with dynamic scales: rows
+        the single-read kernels hold (16-byte vectors, at most 16384 elements, aligned)."""
+        _, g = self._geometry(tensor)
+        v = 16 // tensor.element_size()
+        return g % v == 0 and g <= 16384 and tensor.data_ptr() % 16 == 0
 
     def _decode(self, codes):
         """uint8 codes of a narrow format -> their values in fp32 (a 16- / 64-entry table: exact)."""
@@ -896,9 +883,8 @@ class FloatQuantizer(BaseQuantizer):
             # our extension (the reference asserts e4m3 / e5m2 here): e2m1 packed two per byte, e3m2 one code per byte
             codes = bits.reshape(shape)
             weight = pack_fp4(codes.reshape(-1, shape[-1])).reshape(*shape[:-1], shape[-1] // 2) if self.bit == 'e2m1' else codes
-            qshape = 1 if self.granularity == 'per_tensor' else (shape[0], -1)
-            return weight, scales.reshape(qshape), None
-        weight = bits.view(self._tdtype).reshape(shape)
+        else:
+            weight = bits.view(self._tdtype).reshape(shape)
         qshape = 1 if self.granularity == 'per_tensor' else (shape[0], -1)
         return weight, scales.reshape(qshape), None
 

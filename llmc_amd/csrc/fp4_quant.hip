@@ -15,18 +15,19 @@
 //               multiplier) waits in LDS between the reduction and the rounding. One HBM read.
 //   k_fpx_flat  static scales, and dynamic ones on everything else (longer rows, g not a multiple of V, misaligned pointers):
 //               absmax from llmc_minmax_qparams first (a second read), then a flat grid-stride pass, vectors or scalars.
-// 16-bit tensors divide by multiplying with fl(1 / s) and send the vectors with an element within 4 fp32 ulps of a rounding
-// boundary of the tensor dtype (or outside its normal range) through the IEEE division: the scheme of k_fp8_cast (fp8_pack.hip).
+// The quantizer step (scale rule, exact element, the division-free form of 16-bit tensors with its guard, emit) is
+// float_quant_math.h's, shared with k_fp8_cast (fp8_quant.hip).
 #include <type_traits>
 
 #include "common.h"
+#include "float_quant_math.h"
 #include "fp8_math.h"
 
 namespace llmc {
 namespace {
 
 constexpr int XB = 256;
-constexpr int FPX_FAKE = 1, FPX_FMT_SHIFT = 4, FPX_OCP = 0x100, FPX_E8M0 = 0x200, FPX_RAW_SCALES = 0x800;
+constexpr int FPX_OCP = 0x100, FPX_E8M0 = 0x200;        // beside the shared bits of float_quant_math.h
 constexpr int64_t FPX_RESIDENT = 16384;      // elements of a row k_fpx_row keeps in LDS
 
 struct FpxArgs {
@@ -50,79 +51,27 @@ template <int KIND> __device__ __forceinline__ float fpx_q_any(float t) { return
 template <int KIND> __device__ __forceinline__ uint8_t fpx_enc(float v) { return fpx_code(v, 2 + (KIND >> 1)); }
 template <int KIND> __device__ __forceinline__ float fpx_qmax() { return fpx_format_max(2 + (KIND >> 1)); }
 
-__device__ __forceinline__ float e8m0_value(uint32_t c) { return __uint_as_float(c ? c << 23 : 0x00400000u); }
-__device__ __forceinline__ float e8m0_recip(uint32_t c) { return e8m0_value(254u - c); }
-// the OCP MX rule: floor(log2(absmax)) - emax + 127, clamped to [0, 254]; an all-zero row takes 127 (scale 1)
-template <int KIND> __device__ __forceinline__ uint32_t e8m0_code(float absmax) {
-    constexpr int emax = fpx_fmt<(KIND >> 1) ? 3 : 2, (KIND >> 1) ? 2 : 1>::max_exp;
-    const int e = (int)((__float_as_uint(absmax) >> 23) & 0xffu) - emax;
-    return absmax == 0.0f ? 127u : (uint32_t)min(max(e, 0), 254);
-}
-
-// The scale of one row and what goes with it. s: the divisor (never 0); rs: fl(1 / s); fast: rs may replace the division.
-struct FpxScale {
-    float s, rs;
-    bool fast;
-};
+// the exponent of the format's largest value: what the OCP MX scale rule subtracts
+template <int KIND> constexpr int fpx_emax() { return fpx_fmt<(KIND >> 1) ? 3 : 2, (KIND >> 1) ? 2 : 1>::max_exp; }
 
 // dynamic scale from the row's absmax (a value of the tensor dtype); `first` lanes write it back
 template <typename T, int KIND>
-__device__ __forceinline__ FpxScale fpx_dynamic_scale(float absmax, bool clamped, const FpxArgs& a, int64_t row, bool first) {
-    constexpr int DT = dt_of<T>::value;
-    FpxScale r;
-    if (a.mode & FPX_E8M0) {
-        const uint32_t c = e8m0_code<KIND>(absmax);
-        if (first) ((uint8_t*)a.scales)[row] = (uint8_t)c;
-        r.s = e8m0_value(c);
-        r.rs = e8m0_recip(c);
-        r.fast = true;
-        return r;
-    }
-    const float am = clamped ? absmax : fmaxf(absmax, rndc<DT>(1e-5f));
-    float s = rnd(am / fpx_qmax<KIND>(), a.sdt);
-    // scales[scales == 0] = 1 in place (quant.py:1062) unless the caller wants get_qparams' own value (k_fp8_cast's rule)
-    if (first) store_from_f32(a.scales, row, a.sdt, (s == 0.0f && !(a.mode & FPX_RAW_SCALES)) ? 1.0f : s);
-    if (s == 0.0f) s = 1.0f;
-    r.s = s;
-    r.rs = 1.0f / s;
-    r.fast = s > 1e-30f && s < 1e30f;
-    return r;
-}
-__device__ __forceinline__ FpxScale fpx_static_scale(const FpxArgs& a, int64_t row) {
-    FpxScale r;
-    if (a.mode & FPX_E8M0) {
-        const uint32_t c = ((const uint8_t*)a.scales)[row];
-        r.s = e8m0_value(c);
-        r.rs = e8m0_recip(c);
-        r.fast = true;
-        return r;
-    }
-    float s = load_as_f32(a.scales, row, a.sdt);
-    if (s == 0.0f) s = 1.0f;                       // the caller's tensor is left alone
-    r.s = s;
-    r.rs = 1.0f / s;
-    r.fast = s > 1e-30f && s < 1e30f;
-    return r;
-}
-
-// the scaled element as the reference forms it: rnd_dt(w / s) + 0 (the `+ zeros` turns -0 into +0). A NaN keeps the bits it
-// came with (its sign decides the 'ocp' result). tdt: the dtype the quotient is rounded to (fp32 for an e8m0 scale: exact).
-__device__ __forceinline__ float fpx_scaled_exact(float w, float s, int tdt) {
-    const float t = rnd(rnd(w / s, tdt) + 0.0f, tdt);
-    return w != w ? w : t;
+__device__ __forceinline__ FloatScale fpx_dynamic_scale(float absmax, bool clamped, const FpxArgs& a, int64_t row, bool first) {
+    return float_dynamic_scale<dt_of<T>::value>(absmax, clamped, fpx_qmax<KIND>(), a.sdt, a.mode,
+                                                a.mode & FPX_E8M0, fpx_emax<KIND>(), a.scales, row, first);
 }
 template <typename T, int KIND>
 __device__ __forceinline__ void fpx_emit(float v, float s, int fake, T* of, uint8_t* ob) {
-    if (fake) *of = from_f32<T>(opaque_f32(v * s));           // fp32 product, one rounding to dt
+    if (fake) *of = float_emit<T>(v, s);
     else *ob = fpx_enc<KIND>(v);
 }
 
 // one 16-byte vector of (already column-scaled) elements
 template <typename T, int KIND>
-__device__ __forceinline__ void fpx_vec(const T (&w)[16 / sizeof(T)], const FpxScale sc, int tdt, int mode, T* of, uint8_t* ob) {
+__device__ __forceinline__ void fpx_vec(const T (&w)[16 / sizeof(T)], const FloatScale sc, int tdt, int mode, T* of, uint8_t* ob) {
     constexpr int DT = dt_of<T>::value;
     constexpr int V = 16 / sizeof(T);
-    const int fake = mode & FPX_FAKE;
+    const int fake = mode & FQ_FAKE;
     float v[V];
     bool done = false;
     if (mode & FPX_E8M0) {                                    // a power-of-two scale: the product with its reciprocal IS the quotient
@@ -135,29 +84,21 @@ __device__ __forceinline__ void fpx_vec(const T (&w)[16 / sizeof(T)], const FpxS
         done = true;
     } else if constexpr (V == 8) {
         if (sc.fast && tdt == DT) {
-            uint32_t tie = 0xffffffffu, tiny = 0xffffffffu, big = 0;
+            DivFreeGuard<DT> guard;
 #pragma unroll
             for (int k = 0; k < V; ++k) {
                 const float q = __builtin_fmaf(to_f32<T>(w[k]), sc.rs, 0.0f);
-                const uint32_t b = __float_as_uint(q);
-                if constexpr (DT == LLMC_BF16) {
-                    tie = min(tie, (b & 0xffffu) - 0x7ffcu);
-                } else {
-                    tie = min(tie, (b & 0x1fffu) - 0x0ffcu);
-                    tiny = min(tiny, (b & 0x7fffffffu) - 1u);
-                }
+                guard.quotient(q);
                 const float t = rndc<DT>(q);
-                big = max(big, __float_as_uint(t) & 0x7fffffffu);
+                guard.rounded(t);
                 v[k] = fpx_q_finite<KIND>(t);
             }
-            bool slow = tie <= 8u || big >= 0x7f800000u;                       // near a rounding boundary; inf / NaN
-            if constexpr (DT == LLMC_F16) slow = slow || tiny < 0x387fffffu || big >= 0x477fe000u;
-            done = !slow;
+            done = !(guard.slow() || guard.reaches(guard.T_NONFINITE));
         }
     }
     if (!done) {
 #pragma unroll
-        for (int k = 0; k < V; ++k) v[k] = fpx_q_any<KIND>(fpx_scaled_exact(to_f32<T>(w[k]), sc.s, tdt));
+        for (int k = 0; k < V; ++k) v[k] = fpx_q_any<KIND>(float_scaled_exact(to_f32<T>(w[k]), sc.s, tdt, true));
     }
 #pragma unroll
     for (int k = 0; k < V; ++k) fpx_emit<T, KIND>(v[k], sc.s, fake, &of[k], &ob[k]);
@@ -166,7 +107,7 @@ __device__ __forceinline__ void fpx_vec(const T (&w)[16 / sizeof(T)], const FpxS
 template <typename T>
 __device__ __forceinline__ void fpx_store_vec(const FpxArgs& a, int64_t i, const T* of, const uint8_t* ob) {
     constexpr int V = 16 / sizeof(T);
-    if (a.mode & FPX_FAKE) {
+    if (a.mode & FQ_FAKE) {
         uint4 o;
         __builtin_memcpy(&o, of, 16);
         *reinterpret_cast<uint4*>((T*)a.out + i * V) = o;
@@ -235,7 +176,7 @@ __global__ __launch_bounds__(XB) void k_fpx_seg(const FpxArgs a, int L, int lshi
         m = fpx_seg_max(m, L);
         if (active) {
             const int64_t row = i >> lshift;
-            const FpxScale sc = fpx_dynamic_scale<T, KIND>(m, false, a, row, (i & (L - 1)) == 0);
+            const FloatScale sc = fpx_dynamic_scale<T, KIND>(m, false, a, row, (i & (L - 1)) == 0);
             T of[V];
             uint8_t ob[V];
             fpx_vec<T, KIND>(w, sc, tdt, a.mode, of, ob);
@@ -266,7 +207,7 @@ __global__ __launch_bounds__(XB) void k_fpx_row(const FpxArgs a) {
         __syncthreads();
         m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
         __syncthreads();                            // red is written again for the next row
-        const FpxScale sc = fpx_dynamic_scale<T, KIND>(m, false, a, row, threadIdx.x == 0);
+        const FloatScale sc = fpx_dynamic_scale<T, KIND>(m, false, a, row, threadIdx.x == 0);
         for (int64_t j = threadIdx.x; j < vpr; j += XB) {
             T w[V], of[V];
             uint8_t ob[V];
@@ -285,17 +226,17 @@ __global__ __launch_bounds__(XB) void k_fpx_flat(const FpxArgs a, int vec) {
     const int tdt = (a.mode & FPX_E8M0) ? LLMC_F32 : (a.G == 1 ? DT : promote(DT, a.sdt));
     const int64_t total = a.G * a.g;
     auto scale_of = [&](int64_t row, bool first) {
-        if (a.static_scales) return fpx_static_scale(a, row);
+        if (a.static_scales) return float_static_scale(a.scales, a.sdt, a.mode & FPX_E8M0, row);
         return fpx_dynamic_scale<T, KIND>(to_f32<T>(((const T*)a.amax)[row]), true, a, row, first);      // the pre-pass clamped it
     };
     if (vec) {
         const int64_t nv = total / V, vpr = a.g / V;
         for (int64_t i = (int64_t)blockIdx.x * XB + threadIdx.x; i < nv; i += (int64_t)gridDim.x * XB) {
-            const int64_t row = a.G == 1 ? 0 : (nv < (int64_t)0xffffffffll ? (int64_t)((uint32_t)i / (uint32_t)vpr) : i / vpr);
+            const int64_t row = a.G == 1 ? 0 : row_of_vector(i, nv, vpr);
             T w[V], of[V];
             uint8_t ob[V];
             fpx_load_vec<T>(a, i, w);
-            const FpxScale sc = scale_of(row, i == row * vpr);
+            const FloatScale sc = scale_of(row, i == row * vpr);
             fpx_vec<T, KIND>(w, sc, tdt, a.mode, of, ob);
             fpx_store_vec<T>(a, i, of, ob);
         }
@@ -303,14 +244,14 @@ __global__ __launch_bounds__(XB) void k_fpx_flat(const FpxArgs a, int vec) {
     }
     for (int64_t i = (int64_t)blockIdx.x * XB + threadIdx.x; i < total; i += (int64_t)gridDim.x * XB) {
         const int64_t row = i / a.g;
-        const FpxScale sc = scale_of(row, i == row * a.g);
+        const FloatScale sc = scale_of(row, i == row * a.g);
         float x = to_f32<T>(((const T*)a.W)[i]);
         if (a.cols) x = rndc<DT>(x * to_f32<T>(((const T*)a.cols)[i % a.K]));
-        const float t = (a.mode & FPX_E8M0) ? (x != x ? x : __builtin_fmaf(x, sc.rs, 0.0f)) : fpx_scaled_exact(x, sc.s, tdt);
+        const float t = (a.mode & FPX_E8M0) ? (x != x ? x : __builtin_fmaf(x, sc.rs, 0.0f)) : float_scaled_exact(x, sc.s, tdt, true);
         T of;
         uint8_t ob;
-        fpx_emit<T, KIND>(fpx_q_any<KIND>(t), sc.s, a.mode & FPX_FAKE, &of, &ob);
-        if (a.mode & FPX_FAKE) ((T*)a.out)[i] = of; else ((uint8_t*)a.out)[i] = ob;
+        fpx_emit<T, KIND>(fpx_q_any<KIND>(t), sc.s, a.mode & FQ_FAKE, &of, &ob);
+        if (a.mode & FQ_FAKE) ((T*)a.out)[i] = of; else ((uint8_t*)a.out)[i] = ob;
     }
 }
 
@@ -394,12 +335,12 @@ extern "C" size_t llmc_fpx_quant_ws_bytes(int64_t G, int64_t g) { return llmc_fp
 extern "C" int llmc_fpx_quant(const void* W, int dt, int64_t G, int64_t g, const void* cols, int64_t K, int mode, void* out,
                               void* scales, int sdt, int static_scales, void* ws, llmc_stream_t stream) {
     LLMC_REQUIRE(dtype_ok(dt) && W && out && scales && G > 0 && g > 0, "fpx_quant: bad argument");
-    const int fmt = (mode >> FPX_FMT_SHIFT) & 3;
+    const int fmt = (mode >> FQ_FMT_SHIFT) & 3;
     if (fmt != 2 && fmt != 3) {
         set_last_error_msg("fpx_quant: format must be 2 (e2m1) or 3 (e3m2); e4m3 / e5m2 are llmc_fp8_quant's");
         return LLMC_ENOTSUP;
     }
-    if (mode & ~(FPX_FAKE | (3 << FPX_FMT_SHIFT) | FPX_OCP | FPX_E8M0 | FPX_RAW_SCALES)) {
+    if (mode & ~(FQ_FAKE | (3 << FQ_FMT_SHIFT) | FPX_OCP | FPX_E8M0 | FQ_RAW_SCALES)) {
         set_last_error_msg("fpx_quant: unknown semantics bits in mode");
         return LLMC_ENOTSUP;
     }

@@ -6,7 +6,7 @@
 //   llmc_fp8_act_quant      act_quant (one scale per `block` consecutive elements of a row)
 //   llmc_fp8_block_gemm     fp8_gemm + block_wise_fp8_forward_func: C = sum_kb (A_kb . B_kb^T) * a_s[m, kb] * b_s[n/128, kb]
 //                           on v_mfma_f32_32x32x16_fp8_fp8 (gfx950 reads OCP e4m3fn, not MI300's fnuz)
-// e4m3 rounding is pinned to torch.float8_e4m3fn's cast (RNE) like fp8_pack.hip; products of two e4m3 values are
+// e4m3 rounding is pinned to torch.float8_e4m3fn's cast (RNE) like fp8_quant.hip; products of two e4m3 values are
 // exact in fp32, the 128-deep partial sums accumulate in fp32 inside the MFMA.
 #include "common.h"
 #include <stdlib.h>

@@ -1,4 +1,4 @@
-// fp8_math.h — OCP e4m3fn conversions shared by fp8_pack.hip and fp8_block.hip. Rounding is pinned to torch.float8_e4m3fn's
+// fp8_math.h — OCP e4m3fn conversions shared by fp8_quant.hip, fp4_quant.hip and fp8_block.hip (the quantizer step around them: float_quant_math.h). Rounding is pinned to torch.float8_e4m3fn's
 // cast (round to nearest even, no saturation: a value that rounds above 448 becomes NaN).
 #pragma once
 #include "common.h"

@@ -1,5 +1,5 @@
 // quant_kernels.hip — HBM-bound quantizer kernels (K5/K6/K7 of SURVEY.md §2.3):
-//   min/max -> scale/zero, round/clamp (fake + real), LSB-first int packing.
+//   min/max -> scale/zero, round/clamp (fake + real), LSB-first int packing, the AutoAWQ GEMM packer (K7b).
 // Layout: W is a contiguous [G, g] view (one quantization group per row). A wave64 is cut into
 // 64/LPR sub-groups of LPR lanes, one row per sub-group, 16 B per lane per load (coalesced: a sub-group
 // reads LPR*16 contiguous bytes). Rows are distributed over a grid-stride of waves.
@@ -423,6 +423,50 @@ __global__ __launch_bounds__(kBlock) void k_pack_lsb(const C* __restrict__ codes
     }
 }
 
+// K7b: the AutoAWQ GEMM packer (module_utils.py:1004-1065): one thread per output word
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_pack_awq_w(const T* __restrict__ W, const void* __restrict__ scales, int sdt,
+                                                       const int32_t* __restrict__ zeros, int64_t R, int64_t K,
+                                                       int64_t g, int32_t* __restrict__ qweight) {
+    constexpr int WDT = dt_of<T>::value;
+    const int p = promote(WDT, LLMC_F16);
+    const int64_t R8 = R / 8, ng = K / g;
+    const int64_t total = K * R8;
+    const int order[8] = {0, 2, 4, 6, 1, 3, 5, 7};
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlock) {
+        const int64_t rw = i / K, k = i - rw * K;   // k fastest: coalesced reads of W rows
+        const int64_t gi = k / g;
+        uint32_t word = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int64_t r = rw * 8 + order[j];
+            const float s = rnd(load_as_f32(scales, r * ng + gi, sdt), LLMC_F16);   // scales.to(float16)
+            const float sz = rnd((float)zeros[r * ng + gi] * s, LLMC_F16);           // zeros * scales
+            float t = rnd(to_f32<T>(W[r * K + k]) + sz, p);
+            t = rnd(t / s, p);
+            const int code = (int)rintf(t);
+            word |= ((uint32_t)code) << (4 * j);
+        }
+        qweight[k * R8 + rw] = (int32_t)word;
+    }
+}
+__global__ __launch_bounds__(kBlock) void k_pack_awq_z(const void* __restrict__ scales, int sdt,
+                                                       const int32_t* __restrict__ zeros, int64_t R, int64_t ng,
+                                                       int32_t* __restrict__ qzeros, uint16_t* __restrict__ sout) {
+    const int64_t R8 = R / 8;
+    const int order[8] = {0, 2, 4, 6, 1, 3, 5, 7};
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < ng * R; i += (int64_t)gridDim.x * kBlock) {
+        const int64_t gi = i / R, r = i - gi * R;
+        sout[gi * R + r] = f32_to_f16_bits(load_as_f32(scales, r * ng + gi, sdt));
+        if (r < R8) {
+            uint32_t word = 0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) word |= ((uint32_t)zeros[(r * 8 + order[j]) * ng + gi]) << (4 * j);
+            qzeros[gi * R8 + r] = (int32_t)word;
+        }
+    }
+}
+
 static inline int choose_lpr(int64_t g, int vec) {
     int lpr = pow2_ceil(ceil_div64(g, vec));
     if (lpr > 64) lpr = 64;
@@ -775,6 +819,24 @@ extern "C" int llmc_pack_lsb(const void* codes, int code_kind, int64_t R, int64_
         hipLaunchKernelGGL((k_pack_lsb<int8_t, false>), dim3(grid), dim3(kBlock), 0, st, (const int8_t*)codes,
                            R, K, bits, Kp, packed);
     }
+    LLMC_LAUNCH_CHECK();
+    return LLMC_OK;
+}
+
+extern "C" int llmc_pack_awq_gemm(const void* weight, int wdt, const void* scales, int sdt, const int32_t* zeros,
+                                  int64_t R, int64_t K, int64_t g, int32_t* qweight, int32_t* qzeros,
+                                  void* scales_out_f16, llmc_stream_t stream) {
+    LLMC_REQUIRE(dtype_ok(wdt) && dtype_ok(sdt), "pack_awq_gemm: bad dtype");
+    LLMC_REQUIRE(weight && scales && zeros && qweight && qzeros && scales_out_f16 && R > 0 && K > 0 && g > 0,
+                 "pack_awq_gemm: null/empty argument (AutoAWQ needs asymmetric zeros)");
+    LLMC_REQUIRE(R % 8 == 0 && K % g == 0, "pack_awq_gemm: R must be a multiple of 8 and K of the group size");
+    hipStream_t st = (hipStream_t)stream;
+    const int grid = capped_grid(K * (R / 8), kBlock, 8192);
+    DISPATCH_DT(wdt, hipLaunchKernelGGL((k_pack_awq_w<T>), dim3(grid), dim3(kBlock), 0, st, (const T*)weight, scales, sdt, zeros, R,
+                                        K, g, qweight));
+    LLMC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_pack_awq_z, dim3(capped_grid((K / g) * R, kBlock, 8192)), dim3(kBlock), 0, st, scales, sdt, zeros, R, K / g, qzeros,
+                       (uint16_t*)scales_out_f16);
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;
 }

@@ -8,6 +8,7 @@
 //                          llmc_quant_dynamic (integer) or llmc_fp8_quant (FP8, dynamic per-row scales).
 // All three data passes are HBM-bound; DESIGN.md holds the byte counts they are measured against.
 #include "common.h"
+#include "float_quant_math.h"
 #include "fp8_math.h"
 #include "quant_math.h"
 #include "vec_powf.h"
@@ -244,13 +245,10 @@ __global__ __launch_bounds__(SB) void k_osplus_act_step(const T* __restrict__ X,
                 }
             }
         } else {
-            // llmc_fp8_quant with dynamic per-row scales: amax = clamp(absmax, 1e-5) in dt (the symmetric qparams with
-            // qmax = 1), scale = rnd(amax / finfo.max), zero scales replaced by 1, quotient rounded in dt, the encoder of
-            // fp8_math.h, value * scale in fp32 rounded once.
-            const int fmt = (mode >> 4) & 3, sem = mode & 0x100;
-            const float amax = qparams_from_minmax(mn, mx, DT, 1, 1, -1.0f, 1.0f).s;
-            float sc = rndc<DT>(amax / fp8_format_max(fmt));
-            if (sc == 0.0f) sc = 1.0f;
+            // llmc_fp8_quant with dynamic per-row scales (float_quant_math.h); the scale is not returned
+            const int fmt = (mode >> FQ_FMT_SHIFT) & 3, sem = mode & 0x100;
+            const float amax = qparams_from_minmax(mn, mx, DT, 1, 1, -1.0f, 1.0f).s;      // clamp(absmax, 1e-5) in dt
+            const float sc = float_dynamic_scale<DT>(amax, true, fp8_format_max(fmt), DT, 0, false, 0, nullptr, row, false).s;
 #pragma unroll 1
             for (int j = 0; j < MAXV; ++j) {
                 const int vi = j * SB + threadIdx.x;
@@ -263,10 +261,9 @@ __global__ __launch_bounds__(SB) void k_osplus_act_step(const T* __restrict__ X,
                     __builtin_memcpy(v, &rq, 16);
 #pragma unroll
                     for (int k = 0; k < V; ++k) {
-                        const float t = rndc<DT>(rndc<DT>(to_f32<T>(v[k]) / sc) + 0.0f);
                         float val;
-                        (void)fp8_encode(t, fmt, sem, &val);
-                        o[k] = from_f32<T>(opaque_f32(val * sc));
+                        (void)fp8_encode(float_scaled_exact(to_f32<T>(v[k]), sc, DT, false), fmt, sem, &val);
+                        o[k] = float_emit<T>(val, sc);
                     }
                     uint4 ro;
                     __builtin_memcpy(&ro, o, 16);

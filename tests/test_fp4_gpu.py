@@ -77,8 +77,8 @@ def test_every_input_pattern_with_static_scales(dt):
                 st = torch.tensor(s, dtype=torch.float32, device='cuda')
                 want = O.run(x.reshape(1, -1), dt, bit, sem, scales=np.array([[s]], np.float32), sdt='f32')
                 ok = defined(x, sem)
-                codes, _ = q._run_narrow(xg, False, scales=st)
-                fake, _ = q._run_narrow(xg, True, scales=st)
+                codes, _ = q._run(xg, False, scales=st)
+                fake, _ = q._run(xg, True, scales=st)
                 got_c, got_f = codes.cpu().numpy().reshape(-1), bits_of(fake).reshape(-1)
                 bad_c = (got_c != want['codes'].reshape(-1)) & ok
                 bad_f = (got_f != want_bits(want['fake'], dt).reshape(-1)) & ok
@@ -111,8 +111,8 @@ def test_every_finite_pattern_with_dynamic_group_scales(dt):
         for sem in SEMS:
             q = quantizer(bit, 'per_group', 128, sem=sem)
             want = O.run(x, dt, bit, sem)
-            codes, s = q._run_narrow(xg, False)
-            fake, _ = q._run_narrow(xg, True)
+            codes, s = q._run(xg, False)
+            fake, _ = q._run(xg, True)
             assert np.array_equal(bits_of(s).reshape(-1), want_bits(want['scales'], dt).reshape(-1)), (dt, bit, sem)
             bad = codes.cpu().numpy() != want['codes']
             assert not bad.any(), (dt, bit, sem, int(bad.sum()), x[bad][:4])
@@ -194,7 +194,7 @@ def test_shapes_where_the_kernel_takes_another_path(case, sem):
         want = O.run(x2, dt, bit, sem)
         xg = to_gpu(x, dt)
         fake = q.fake_quant_weight_dynamic(xg)
-        codes, s = q._run_narrow(q.reshape_tensor(xg), False)
+        codes, s = q._run(q.reshape_tensor(xg), False)
         assert s.dtype == TDT[dt]
         assert np.array_equal(bits_of(s).reshape(-1), want_bits(want['scales'], dt).reshape(-1)), (name, bit)
         assert np.array_equal(codes.cpu().numpy().reshape(x2.shape), want['codes']), (name, bit)
@@ -214,7 +214,7 @@ def test_misaligned_view_and_given_scales():
     want = O.run(x.reshape(-1, 128), dt, 'e2m1')
     t = view.reshape(-1, 128)
     assert t.data_ptr() == view.data_ptr()
-    fake, s = q._run_narrow(t, True)
+    fake, s = q._run(t, True)
     assert np.array_equal(bits_of(fake), want_bits(want['fake'], dt))
     assert np.array_equal(bits_of(s).reshape(-1), want_bits(want['scales'], dt).reshape(-1))
     given = want['scales'].copy()
@@ -241,16 +241,16 @@ def test_fused_column_multiplier_equals_mul_cols_then_quantize(shape, dt):
         t = q.reshape_tensor(w)
         assert q.fused_cols_ok(t)
         for fake in (True, False):
-            out1, s1 = q._run_narrow(t, fake, cols=cols)
+            out1, s1 = q._run(t, fake, cols=cols)
             assert torch.equal(w, keep)
             w2 = awq_ops.mul_cols_(w.clone(), cols)
-            out2, s2 = q._run_narrow(q.reshape_tensor(w2), fake)
+            out2, s2 = q._run(q.reshape_tensor(w2), fake)
             assert torch.equal(out1.view(torch.uint8), out2.view(torch.uint8)), (bit, gran, fake)
             assert torch.equal(s1.view(torch.uint8), s2.view(torch.uint8)), (bit, gran, fake)
     # small case against the oracle too
     if shape[0] == 6:
         q = quantizer('e2m1', 'per_group', 128)
-        out, _ = q._run_narrow(q.reshape_tensor(w), True, cols=cols)
+        out, _ = q._run(q.reshape_tensor(w), True, cols=cols)
         wn = O.mul_cols(w.float().cpu().numpy(), cols.float().cpu().numpy(), dt)
         want = O.run(wn.reshape(-1, 128), dt, 'e2m1')
         assert np.array_equal(bits_of(out), want_bits(want['fake'], dt))
@@ -266,7 +266,7 @@ def test_pack_and_dequant(shape, mx):
     xg = to_gpu(x, dt)
     q = quantizer('e2m1', 'per_group', 32, sem='ocp' if mx else 'qtorch', scale_format='e8m0' if mx else 'dtype')
     want = O.run(x.reshape(-1, 32), dt, 'e2m1', 'ocp' if mx else 'qtorch', 'e8m0' if mx else 'dtype')
-    codes, s = q._run_narrow(q.reshape_tensor(xg), False)
+    codes, s = q._run(q.reshape_tensor(xg), False)
     codes = codes.reshape(shape)
     assert np.array_equal(codes.cpu().numpy(), want['codes'].reshape(shape))
     packed = pack_fp4(codes)
@@ -304,8 +304,8 @@ def test_mx_block_scales(bit, dt):
     want = O.run(x2, dt, bit, 'ocp', 'e8m0')
     assert want['scales'][0, 0] == 127 and want['scales'][1, 0] == 127 + 2 - O.EMAX[bit] and want['scales'][2, 0] == want['scales'][1, 0]
     xg = to_gpu(x2, dt).reshape(8, 96)
-    codes, s = q._run_narrow(q.reshape_tensor(xg), False)
-    fake, s2 = q._run_narrow(q.reshape_tensor(xg), True)
+    codes, s = q._run(q.reshape_tensor(xg), False)
+    fake, s2 = q._run(q.reshape_tensor(xg), True)
     assert s.dtype == torch.uint8 and torch.equal(s, s2)
     assert np.array_equal(s.cpu().numpy().reshape(-1), want['scales'].reshape(-1))
     assert np.array_equal(codes.cpu().numpy(), want['codes'])
@@ -340,13 +340,13 @@ def run_awq(two_call):
             return algo.wquantizer.fake_quant_weight_dynamic(awq_ops.mul_cols_(w0.clone(), cols))
         algo._fake_quantize_weight = two
     else:
-        fused = algo.wquantizer._run_narrow
+        fused = algo.wquantizer._run
 
         def counting(*a, **k):
             if k.get('cols') is not None:
                 calls.append(1)
             return fused(*a, **k)
-        algo.wquantizer._run_narrow = counting
+        algo.wquantizer._run = counting
     algo.run_block_loop()
     assert calls                                           # the route under test ran
     pre = [m.weight.data.clone() for b in model.get_blocks() for m in (b.gate_proj, b.up_proj, b.down_proj)]

@@ -1,6 +1,6 @@
-"""The division-free form of the FP8 cast (csrc/fp8_pack.hip:fp8_fast8) against the same kernel with FP8_EXACT_DIV (every element
-through the IEEE division and the general encoder): identical codes and identical fake-quantized values, for both semantics,
-bf16 and fp16, per_tensor and per_channel, on tensors large enough to hit every guard thousands of times."""
+"""The division-free form of the FP8 cast (csrc/fp8_quant.hip:fp8_fast8, its guard in csrc/float_quant_math.h) against the same
+kernel with FP8_EXACT_DIV (every element through the IEEE division and the general encoder): identical codes and identical
+fake-quantized values, for both semantics, bf16 and fp16, per_tensor and per_channel, on tensors large enough to hit every guard thousands of times."""
 import time
 
 import numpy as np
@@ -48,6 +48,49 @@ def test_fast_cast_equals_the_exact_division_path(dt, sem):
                 assert torch.equal(a.view(torch.int16), b.view(torch.int16)), (gran, fake, float((a != b).float().mean()))
             else:
                 assert torch.equal(a, b), (gran, fake, float((a != b).float().mean()))
+
+
+def run_static(w, G, g, mode, scales):
+    from llmc_amd import _ffi
+    L = _ffi.lib()
+    out = torch.empty_like(w) if mode & 1 else torch.empty(w.shape, dtype=torch.uint8, device=w.device)
+    _ffi.check(L.llmc_fp8_quant(_ffi.ptr(w), _ffi.dt(w), G, g, mode, _ffi.ptr(out), _ffi.ptr(scales), _ffi.dt(scales.dtype), 1, None,
+                                _ffi.stream()), 'llmc_fp8_quant')
+    return out
+
+
+@pytest.mark.parametrize('dt', [torch.bfloat16, torch.float16])
+def test_every_bit_pattern_equals_the_exact_division_path(dt):
+    """The guard of the division-free form (csrc/float_quant_math.h:DivFreeGuard) on ALL 65536 patterns of the dtype — NaN, +-inf,
+    +-0 and subnormals included — per row, under static scales that exercise the zero -> 1 rule (0) and push quotients into the
+    8-bit subnormal range (3e4); as one per_tensor row with an fp32 scale; and with [5] fp32 scales, which promote the quotient to
+    fp32 (the fast form must not be taken). Each call equals the same call with FP8_EXACT_DIV, bit for bit.
+
+    The bf16 row with scale 3e4 holds the case this test found: negative patterns 0x8001..0x83e7 have a quotient below half of
+    bf16's smallest subnormal, rnd_bf16(w / s) is -0 and the reference's `+ zeros` makes it +0 (code 0x00); a division-free form
+    that adds its zero before the rounding returns -0 (code 0x80) under the dtype-cast semantics."""
+    from llmc_amd import _ffi
+    R, K = 5, 65536
+    row = torch.from_numpy(np.arange(K, dtype=np.uint16).view(np.int16)).view(dt)
+    w = row.repeat(R, 1).contiguous().cuda()
+    vals = [1.0, 0.0123, 2.0 ** -14, 0.0, 3e4]
+    layouts = (('rows, scales in dt', R, K, torch.tensor(vals, dtype=dt).cuda()),
+               ('one row, fp32 scale', 1, R * K, torch.tensor([0.0123], dtype=torch.float32).cuda()),
+               ('rows, fp32 scales', R, K, torch.tensor(vals, dtype=torch.float32).cuda()))
+    for fmt in (0, 0x10):                       # e4m3; e5m2 as the control (never on the fast form)
+        for sem in (0x100, 0):
+            for fake in (0, 1):
+                for no_packed16 in (0, 1):
+                    for name, G, g, s in layouts:
+                        mode = fake | fmt | sem
+                        with _ffi.option(fp8_no_packed16=no_packed16):
+                            a = run_static(w, G, g, mode, s)
+                            b = run_static(w, G, g, mode | EXACT_DIV, s)
+                        where = (fmt, sem, fake, no_packed16, name)
+                        if fake:
+                            assert torch.equal(a.view(torch.int16), b.view(torch.int16)), where
+                        else:
+                            assert torch.equal(a, b), where
 
 
 def test_cast_rate_at_the_mixtral_expert_shape():

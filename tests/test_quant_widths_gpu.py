@@ -1,4 +1,4 @@
-"""The shared quantizer kernels (quant_kernels.hip, fp8_pack.hip, fp8_block.hip) at model shapes, on every dispatch branch.
+"""The shared quantizer kernels (quant_kernels.hip, fp8_quant.hip, fp8_block.hip) at model shapes, on every dispatch branch.
 
 The goldens stop at 24 x 512 (integer), 24 x 160 (FP8) and 200 x 384 (FP8 per_block). The host entry points pick a kernel from
 the shape, the dtype and the alignment; each case below asserts the branch it was written for, with the host's own predicates
@@ -47,7 +47,7 @@ UNR = 4                                     # row sets per wave turn of k_quant_
 FMAX = {'e4m3': 448.0, 'e5m2': 57344.0}
 
 
-# ---- the host's dispatch predicates (quant_kernels.hip, fp8_pack.hip, fp8_block.hip) ---------------------------------------
+# ---- the host's dispatch predicates (quant_kernels.hip, fp8_quant.hip, fp8_block.hip) ---------------------------------------
 def small_ok(g, vec):
     lpr = g // vec
     return g % vec == 0 and 1 <= lpr <= 64 and (lpr & (lpr - 1)) == 0
@@ -580,7 +580,7 @@ def fp8_scale(absmax, dt, sdt, fmt):
 
 
 def fp8_rows(x, dt, s, tdt, fmt, sem):
-    """fp8_pack.hip:fp8_one: t = rnd(rnd(x / s, tdt) + 0, tdt) (tdt: the tensor dtype, promoted by a dimensioned fp32 scale but not by
+    """float_quant_math.h:float_scaled_exact: t = rnd(rnd(x / s, tdt) + 0, tdt) (tdt: the tensor dtype, promoted by a dimensioned fp32 scale but not by
     a 0-dim one), codes = fp8_encode(t), fake = the fp32 product v * s rounded once to dt"""
     with np.errstate(over='ignore', invalid='ignore', divide='ignore'):
         t = Q.rnd(Q.rnd(x / s, tdt) + np.float32(0.0), tdt)
@@ -861,7 +861,7 @@ def test_fp8_per_token_and_group32(dt, fmt, sem):
 
 @pytest.mark.parametrize('sem', ['qtorch', 'cast'])
 def test_fp8_zero_row_f16_scale_is_one(sem):
-    """an all-zero fp16 row: clamp(0, 1e-5) / 448 underflows to 0 in fp16, stored and returned as 1 (fp8_pack.hip: scale_of)"""
+    """an all-zero fp16 row: clamp(0, 1e-5) / 448 underflows to 0 in fp16, stored and returned as 1 (float_quant_math.h: float_dynamic_scale)"""
     R, K = 4096, 4096
     w = cpu_weights(R, K, 12)
     w[7] = 0.0

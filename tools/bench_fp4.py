@@ -33,8 +33,8 @@ def main():
     arm('e2m1 qtorch fake (one pass)', lambda: q4.fake_quant_weight_dynamic(w), 2 * n * 2 + sc)
     arm('e2m1 ocp fake (one pass)', lambda: o4.fake_quant_weight_dynamic(w), 2 * n * 2 + sc)
     arm('e2m1 ocp e8m0 g32 fake (one pass)', lambda: mx.fake_quant_weight_dynamic(w), 2 * n * 2 + n // 32)
-    arm('e2m1 qtorch codes (one pass)', lambda: q4._run_narrow(q4.reshape_tensor(w), False), n * 2 + n + sc)
-    arm('e2m1 qtorch fake with cols (one pass)', lambda: q4._run_narrow(q4.reshape_tensor(w), True, cols=cols), 2 * n * 2 + sc)
+    arm('e2m1 qtorch codes (one pass)', lambda: q4._run(q4.reshape_tensor(w), False), n * 2 + n + sc)
+    arm('e2m1 qtorch fake with cols (one pass)', lambda: q4._run(q4.reshape_tensor(w), True, cols=cols), 2 * n * 2 + sc)
     for fn, _, _ in arms.values():
         for _ in range(10):
             fn()

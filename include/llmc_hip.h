@@ -619,6 +619,33 @@ int llmc_quant_dynamic_mixed(const void* X, int dt, int64_t N, int64_t K, const 
                              int64_t n_int, int64_t g, int sym, int round_zp, float qmin, float qmax, void* out,
                              llmc_stream_t stream);
 
+/* ---- dynamic quantization along columns (quant.py:833-869 with args['dim'] = 'ic': AdaDim's per-input-channel axis) -----------
+ * W [R, K] row-major of dt with row stride ld >= K elements; a group is g consecutive rows of one column, group index
+ * k * (R / g) + r / g: the order of reshape_tensor(W.T). g == R is per_channel along the input axis; any g >= 1 that divides R
+ * is taken. out is contiguous [R, K] in W's own layout (not transposed), 16-byte aligned, and must not overlap W: fake values
+ * in dt (LLMC_OUT_FAKE) or codes (LLMC_OUT_I32 / I8 / U8). scales_out / zeros_out: optional, [K * R / g] of dt in group order
+ * (zeros_out of a symmetric quantizer: +0). Bit for bit llmc_quant_dynamic on the contiguous transposed copy of W, transposed
+ * back; with round_zp = 0 bit for bit llmc_minmax_qparams + llmc_quant_static with LLMC_FRACTIONAL_ZP on that copy. The one
+ * exception is the sign of a zero minimum, hence of a zero in zeros_out, which follows the order of the reduction as it does
+ * between the row kernel's own paths. No transposed copy, no atomics: lanes walk columns 16 bytes at a time, a wave's load
+ * covers four 256-byte row segments. Launch paths (llmc_quant_dynamic_cols_path answers which one a call takes, or a negative
+ * LLMC_E*, without touching the GPU; llmc_quant_dynamic_cols_paths is their number):
+ *   0  g <= 256: one workgroup takes min / max down a tile of g rows by a strip of columns, then re-reads the tile (from L2) and
+ *      stores. One read from HBM and one write of W, no workspace.
+ *   1  g > 256: the rows of a group are cut into slabs of 64; per-slab fp32 min / max go to ws, a small launch folds them per
+ *      column (and writes scales_out / zeros_out), a third launch quantizes. Two reads and one write of W, all coalesced.
+ *   2  W, ld or K do not allow 16-byte vectors (W not 16-byte aligned, ld or K not a multiple of 16 bytes: a ragged vector
+ *      tail included): the same two structures one element per lane.
+ * ws: llmc_quant_dynamic_cols_ws_bytes(R, K, g) bytes, 0 for g <= 256: (R / g) * (ceil(g / 64) + 1) * K * 8 otherwise.
+ * LLMC_EINVAL (with a llmc_hip_last_error text, before anything is launched): bad dt, a null W or out, R, K or g < 1, g not
+ * dividing R, ld < K, out unaligned or overlapping W, a bad out_kind, a missing workspace. */
+size_t llmc_quant_dynamic_cols_ws_bytes(int64_t R, int64_t K, int64_t g);
+int llmc_quant_dynamic_cols(const void* W, int dt, int64_t R, int64_t K, int64_t ld, int64_t g, int sym, int round_zp,
+                            float qmin, float qmax, int out_kind, void* out, void* scales_out, void* zeros_out, void* ws,
+                            llmc_stream_t stream);
+int llmc_quant_dynamic_cols_paths(void);
+int llmc_quant_dynamic_cols_path(const void* W, int dt, int64_t R, int64_t K, int64_t ld, int64_t g);
+
 /* ---- Walsh-Hadamard transform (hadamard_utils.py:72-122 matmul_hadU / matmul_hadU_cuda, module_utils.py:460-503 Rotater) ------
  * x, y: contiguous [outer, n, inner] of dt (F16 / BF16 / F32 / F64); y == x is allowed. Along the middle axis
  *   y[o, a*m + j, c] = scale * sum_{b, i} hadK[a][b] * S_m[j][i] * x[o, b*m + i, c],   n = K0 * m,

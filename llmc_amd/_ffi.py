@@ -120,6 +120,10 @@ SIGNATURES = {
     'llmc_osplus_act_step': (_i32, [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _f32, _f32, _i32, _vp, _vp]),
     'llmc_quant_dynamic_mixed_fits': (_i32, [_i32, _i64]),
     'llmc_quant_dynamic_mixed': (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _f32, _f32, _vp, _vp]),
+    'llmc_quant_dynamic_cols_ws_bytes': (_sz, [_i64, _i64, _i64]),
+    'llmc_quant_dynamic_cols': (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    'llmc_quant_dynamic_cols_paths': (_i32, []),
+    'llmc_quant_dynamic_cols_path': (_i32, [_vp, _i32, _i64, _i64, _i64, _i64]),
     'llmc_hadamard': (_i32, [_vp, _vp, _i32, _i64, _i64, _i64, _vp, _i32, _f64, _vp]),
     'llmc_test_sgemm': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                _i32, _i32, _vp]),
@@ -185,6 +189,7 @@ HOST_OPTIONS = {
     'awq_kt': 1,                              # 0: AWQ products on row-major operands and the 8-wave kernel (round-1 path)
     'awq_y_bytes': (1 << 32) - (1 << 20),     # chunk bound of the tile-blocked reference output (tests lower it)
     'k3_fused_prep': 1,                       # 0: llmc_hessian_prep + llmc_chol_inv_upper instead of the reversed gather + in-place factor
+    'quant_cols': 1,                          # 0: fake_quant_weight_dynamic with dim 'ic' as the transposed composition instead of llmc_quant_dynamic_cols
 }
 
 _HOST_DEFAULTS = dict(HOST_OPTIONS)

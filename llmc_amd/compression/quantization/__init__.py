@@ -15,3 +15,4 @@ from .osplus import OsPlus  # noqa: F401
 from .quarot import Quarot  # noqa: F401
 from .quik import QUIK  # noqa: F401
 from .llmint8 import LlmInt8  # noqa: F401
+from .adadim import AdaDim  # noqa: F401

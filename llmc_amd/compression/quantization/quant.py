@@ -20,6 +20,9 @@ Also in scope: IntegerQuantizer.fake_quant_act_dynamic / fake_quant_weight_dynam
 (quant.py:754-783, 833-869; QUIK, LLM.int8()): mixed int / fp columns in one kernel (mixed_ops.py, csrc/mixed_quant.hip), calib_algo
 'minmax', per_token / per_channel / per_group; args['current_bit'] is accepted. The two *_static functions and the other
 calib_algos keep refusing int_indices.
+Also in scope: IntegerQuantizer.fake_quant_weight_dynamic with args['dim'] = 'ic' (quant.py:833-869; AdaDim) on the column-wise
+kernel (quant_cols_ops.py, csrc/quant_cols.hip) for 2-D weights, calib_algo 'minmax', per_channel / per_group; the other cases
+keep the transposed composition on the row kernels.
 Out of scope (raise NotImplementedError): W48; calib_algo 'hqq' inside GPTQ's column loop, AWQ's search, AutoClipper and
 SpQR (the algorithms refuse it).
 
@@ -533,14 +536,38 @@ class IntegerQuantizer(BaseQuantizer):
                                          float(self.qmax))
         return out.reshape(tensor.shape)
 
+    def _cols_group(self, weight):
+        """The group length (rows of one column) when fake_quant_weight_dynamic(weight, {'dim': 'ic'}) goes to the column-wise
+        kernel, else None: a 2-D weight, calib_algo minmax, per_channel or per_group with group_size dividing the rows (a
+        weight of fewer rows than group_size is one group per column, as reshape_tensor keeps a short last dimension whole),
+        and HOST_OPTIONS['quant_cols'] on. Everything else (per_tensor, mse / learnable / hqq, 1-D tensors) keeps the
+        transposed composition."""
+        if not _ffi.HOST_OPTIONS['quant_cols'] or weight.dim() != 2 or self.calib_algo != 'minmax':
+            return None
+        R = weight.shape[0]
+        if self.granularity == 'per_channel':
+            return R
+        if self.granularity == 'per_group':
+            g = int(self.group_size)
+            if R < g:
+                return R
+            return g if R % g == 0 else None
+        return None
+
     def fake_quant_weight_dynamic(self, weight, args={}):
-        """quant.py:833-869. With args['int_indices'] / args['fp_indices'] (QUIK, LLM.int8()) the weight is cut along its last
+        """quant.py:833-869. With args['dim'] = 'ic' the groups run down the columns of the weight (AdaDim): see _cols_group. With args['int_indices'] / args['fp_indices'] (QUIK, LLM.int8()) the weight is cut along its last
         dimension: see _fake_quant_mixed. args['current_bit'] is accepted and has no arithmetic effect: the reference swaps
         self.bit for the call, but qmin / qmax were fixed in __init__ (quant.py:665-677) and only the real-quant dtype choice
         reads self.bit."""
         if 'int_indices' in args:
             return self._fake_quant_mixed(weight, args)
         transpose = 'dim' in args and 'ic' in args['dim']
+        if transpose and self._cols_group(weight) is not None:
+            # groups down the columns of the weight as it lies (llmc_quant_dynamic_cols): the bits of the route below without
+            # its two transposed copies, and contiguous
+            from . import quant_cols_ops
+            return quant_cols_ops.fake_quant_cols(weight, self._cols_group(weight), self.sym, self.round_zp, float(self.qmin),
+                                                  float(self.qmax))
         q_weight = weight.T if transpose else weight
         org_w_shape = q_weight.shape
         if self.calib_algo == 'learnable' and args.get('upbound_factor') is not None:

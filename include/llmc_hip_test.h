@@ -78,6 +78,19 @@ int llmc_test_chol_plan(int64_t K, int rev, int with_lanes, int32_t* out, int ca
  *   Everything after status is meaningful only for status 0 and a launch. Returns 1 when nothing would be launched (M, N or
  *   batch <= 0), else 0. */
 int llmc_test_gemm_route(const int64_t* in, int32_t* out);
+/* tests/test_linear_route.py, tests/test_linear_eval_exact_gpu.py: what llmc_linear_eval / llmc_linear_eval_kt would launch for a
+ * call, under the calling thread's options (linear_nosplit). The launchers fill their kernel arguments from the same record. Pure
+ * host call: the buffers are fake addresses, 16-B aligned and far apart. in, 16 int64:
+ *   [0] entry (0 llmc_linear_eval, 1 llmc_linear_eval_kt), [1] dt, [2..4] N, K, R, [5] mode (flags), [6..9] Yout, Y0, loss_sum, ws
+ *   given (0: NULL), [10..14] bytes added to the addresses of X, W, Yout, Y0, ws, [15] compute units of the device (0: ask the
+ *   current device; 256 where there is none).
+ * out, 12 int32: status (0 or the error the launcher would return, its message in llmc_hip_last_error), kernel (0 k_linear_eval, 1
+ *   k_linear_eval4), grid, threads, sbm, sbn, nrounds (the tile order: each of the 8 XCDs works on one sbm x sbn block of tiles per
+ *   round), ksplit (1: single pass), store (mode 0: 0 two-byte stores from the accumulators, 1 rows staged through LDS and stored
+ *   16 B per lane, 2 tile-blocked, 3 fp32 k-slices + the reduction kernel; mode 1: -1), STAGE_Y (mode 1: 0 Y0 read from global
+ *   memory, 1 row-major Y0 staged through LDS, 2 tile-blocked Y0 staged; mode 0: -1), tile rows (k-slices included) and tile
+ *   columns. Everything after status is meaningful only for status 0. Returns 0, or LLMC_EINVAL for a NULL argument. */
+int llmc_test_linear_route(const int64_t* in, int32_t* out);
 
 #ifdef __cplusplus
 }

@@ -135,6 +135,7 @@ SIGNATURES = {
     'llmc_test_gptq_pipe_plan': (_i32, [_i64, _i64, _i64, _i64, _i32, _vp, _i32]),
     'llmc_test_chol_plan': (_i32, [_i64, _i32, _i32, _vp, _i32]),
     'llmc_test_gemm_route': (_i32, [_vp, _vp]),
+    'llmc_test_linear_route': (_i32, [_vp, _vp]),
 }
 
 

@@ -63,21 +63,21 @@ __device__ __forceinline__ bool lin_tile(const LinArgs& a, int round, int& tm, i
     return tm < a.ntm && tn < a.ntn;
 }
 
-static void lin_tile_order(LinArgs& a, int grid) {
+static void lin_tile_order(int ntm, int ntn, int grid, int& sbm_out, int& sbn_out, int& nsn, int& nrounds) {
     const int spx = grid / 8;
     int best = 1;
     int64_t best_cost = -1;
     for (int sbn = 1; sbn <= 8; sbn *= 2) {
         if (spx % sbn) continue;
         const int sbm = spx / sbn;
-        const int64_t padded = ceil_div64(a.ntm, sbm) * sbm * ceil_div64(a.ntn, sbn) * sbn;
+        const int64_t padded = ceil_div64(ntm, sbm) * sbm * ceil_div64(ntn, sbn) * sbn;
         const int64_t cost = padded * 64 + (sbm + sbn);   // fewest padded tiles, then fewest panels per XCD
         if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = sbn; }
     }
-    a.sbn = best;
-    a.sbm = spx / best;
-    a.nsn = (int)ceil_div64(a.ntn, a.sbn);
-    a.nrounds = (int)ceil_div64(ceil_div64(a.ntm, a.sbm) * a.nsn, 8);
+    sbn_out = best;
+    sbm_out = spx / best;
+    nsn = (int)ceil_div64(ntn, sbn_out);
+    nrounds = (int)ceil_div64(ceil_div64(ntm, sbm_out) * nsn, 8);
 }
 
 template <int DT>
@@ -705,6 +705,92 @@ static int lin_ksplit(int64_t N, int64_t K, int64_t R, int grid) {
     return sk < 2 ? 1 : sk;
 }
 
+// Everything llmc_linear_eval / llmc_linear_eval_kt decide before they launch, as data: both launchers fill LinArgs and pick
+// the kernel instantiation from this struct, and llmc_test_linear_route (include/llmc_hip_test.h) returns it for given numbers.
+// `store` names the branch of the kernel's mode-0 epilogue the arguments select; the kernel tests the same expressions on
+// LinArgs (yblk, R & 7, the low bits of Y), so the two lines below that set it are the one place to keep in step with it.
+enum { LIN_STORE_NONE = -1, LIN_STORE_SCALAR = 0, LIN_STORE_ROWS = 1, LIN_STORE_BLOCKED = 2, LIN_STORE_SPLITK = 3 };
+struct LinRoute {
+    int status;                    // LLMC_OK or what the launcher returns (the message is in the last error)
+    int kernel;                    // 0 k_linear_eval, 1 k_linear_eval4
+    int grid, threads, lds;
+    int mode, yblk;                // of the call (mode 0 / 1), before split-K turns the kernel's mode into 3
+    int ntm, ntn;                  // ntm counts every k-slice's tile rows (LinArgs::ntm)
+    int sbm, sbn, nsn, nrounds;
+    int ksplit;                    // 1: single pass
+    int store;                     // LIN_STORE_* (mode 1: LIN_STORE_NONE)
+    int stage_y;                   // k_linear_eval4's STAGE_Y in mode 1 (the row-major kernel: 0), mode 0: -1
+};
+
+// kt: llmc_linear_eval_kt, else llmc_linear_eval. cus: the device's compute units (the k-tiled kernel's grid; the row-major
+// kernel always launches 256 workgroups). The pointers are only tested for null and alignment.
+static LinRoute lin_route(bool kt, const void* X, const void* W, int dt, int64_t N, int64_t K, int64_t R, int mode_flags,
+                          const void* Yout, const void* Y0, const float* loss_sum, const void* ws, int cus) {
+    LinRoute r{};
+    const char* const who = kt ? "linear_eval_kt" : "linear_eval";
+    auto refuse = [&](int status, const char* what) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "%s: %s", who, what);
+        set_last_error_msg(msg);
+        LinRoute no{};
+        no.status = status;
+        return no;
+    };
+    const int mode = kt ? (mode_flags & 3) : mode_flags;
+    const int yblk = kt && (mode_flags & LLMC_LINEAR_YBLOCKED) != 0;
+    if (!(dt == LLMC_F16 || dt == LLMC_BF16)) return refuse(LLMC_EINVAL, "dtype must be f16 or bf16");
+    if (!(X && W && N > 0 && K > 0 && R > 0)) return refuse(LLMC_EINVAL, "null/empty argument");
+    if (kt && (mode_flags & ~(1 | LLMC_LINEAR_YBLOCKED)) != 0) return refuse(LLMC_EINVAL, "unknown mode bits");
+    if (!((mode == 0 && Yout) || (mode == 1 && Y0 && loss_sum && ws))) return refuse(LLMC_EINVAL, "outputs for the mode missing");
+    if (((uintptr_t)X & 15) != 0 || ((uintptr_t)W & 15) != 0) return refuse(LLMC_EINVAL, "operands must be 16-B aligned");
+    const int kmul = kt ? L4_KS * L4_RING : LBK;
+    if (K % kmul != 0 || N * K * 2 >= (1ll << 32) || R * K * 2 >= (1ll << 32))
+        return refuse(LLMC_ENOTSUP, kt ? "needs K % 128 == 0 and operands below 4 GiB" : "needs K % 64 == 0 and operands below 4 GiB");
+    if (yblk) {
+        if ((((uintptr_t)(mode == 0 ? Yout : Y0)) & 15) != 0) return refuse(LLMC_EINVAL, "blocked Y must be 16-B aligned");
+        if (llmc_linear_eval_yblocked_bytes(N, R) >= (1ull << 32))
+            return refuse(LLMC_ENOTSUP, "tile-blocked Y must stay below 4 GiB");
+    }
+    r.mode = mode; r.yblk = yblk; r.kernel = kt ? 1 : 0;
+    r.ntm = (int)ceil_div64(N, LT); r.ntn = (int)ceil_div64(R, LT);
+    r.ksplit = 1;
+    if (!kt) {
+        r.grid = 256; r.threads = LTHREADS; r.lds = LLDS + 64;
+        r.store = mode == 0 ? LIN_STORE_SCALAR : LIN_STORE_NONE;
+        r.stage_y = mode == 1 ? 0 : -1;
+    } else {
+        r.grid = cus & ~7; r.threads = L4_THREADS; r.lds = L4_LDS + 64;
+        if (r.grid < 8) return refuse(LLMC_EINVAL, "device has fewer than 8 compute units");
+        // split-K for products that leave CUs idle (mode 0, row-major output, workspace given): fp32 slices into ws, then one
+        // reduction + rounding pass. option linear_nosplit keeps the single-pass form (tests compare the two).
+        if (mode == 0 && !yblk && ws && ((uintptr_t)ws & 15) == 0 && ((uintptr_t)Yout & 15) == 0 && !opt(OPT_LINEAR_NOSPLIT))
+            r.ksplit = lin_ksplit(N, K, R, r.grid);
+        if (r.ksplit > 1) r.ntm *= r.ksplit;
+        if (mode == 0)
+            r.store = r.ksplit > 1 ? LIN_STORE_SPLITK : yblk ? LIN_STORE_BLOCKED
+                      : ((R & 7) == 0 && ((uintptr_t)Yout & 15) == 0) ? LIN_STORE_ROWS : LIN_STORE_SCALAR;
+        else r.store = LIN_STORE_NONE;
+        const bool y0_lds = mode == 1 && !yblk && R % 8 == 0 && ((uintptr_t)Y0 & 15) == 0 && N * R * 2 < (1ll << 32);
+        r.stage_y = mode == 1 ? (yblk ? 2 : y0_lds ? 1 : 0) : -1;
+    }
+    lin_tile_order(r.ntm, r.ntn, r.grid, r.sbm, r.sbn, r.nsn, r.nrounds);
+    return r;
+}
+
+// the kernel arguments of a routed call
+static LinArgs lin_args(const LinRoute& r, const void* X, const void* W, int64_t N, int64_t K, int64_t R, void* Yout, const void* Y0,
+                        void* ws) {
+    LinArgs a;
+    a.X = (const char*)X; a.W = (const char*)W; a.N = N; a.K = K; a.R = R; a.mode = r.mode;
+    a.Y = (char*)Yout; a.Y0 = (const char*)Y0; a.part = (float*)ws;
+    a.ntm = r.ntm; a.ntn = r.ntn; a.sbm = r.sbm; a.sbn = r.sbn; a.nsn = r.nsn; a.nrounds = r.nrounds;
+    a.yblk = r.yblk; a.y0_lds = r.stage_y == 1;
+    a.C = nullptr; a.ldc = 0; a.csign = 1.0f; a.krange = 0; a.kunit = 1; a.queue = nullptr;
+    a.ksplit = r.ksplit; a.ntm_real = r.ntm / r.ksplit;
+    if (r.ksplit > 1) { a.mode = 3; a.C = (float*)ws; a.ldc = R; }
+    return a;
+}
+
 }  // namespace llmc
 
 using namespace llmc;
@@ -719,29 +805,16 @@ extern "C" size_t llmc_linear_eval_ws_bytes(int64_t N, int64_t K, int64_t R) {
 
 extern "C" int llmc_linear_eval(const void* X, const void* Wq, int dt, int64_t N, int64_t K, int64_t R, int mode,
                                 void* Yout, const void* Y0, float* loss_sum, void* ws, llmc_stream_t stream) {
-    LLMC_REQUIRE(dt == LLMC_F16 || dt == LLMC_BF16, "linear_eval: dtype must be f16 or bf16");
-    LLMC_REQUIRE(X && Wq && N > 0 && K > 0 && R > 0, "linear_eval: null/empty argument");
-    LLMC_REQUIRE((mode == 0 && Yout) || (mode == 1 && Y0 && loss_sum && ws), "linear_eval: outputs for the mode missing");
-    LLMC_REQUIRE(((uintptr_t)X & 15) == 0 && ((uintptr_t)Wq & 15) == 0, "linear_eval: operands must be 16-B aligned");
-    if (K % LBK != 0 || N * K * 2 >= (1ll << 32) || R * K * 2 >= (1ll << 32)) {
-        set_last_error_msg("linear_eval: needs K % 64 == 0 and operands below 4 GiB");
-        return LLMC_ENOTSUP;
-    }
+    const LinRoute r = lin_route(false, X, Wq, dt, N, K, R, mode, Yout, Y0, loss_sum, ws, 0);
+    if (r.status != LLMC_OK) return r.status;
     hipStream_t st = (hipStream_t)stream;
-    LinArgs a;
-    a.X = (const char*)X; a.W = (const char*)Wq; a.N = N; a.K = K; a.R = R; a.mode = mode;
-    a.Y = (char*)Yout; a.Y0 = (const char*)Y0; a.part = (float*)ws;
-    a.ntm = (int)ceil_div64(N, LT); a.ntn = (int)ceil_div64(R, LT);
-    lin_tile_order(a, 256);
-    a.y0_lds = 0;
-    a.yblk = 0;
-    a.C = nullptr; a.ldc = 0; a.csign = 1.0f; a.krange = 0; a.kunit = 1; a.queue = nullptr; a.ksplit = 1; a.ntm_real = a.ntm;
+    const LinArgs a = lin_args(r, X, Wq, N, K, R, Yout, Y0, ws);
     if (dt == LLMC_BF16) {
-        if (int rc = ensure_dynamic_lds((const void*)k_linear_eval<LLMC_BF16>, LLDS + 64)) return rc;
-        hipLaunchKernelGGL((k_linear_eval<LLMC_BF16>), dim3(256), dim3(LTHREADS), LLDS + 64, st, a);
+        if (int rc = ensure_dynamic_lds((const void*)k_linear_eval<LLMC_BF16>, r.lds)) return rc;
+        hipLaunchKernelGGL((k_linear_eval<LLMC_BF16>), dim3(r.grid), dim3(r.threads), r.lds, st, a);
     } else {
-        if (int rc = ensure_dynamic_lds((const void*)k_linear_eval<LLMC_F16>, LLDS + 64)) return rc;
-        hipLaunchKernelGGL((k_linear_eval<LLMC_F16>), dim3(256), dim3(LTHREADS), LLDS + 64, st, a);
+        if (int rc = ensure_dynamic_lds((const void*)k_linear_eval<LLMC_F16>, r.lds)) return rc;
+        hipLaunchKernelGGL((k_linear_eval<LLMC_F16>), dim3(r.grid), dim3(r.threads), r.lds, st, a);
     }
     LLMC_LAUNCH_CHECK();
     if (mode == 1) {
@@ -770,42 +843,12 @@ extern "C" size_t llmc_linear_eval_yblocked_bytes(int64_t N, int64_t R) {
 
 extern "C" int llmc_linear_eval_kt(const void* Xt, const void* Wt, int dt, int64_t N, int64_t K, int64_t R, int mode_flags,
                                    void* Yout, const void* Y0, float* loss_sum, void* ws, llmc_stream_t stream) {
-    const int mode = mode_flags & 3, yblk = (mode_flags & LLMC_LINEAR_YBLOCKED) != 0;
-    LLMC_REQUIRE(dt == LLMC_F16 || dt == LLMC_BF16, "linear_eval_kt: dtype must be f16 or bf16");
-    LLMC_REQUIRE(Xt && Wt && N > 0 && K > 0 && R > 0, "linear_eval_kt: null/empty argument");
-    LLMC_REQUIRE((mode_flags & ~(1 | LLMC_LINEAR_YBLOCKED)) == 0, "linear_eval_kt: unknown mode bits");
-    LLMC_REQUIRE((mode == 0 && Yout) || (mode == 1 && Y0 && loss_sum && ws), "linear_eval_kt: outputs for the mode missing");
-    LLMC_REQUIRE(((uintptr_t)Xt & 15) == 0 && ((uintptr_t)Wt & 15) == 0, "linear_eval_kt: operands must be 16-B aligned");
-    if (K % (L4_KS * L4_RING) != 0 || N * K * 2 >= (1ll << 32) || R * K * 2 >= (1ll << 32)) {
-        set_last_error_msg("linear_eval_kt: needs K % 128 == 0 and operands below 4 GiB");
-        return LLMC_ENOTSUP;
-    }
-    if (yblk) {
-        LLMC_REQUIRE((((uintptr_t)(mode == 0 ? (const void*)Yout : Y0)) & 15) == 0, "linear_eval_kt: blocked Y must be 16-B aligned");
-        if (llmc_linear_eval_yblocked_bytes(N, R) >= (1ull << 32)) {
-            set_last_error_msg("linear_eval_kt: tile-blocked Y must stay below 4 GiB");
-            return LLMC_ENOTSUP;
-        }
-    }
+    const LinRoute r = lin_route(true, Xt, Wt, dt, N, K, R, mode_flags, Yout, Y0, loss_sum, ws, device_cu_count());
+    if (r.status != LLMC_OK) return r.status;
     hipStream_t st = (hipStream_t)stream;
-    LinArgs a;
-    a.X = (const char*)Xt; a.W = (const char*)Wt; a.N = N; a.K = K; a.R = R; a.mode = mode;
-    a.Y = (char*)Yout; a.Y0 = (const char*)Y0; a.part = (float*)ws;
-    a.ntm = (int)ceil_div64(N, LT); a.ntn = (int)ceil_div64(R, LT);
-    const int grid = device_cu_count() & ~7;
-    LLMC_REQUIRE(grid >= 8, "linear_eval_kt: device has fewer than 8 compute units");
-    a.yblk = yblk;
-    a.C = nullptr; a.ldc = 0; a.csign = 1.0f; a.krange = 0; a.kunit = 1; a.queue = nullptr; a.ksplit = 1; a.ntm_real = a.ntm;
-    // split-K for products that leave CUs idle (mode 0, row-major output, workspace given): fp32 slices into ws, then one
-    // reduction + rounding pass. option linear_nosplit keeps the single-pass form (tests compare the two).
-    const int sk = (mode == 0 && !yblk && ws && ((uintptr_t)ws & 15) == 0 && ((uintptr_t)Yout & 15) == 0 && !opt(OPT_LINEAR_NOSPLIT))
-                       ? lin_ksplit(N, K, R, grid) : 1;
-    if (sk > 1) {
-        a.mode = 3; a.C = (float*)ws; a.ldc = R; a.ksplit = sk; a.ntm = a.ntm_real * sk;
-    }
-    lin_tile_order(a, grid);
-    a.y0_lds = mode == 1 && !yblk && R % 8 == 0 && ((uintptr_t)Y0 & 15) == 0 && N * R * 2 < (1ll << 32);
-    int stage = mode == 1 ? (yblk ? 2 : a.y0_lds ? 1 : 0) : 0;
+    LinArgs a = lin_args(r, Xt, Wt, N, K, R, Yout, Y0, ws);
+    const int mode = r.mode, sk = r.ksplit;
+    int stage = mode == 1 ? r.stage_y : 0;
 #ifdef LLMC_LAB   // lab builds only (tools/probes): wrong losses by design, never compiled into the shipped library
     if (const char* e = lab_env("LLMC_LIN_ABL")) {
         const int v = atoi(e);
@@ -818,9 +861,9 @@ extern "C" int llmc_linear_eval_kt(const void* Xt, const void* Wt, int dt, int64
     const void* fn = stage == 2 ? (bf ? (const void*)k_linear_eval4<LLMC_BF16, 2> : (const void*)k_linear_eval4<LLMC_F16, 2>)
                    : stage == 1 ? (bf ? (const void*)k_linear_eval4<LLMC_BF16, 1> : (const void*)k_linear_eval4<LLMC_F16, 1>)
                                 : (bf ? (const void*)k_linear_eval4<LLMC_BF16, 0> : (const void*)k_linear_eval4<LLMC_F16, 0>);
-    if (int rc = ensure_dynamic_lds(fn, L4_LDS + 64)) return rc;
+    if (int rc = ensure_dynamic_lds(fn, r.lds)) return rc;
     void* kargs[] = {(void*)&a};
-    LLMC_HIP_CHECK(hipLaunchKernel(fn, dim3(grid), dim3(L4_THREADS), kargs, (size_t)(L4_LDS + 64), st));
+    LLMC_HIP_CHECK(hipLaunchKernel(fn, dim3(r.grid), dim3(r.threads), kargs, (size_t)r.lds, st));
     if (sk > 1) {
         const int64_t NR = N * R;
         const unsigned blocks = (unsigned)ceil_div64(NR, 256 * 8);
@@ -832,6 +875,21 @@ extern "C" int llmc_linear_eval_kt(const void* Xt, const void* Wt, int dt, int64
         hipLaunchKernelGGL(k_loss_reduce, dim3(1), dim3(1024), 0, st, (const float*)ws, a.ntm * a.ntn, loss_sum);
         LLMC_LAUNCH_CHECK();
     }
+    return LLMC_OK;
+}
+
+// C ABI test hook (include/llmc_hip_test.h): the route of a call given as numbers, on addresses that are only tested for null and
+// alignment
+extern "C" int llmc_test_linear_route(const int64_t* in, int32_t* out) {
+    if (!in || !out) return LLMC_EINVAL;
+    char* const base = (char*)(uintptr_t)((uint64_t)1 << 40);
+    const size_t span = (size_t)1 << 36;
+    auto at = [&](int slot, int64_t given, int64_t add) { return given ? (void*)(base + slot * span + add) : nullptr; };
+    const int cus = in[15] > 0 ? (int)in[15] : device_cu_count();
+    const LinRoute r = lin_route(in[0] != 0, at(0, 1, in[10]), at(1, 1, in[11]), (int)in[1], in[2], in[3], in[4], (int)in[5],
+                                 at(2, in[6], in[12]), at(3, in[7], in[13]), (const float*)at(4, in[8], 0), at(5, in[9], in[14]), cus);
+    const int32_t v[12] = {r.status, r.kernel, r.grid, r.threads, r.sbm, r.sbn, r.nrounds, r.ksplit, r.store, r.stage_y, r.ntm, r.ntn};
+    memcpy(out, v, sizeof v);
     return LLMC_OK;
 }
 
@@ -934,7 +992,7 @@ int gemm6_launch(const float* A, int64_t lda, const float* B, int64_t ldb, float
     a.ntm = (int)ceil_div64(M, LT); a.ntn = (int)ceil_div64(N, LT);
     const int grid = device_cu_count() & ~7;
     LLMC_REQUIRE(grid >= 8, "gemm6: device has fewer than 8 compute units");
-    lin_tile_order(a, grid);
+    lin_tile_order(a.ntm, a.ntn, grid, a.sbm, a.sbn, a.nsn, a.nrounds);
     a.yblk = 0; a.y0_lds = 0;
     a.C = C; a.ldc = ldc; a.csign = sign; a.krange = a_upper ? 1 : b_upper ? 2 : 0; a.kunit = 6;
     a.queue = (unsigned*)((char*)Bp + g6_align((size_t)6 * Kd * N * 2));

@@ -98,6 +98,14 @@ template <> struct dt_of<float> { static constexpr int value = LLMC_F32; };
         case LLMC_BF16: { using T = ::llmc::bf16_t; __VA_ARGS__; break; } \
         default: { using T = float; __VA_ARGS__; break; }                 \
     }
+// out_kind -> KIND as a compile-time constant for the statement(s); an unknown kind runs nothing
+#define DISPATCH_OUT_KIND(kind, ...)                                                     \
+    switch (kind) {                                                                      \
+        case LLMC_OUT_FAKE: { constexpr int KIND = LLMC_OUT_FAKE; __VA_ARGS__; break; }  \
+        case LLMC_OUT_I32: { constexpr int KIND = LLMC_OUT_I32; __VA_ARGS__; break; }    \
+        case LLMC_OUT_I8: { constexpr int KIND = LLMC_OUT_I8; __VA_ARGS__; break; }      \
+        case LLMC_OUT_U8: { constexpr int KIND = LLMC_OUT_U8; __VA_ARGS__; break; }      \
+    }
 
 __device__ __forceinline__ float f16_bits_to_f32(uint16_t u) {
     _Float16 h;
@@ -172,12 +180,6 @@ __host__ __device__ __forceinline__ int promote(int a, int b) {
     if (a == b) return a;
     return LLMC_F32;
 }
-
-// 16-byte vector of T
-template <typename T> struct vec16 {
-    static constexpr int N = 16 / sizeof(T);
-    T v[N];
-};
 
 // wave64 helpers
 __device__ __forceinline__ float wave_max(float v, int width) {

@@ -16,6 +16,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "quant_group.h"
 #include "quant_math.h"
 
 namespace llmc {
@@ -69,10 +70,13 @@ __device__ __forceinline__ void load_group(const HqqArgs& a, int64_t t, float (&
         const int64_t per_row = a.K / GS;
         const int64_t base = (t / per_row) * a.ld + (t % per_row) * GS;
         if (a.vec) {
-            constexpr int V = vec16<T>::N;
+            constexpr int V = 16 / sizeof(T);
 #pragma unroll
             for (int j = 0; j < GS / V; ++j) {
-                const vec16<T> v = *(const vec16<T>*)(W + base + j * V);
+                // a plain struct load, which claims the element's alignment only. With load_vec (a 16-byte aligned uint4) here
+                // k_hqq_chunk compiled to other register counts, 154 -> 248 VGPRs at <float, 64>: one occupancy step lost
+                // (profiles/quant_group_refactor.txt)
+                const Vec<T, V> v = *(const Vec<T, V>*)(W + base + j * V);
 #pragma unroll
                 for (int u = 0; u < V; ++u) w[j * V + u] = to_f32<T>(v.v[u]);
             }

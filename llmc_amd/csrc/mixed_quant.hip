@@ -1,7 +1,7 @@
 // mixed_quant.hip — IntegerQuantizer.fake_quant_act_dynamic / fake_quant_weight_dynamic with `int_indices` / `fp_indices`
 // (llmc quant.py:754-783, 833-869; the methods QUIK and LLM.int8()): some columns are fake-quantized, some pass through in
 // 16 bit, the rest are zero. The reference spells it gather -> quantize -> zeros_like -> two scatters; here a row is read from
-// HBM once (16-byte loads), waits in LDS, and is written once. The arithmetic is quant_math.h's, so a group gives bit for bit
+// HBM once (16-byte loads), waits in LDS, and is written once. The group step is quant_group.h's, so a group gives bit for bit
 // what llmc_quant_dynamic (round_zp) or llmc_minmax_qparams + llmc_quant_static (fractional zero point) give on the gathered
 // copy.
 //
@@ -17,6 +17,7 @@
 //                 random order costs bank conflicts (lanes of one 32-lane half on one bank, cdna LDS banking), not uncoalesced
 //                 HBM accesses; int_idx itself is read coalesced and, like role, is shared by all rows (L2).
 #include "common.h"
+#include "quant_group.h"
 #include "quant_math.h"
 
 namespace llmc {
@@ -26,30 +27,6 @@ static constexpr int MQ_LDS_MAX = 160 * 1024;     // gfx950: LDS of a CU, and th
 static constexpr int MQ_RED = 64;                 // workgroup-reduction scratch in front of the rows (dynamic region only)
 static constexpr int MQ_MULTI_ROW_LDS = 64 * 1024;   // k_mixed_idx takes several rows per workgroup up to this many bytes
 
-template <typename T, int V> struct MVec {
-    T v[V];
-};
-template <typename T, int V> __device__ __forceinline__ MVec<T, V> mload(const T* p) {
-    MVec<T, V> r;
-    if constexpr (V * sizeof(T) == 16) {
-        const uint4 raw = *reinterpret_cast<const uint4*>(p);
-        __builtin_memcpy(&r, &raw, 16);
-    } else {
-#pragma unroll
-        for (int i = 0; i < V; ++i) r.v[i] = p[i];
-    }
-    return r;
-}
-template <typename T, int V> __device__ __forceinline__ void mstore(T* p, const MVec<T, V>& r) {
-    if constexpr (V * sizeof(T) == 16) {
-        uint4 raw;
-        __builtin_memcpy(&raw, &r, 16);
-        *reinterpret_cast<uint4*>(p) = raw;
-    } else {
-#pragma unroll
-        for (int i = 0; i < V; ++i) p[i] = r.v[i];
-    }
-}
 // the roles of V consecutive columns (V = 8 / 4: one aligned load; the host checks role's alignment)
 template <int V> struct RoleVec {
     uint8_t r[V];
@@ -74,44 +51,16 @@ template <typename T> __device__ __forceinline__ T zero_of() {
     return z;
 }
 
-// A group's quantizer: get_qparams of its min / max, and the hoisted divisor. round_zp = 0 is the reference's other branch
-// (quant.py:702-707: round(x / s.clamp_min(1e-9) + z)), exactly as k_quant_static evaluates LLMC_FRACTIONAL_ZP.
-struct GroupQ {
-    Divisor dv;
-    float s, z;
-    bool fz;
-};
-template <int DT>
-__device__ __forceinline__ GroupQ group_q(float mn, float mx, int sym, int round_zp, float qmin, float qmax) {
-    const QParams q = qparams_from_minmax(mn, mx, DT, sym, round_zp, qmin, qmax);
-    GroupQ r;
-    r.s = q.s;
-    r.z = q.z;
-    r.fz = !round_zp;
-    const float sdiv = r.fz ? fmaxf(q.s, rnd(1e-9f, DT)) : q.s;
-    r.dv = make_divisor(sdiv, fmaxf(fabsf(mn), fabsf(mx)));
-    return r;
-}
-template <typename T> __device__ __forceinline__ T fake_value(T x, const GroupQ& q, float qmin, float qmax) {
-    constexpr int DT = dt_of<T>::value;
+// A group takes either branch of round_zp at run time (GroupQuant<true>): round_zp = 0 is the reference's fractional zero point,
+// exactly as k_quant_static evaluates LLMC_FRACTIONAL_ZP. The select is written out here, fractional arm first, as it always
+// was: q.fake() states it the other way round (the column kernels' order), and with that block order k_mixed_idx measured
+// 0.6 % slower than the parent commit's, above the run-to-run spread (profiles/quant_group_refactor.txt). With this select and
+// the pairwise block_minmax both kernels compile to the parent's instruction stream.
+using MixedQuant = GroupQuant<true>;
+template <typename T> __device__ __forceinline__ T fake_value(T x, const MixedQuant& q, float qmin, float qmax) {
     const float f = to_f32<T>(x);
-    const float c = q.fz ? quant_code_fz(f, q.dv, q.z, DT, DT, qmin, qmax) : quant_code(f, q.dv, q.z, DT, DT, qmin, qmax);
-    return from_f32<T>(dequant_code(c, q.s, q.z, DT));
-}
-
-// min / max over the workgroup. fminf / fmaxf drop NaNs whatever the order, and the sign of a zero minimum or maximum does not
-// reach the qparams (|.| in the symmetric branch; mx - mn and qmin - round(mn / s) in the other), so the order is free.
-__device__ __forceinline__ void block_minmax(float* red, float& mn, float& mx) {
-    mn = wave_min(mn, 64);
-    mx = wave_max(mx, 64);
-    __syncthreads();                       // the previous round's readers are done
-    if ((threadIdx.x & 63) == 0) {
-        red[threadIdx.x >> 6] = mn;
-        red[MB / 64 + (threadIdx.x >> 6)] = mx;
-    }
-    __syncthreads();
-    mn = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
-    mx = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
+    const float c = q.fz ? quant_code_fz(f, q.dv, q.z, q.p1, q.p2, qmin, qmax) : quant_code(f, q.dv, q.z, q.p1, q.p2, qmin, qmax);
+    return from_f32<T>(dequant_code(c, q.s, q.z, q.p2));
 }
 
 // X and out may be the same buffer: a workgroup reads its rows completely before it writes them, and no other reads them.
@@ -131,9 +80,9 @@ __global__ __launch_bounds__(MB) void k_mixed_mask(const T* X, int64_t N, int K,
     T* lp = rows + (size_t)team * K;
     float mn = INFINITY, mx = -INFINITY;
     for (int c = tl * V; c < K; c += ts * V) {
-        const MVec<T, V> v = mload<T, V>(xp + c);
+        const Vec<T, V> v = load_vec<T, V>(xp + c);
         const RoleVec<V> r = load_role<V>(role + c);
-        mstore<T, V>(lp + c, v);
+        store_vec<T, V>(lp + c, v);
 #pragma unroll
         for (int i = 0; i < V; ++i) {
             if (r.r[i] & 1) {
@@ -147,19 +96,19 @@ __global__ __launch_bounds__(MB) void k_mixed_mask(const T* X, int64_t N, int K,
         mn = wave_min(mn, ts);
         mx = wave_max(mx, ts);
     } else {
-        block_minmax(red, mn, mx);
+        block_minmax<MB, true>(red, mn, mx);
     }
     if (!valid) return;
-    const GroupQ q = group_q<DT>(mn, mx, sym, round_zp, qmin, qmax);
+    const MixedQuant q = MixedQuant::from_minmax(mn, mx, DT, sym, round_zp, qmin, qmax);
     T* op = out + rr * K;
     for (int c = tl * V; c < K; c += ts * V) {
-        const MVec<T, V> v = mload<T, V>(lp + c);
+        const Vec<T, V> v = load_vec<T, V>(lp + c);
         const RoleVec<V> r = load_role<V>(role + c);
-        MVec<T, V> o;
+        Vec<T, V> o;
 #pragma unroll
         for (int i = 0; i < V; ++i)
             o.v[i] = r.r[i] == 1 ? fake_value<T>(v.v[i], q, qmin, qmax) : (r.r[i] == 0 ? zero_of<T>() : v.v[i]);
-        mstore<T, V>(op + c, o);
+        store_vec<T, V>(op + c, o);
     }
 }
 
@@ -176,12 +125,12 @@ __global__ __launch_bounds__(MB) void k_mixed_idx(const T* X, int64_t N, int K, 
     const int64_t base = row0 * K;
     const int total = nr * K;                 // the workgroup's rows are one contiguous piece; V divides K
     for (int e = threadIdx.x * V; e < total; e += MB * V) {
-        MVec<T, V> v = mload<T, V>(X + base + e);
+        Vec<T, V> v = load_vec<T, V>(X + base + e);
         const RoleVec<V> r = load_role<V>(role + e % K);
 #pragma unroll
         for (int i = 0; i < V; ++i)
             if (r.r[i] == 0) v.v[i] = zero_of<T>();
-        mstore<T, V>(rows + e, v);
+        store_vec<T, V>(rows + e, v);
     }
     __syncthreads();
     const int items = nr * ng;                // (row, group) pairs of this workgroup
@@ -205,7 +154,7 @@ __global__ __launch_bounds__(MB) void k_mixed_idx(const T* X, int64_t N, int K, 
             mn = wave_min(mn, lpr);
             mx = wave_max(mx, lpr);
             if (!valid) continue;
-            const GroupQ q = group_q<DT>(mn, mx, sym, round_zp, qmin, qmax);
+            const MixedQuant q = MixedQuant::from_minmax(mn, mx, DT, sym, round_zp, qmin, qmax);
             for (int e = sl; e < g; e += lpr) {
                 const int col = ip[e];
                 if ((unsigned)col >= (unsigned)K) continue;
@@ -225,8 +174,8 @@ __global__ __launch_bounds__(MB) void k_mixed_idx(const T* X, int64_t N, int K, 
                 mn = fminf(mn, f);
                 mx = fmaxf(mx, f);
             }
-            block_minmax(red, mn, mx);
-            const GroupQ q = group_q<DT>(mn, mx, sym, round_zp, qmin, qmax);
+            block_minmax<MB, true>(red, mn, mx);
+            const MixedQuant q = MixedQuant::from_minmax(mn, mx, DT, sym, round_zp, qmin, qmax);
             for (int e = threadIdx.x; e < g; e += MB) {
                 const int col = ip[e];
                 if ((unsigned)col >= (unsigned)K) continue;
@@ -235,7 +184,7 @@ __global__ __launch_bounds__(MB) void k_mixed_idx(const T* X, int64_t N, int K, 
         }
     }
     __syncthreads();
-    for (int e = threadIdx.x * V; e < total; e += MB * V) mstore<T, V>(out + base + e, mload<T, V>(rows + e));
+    for (int e = threadIdx.x * V; e < total; e += MB * V) store_vec<T, V>(out + base + e, load_vec<T, V>(rows + e));
 }
 
 static inline bool mq_aligned(const void* p, int a) { return ((uintptr_t)p & (uintptr_t)(a - 1)) == 0; }

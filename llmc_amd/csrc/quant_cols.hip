@@ -5,11 +5,12 @@
 // Layout: lanes walk columns. A lane owns VEC = 16 B of consecutive columns; 16 lanes cover a 256-B row segment, so one load
 // instruction of a wave reads four such segments (four consecutive rows of the strip) and a workgroup of four waves sixteen rows.
 // Min / max are kept per lane per column and never cross columns: two shuffle steps fold the wave's four rows, LDS folds the waves.
-// No transposed copy, no LDS transpose, no atomics. The scalar arithmetic is quant_math.h's, the one quant_rows runs.
+// No transposed copy, no LDS transpose, no atomics. The group step is quant_group.h's GroupQuant, the one k_quant_static runs.
 //   tile   (g <= kTileMaxG) one workgroup per (group row, strip): min/max down the g rows, then the tile again (L2) for the store
 //   slab   (g >  kTileMaxG) rows cut into slabs of kSlab: k_cols_partial -> ws, k_cols_fold per column, k_cols_apply quantizes
 // Both exist with VEC = 1 for operands that do not allow 16-byte vectors.
 #include "common.h"
+#include "quant_group.h"
 #include "quant_math.h"
 
 namespace llmc {
@@ -27,28 +28,6 @@ static constexpr int kMaxGrid = 256 * 32;
 __host__ __device__ static inline int64_t cols_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 enum { PATH_TILE = 0, PATH_SLAB = 1, PATH_SCALAR = 2, PATH_COUNT = 3 };
-
-template <typename T, int VEC> struct ColVec {
-    T v[VEC];
-};
-template <typename T, int VEC>
-__device__ __forceinline__ ColVec<T, VEC> load_cols(const T* p) {
-    ColVec<T, VEC> r;
-    if constexpr (VEC * sizeof(T) == 16) {
-        uint4 raw = *reinterpret_cast<const uint4*>(p);
-        __builtin_memcpy(&r, &raw, 16);
-    } else {
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) r.v[i] = p[i];
-    }
-    return r;
-}
-
-template <int KIND, typename T> struct cols_out;
-template <typename T> struct cols_out<LLMC_OUT_FAKE, T> { using type = T; };
-template <typename T> struct cols_out<LLMC_OUT_I32, T> { using type = int32_t; };
-template <typename T> struct cols_out<LLMC_OUT_I8, T> { using type = int8_t; };
-template <typename T> struct cols_out<LLMC_OUT_U8, T> { using type = uint8_t; };
 
 // where a thread stands in the strip: its wave, the row of the wave's load it reads, its first column
 struct Lane {
@@ -73,13 +52,13 @@ __device__ __forceinline__ void lane_minmax(const T* __restrict__ W, int64_t ld,
     }
     if (!col_ok) return;
     for (int64_t r = r0 + l.wave * kRowsPerLoad + l.sub; r < r1; r += (int64_t)kRowsPerPass * kUnr) {
-        ColVec<T, VEC> v[kUnr];
+        Vec<T, VEC> v[kUnr];
         bool ok[kUnr];
 #pragma unroll
         for (int u = 0; u < kUnr; ++u) {
             const int64_t rr = r + (int64_t)u * kRowsPerPass;
             ok[u] = rr < r1;
-            if (ok[u]) v[u] = load_cols<T, VEC>(W + rr * ld + c);
+            if (ok[u]) v[u] = load_vec<T, VEC>(W + rr * ld + c);
         }
 #pragma unroll
         for (int u = 0; u < kUnr; ++u) {
@@ -127,63 +106,38 @@ __device__ __forceinline__ void block_fold(float (&mn)[VEC], float (&mx)[VEC], c
     }
 }
 
-// quantize rows [r0, r1) of this lane's VEC columns from their groups' min / max and store fake values or codes.
-// round_zp = 0 is quant_static's LLMC_FRACTIONAL_ZP arithmetic: divisor of the clamped scale, zero point added before the rounding.
+// quantize rows [r0, r1) of this lane's VEC columns from their groups' min / max and store fake values or codes. A group takes
+// either branch of round_zp at run time (GroupQuant<true>): round_zp = 0 is quant_static's LLMC_FRACTIONAL_ZP arithmetic.
 template <typename T, int VEC, int KIND>
 __device__ __forceinline__ void lane_quant(const T* __restrict__ W, int64_t ld, int64_t K, int64_t r0, int64_t r1, int64_t c,
                                            const Lane& l, const float (&mn)[VEC], const float (&mx)[VEC], int sym, int round_zp,
                                            float qmin, float qmax, void* __restrict__ out) {
-    constexpr int DT = dt_of<T>::value;
-    using O = typename cols_out<KIND, T>::type;
-    QParams q[VEC];
-    Divisor dv[VEC];
+    using O = typename out_elem<KIND, T>::type;
+    GroupQuant<true> q[VEC];
 #pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-        q[k] = qparams_from_minmax(mn[k], mx[k], DT, sym, round_zp, qmin, qmax);
-        const float sdiv = round_zp ? q[k].s : fmaxf(q[k].s, rnd(1e-9f, DT));
-        dv[k] = make_divisor(sdiv, fmaxf(fabsf(mn[k]), fabsf(mx[k])));
-    }
+    for (int k = 0; k < VEC; ++k)
+        q[k] = GroupQuant<true>::from_minmax(mn[k], mx[k], dt_of<T>::value, sym, round_zp, qmin, qmax);
     for (int64_t r = r0 + l.wave * kRowsPerLoad + l.sub; r < r1; r += (int64_t)kRowsPerPass * kUnr) {
-        ColVec<T, VEC> v[kUnr];
+        Vec<T, VEC> v[kUnr];
         bool ok[kUnr];
 #pragma unroll
         for (int u = 0; u < kUnr; ++u) {
             const int64_t rr = r + (int64_t)u * kRowsPerPass;
             ok[u] = rr < r1;
-            if (ok[u]) v[u] = load_cols<T, VEC>(W + rr * ld + c);
+            if (ok[u]) v[u] = load_vec<T, VEC>(W + rr * ld + c);
         }
 #pragma unroll
         for (int u = 0; u < kUnr; ++u) {
             if (!ok[u]) continue;
             const int64_t rr = r + (int64_t)u * kRowsPerPass;
-            ColVec<O, VEC> o;
+            Vec<O, VEC> o;
 #pragma unroll
-            for (int k = 0; k < VEC; ++k) {
+            for (int k = 0; k < VEC; ++k) {        // one group per column: quant_vec's step with a quantizer per element
                 const float x = to_f32<T>(v[u].v[k]);
-                const float code = round_zp ? quant_code(x, dv[k], q[k].z, DT, DT, qmin, qmax)
-                                            : quant_code_fz(x, dv[k], q[k].z, DT, DT, qmin, qmax);
-                if constexpr (KIND == LLMC_OUT_FAKE) o.v[k] = from_f32<T>(dequant_code(code, q[k].s, q[k].z, DT));
-                else o.v[k] = (O)code;
+                if constexpr (KIND == LLMC_OUT_FAKE) o.v[k] = from_f32<T>(q[k].fake(x, qmin, qmax));
+                else o.v[k] = (O)q[k].code(x, qmin, qmax);
             }
-            O* op = (O*)out + rr * K + c;
-            if constexpr (VEC * sizeof(O) == 16) {
-                uint4 raw;
-                __builtin_memcpy(&raw, &o, 16);
-                *reinterpret_cast<uint4*>(op) = raw;
-            } else if constexpr (VEC * sizeof(O) == 32) {
-                uint4 lo, hi;
-                __builtin_memcpy(&lo, &o.v[0], 16);
-                __builtin_memcpy(&hi, &o.v[VEC / 2], 16);
-                reinterpret_cast<uint4*>(op)[0] = lo;
-                reinterpret_cast<uint4*>(op)[1] = hi;
-            } else if constexpr (VEC * sizeof(O) == 8) {
-                uint2 raw;
-                __builtin_memcpy(&raw, &o, 8);
-                *reinterpret_cast<uint2*>(op) = raw;
-            } else {
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) op[k] = o.v[k];
-            }
+            store_vec_wide<O, VEC>((O*)out + rr * K + c, o);     // llmc_quant_dynamic_cols requires a 16-B aligned `out`
         }
     }
 }
@@ -342,12 +296,9 @@ static int cols_tk(bool vec, const void* W, int64_t R, int64_t K, int64_t ld, in
 template <typename T>
 static int cols_t(bool vec, int kind, const void* W, int64_t R, int64_t K, int64_t ld, int64_t g, int sym, int round_zp,
                   float qmin, float qmax, void* out, void* scales, void* zeros, void* ws, hipStream_t st) {
-    switch (kind) {
-        case LLMC_OUT_FAKE: return cols_tk<T, LLMC_OUT_FAKE>(vec, W, R, K, ld, g, sym, round_zp, qmin, qmax, out, scales, zeros, ws, st);
-        case LLMC_OUT_I32: return cols_tk<T, LLMC_OUT_I32>(vec, W, R, K, ld, g, sym, round_zp, qmin, qmax, out, scales, zeros, ws, st);
-        case LLMC_OUT_I8: return cols_tk<T, LLMC_OUT_I8>(vec, W, R, K, ld, g, sym, round_zp, qmin, qmax, out, scales, zeros, ws, st);
-        default: return cols_tk<T, LLMC_OUT_U8>(vec, W, R, K, ld, g, sym, round_zp, qmin, qmax, out, scales, zeros, ws, st);
-    }
+    DISPATCH_OUT_KIND(kind, return cols_tk<T, KIND>(vec, W, R, K, ld, g, sym, round_zp, qmin, qmax, out, scales, zeros, ws, st));
+    set_last_error_msg("quant_dynamic_cols: bad out_kind");
+    return LLMC_EINVAL;
 }
 
 }  // namespace llmc

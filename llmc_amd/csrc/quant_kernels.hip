@@ -6,6 +6,7 @@
 // Row kernels: quant_rows behind k_quant_rows* (any g; qparams only, fake values or codes, optionally a column multiplier) and
 // k_quant_dynamic_small (g = LPR * 16 B exactly); launch_quant_rows is the one place that chooses between them.
 #include "common.h"
+#include "quant_group.h"
 #include "quant_math.h"
 
 namespace llmc {
@@ -13,67 +14,12 @@ namespace llmc {
 static constexpr int kBlock = 256;
 static constexpr int kMaxGrid = 256 * 8;
 
-template <typename T, int VEC> struct RowVec {
-    T v[VEC];
-};
-
-template <typename T, int VEC>
-__device__ __forceinline__ RowVec<T, VEC> load_vec(const T* p) {
-    RowVec<T, VEC> r;
-    if constexpr (VEC * sizeof(T) == 16) {
-        uint4 raw = *reinterpret_cast<const uint4*>(p);
-        __builtin_memcpy(&r, &raw, 16);
-    } else {
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) r.v[i] = p[i];
-    }
-    return r;
-}
-template <typename T, int VEC>
-__device__ __forceinline__ void store_vec(T* p, const RowVec<T, VEC>& r) {
-    if constexpr (VEC * sizeof(T) == 16) {
-        uint4 raw;
-        __builtin_memcpy(&raw, &r, 16);
-        *reinterpret_cast<uint4*>(p) = raw;
-    } else {
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) p[i] = r.v[i];
-    }
-}
-
-// what a kernel of output kind KIND writes per element: fake values in the tensor dtype, or codes in KIND's container
-template <int KIND, typename T> struct out_elem;
-template <typename T> struct out_elem<LLMC_OUT_FAKE, T> { using type = T; };
-template <typename T> struct out_elem<LLMC_OUT_I32, T> { using type = int32_t; };
-template <typename T> struct out_elem<LLMC_OUT_I8, T> { using type = int8_t; };
-template <typename T> struct out_elem<LLMC_OUT_U8, T> { using type = uint8_t; };
-
-// One vector of a group through quant (and dequant for LLMC_OUT_FAKE): fake values of T or codes in KIND's container.
-// dv divides by the scale; s, z, p2 are dequant's. FZ is k_quant_static's variant: where its run-time fz is set, dv is the
-// divisor of the clamped scale and the zero point is added before the rounding (quant_code_fz).
-template <int KIND, bool FZ = false, typename T, int VEC>
-__device__ __forceinline__ void quant_vec(RowVec<typename out_elem<KIND, T>::type, VEC>& o, const RowVec<T, VEC>& v,
-                                          const Divisor& dv, float s, float z, int p1, int p2, float qmin, float qmax,
-                                          bool fz = false) {
-    using O = typename out_elem<KIND, T>::type;
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-        float q;
-        if constexpr (FZ)
-            q = fz ? quant_code_fz(to_f32<T>(v.v[k]), dv, z, p1, p2, qmin, qmax)
-                   : quant_code(to_f32<T>(v.v[k]), dv, z, p1, p2, qmin, qmax);
-        else
-            q = quant_code(to_f32<T>(v.v[k]), dv, z, p1, p2, qmin, qmax);
-        if constexpr (KIND == LLMC_OUT_FAKE) o.v[k] = from_f32<T>(dequant_code(q, s, z, p2));
-        else o.v[k] = (O)q;
-    }
-}
 // k_quant_static / quant_rows: fake values as store_vec writes them. Codes are written element by element in source, because
 // the hosts' vec_ok asks for a 16-B aligned `out` only where fake values go; the compiler is free to merge neighbouring element
 // stores of the vector into wider ones that need the element's alignment only (gfx950 global stores are unaligned-capable), and
 // it does: that is intended, k_quant_static has always been compiled this way.
 template <int KIND, typename O, int VEC>
-__device__ __forceinline__ void store_out(void* out, int64_t i, const RowVec<O, VEC>& o) {
+__device__ __forceinline__ void store_out(void* out, int64_t i, const Vec<O, VEC>& o) {
     O* op = (O*)out + i;
     if constexpr (KIND == LLMC_OUT_FAKE) {
         store_vec<O, VEC>(op, o);
@@ -82,39 +28,16 @@ __device__ __forceinline__ void store_out(void* out, int64_t i, const RowVec<O, 
         for (int k = 0; k < VEC; ++k) op[k] = o.v[k];
     }
 }
-// k_quant_dynamic_small (its launch condition guarantees a 16-B aligned `out`): 32 / 16 / 8-byte stores
-template <typename O, int VEC>
-__device__ __forceinline__ void store_vec_aligned(O* op, const RowVec<O, VEC>& o) {
-    if constexpr (sizeof(O) * VEC == 32) {
-        uint4 lo, hi;
-        __builtin_memcpy(&lo, &o.v[0], 16);
-        __builtin_memcpy(&hi, &o.v[VEC / 2], 16);
-        reinterpret_cast<uint4*>(op)[0] = lo;
-        reinterpret_cast<uint4*>(op)[1] = hi;
-    } else if constexpr (sizeof(O) * VEC == 16) {
-        uint4 lo;
-        __builtin_memcpy(&lo, &o.v[0], 16);
-        reinterpret_cast<uint4*>(op)[0] = lo;
-    } else if constexpr (sizeof(O) * VEC == 8) {
-        uint2 lo;
-        __builtin_memcpy(&lo, &o.v[0], 8);
-        reinterpret_cast<uint2*>(op)[0] = lo;
-    } else {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) op[k] = o.v[k];
-    }
-}
-
 // --------------------------------------------------------------------------------------------
 // row scan: min/max of one row by LPR lanes
 // --------------------------------------------------------------------------------------------
 // one vector of the row at column c; SCALE: times the column multiplier, w' = rnd(w * cs[col]) in the tensor dtype (from_f32
 // is that one rounding)
 template <typename T, int VEC, bool SCALE>
-__device__ __forceinline__ RowVec<T, VEC> load_row_vec(const T* row, const T* cs, int c) {
-    RowVec<T, VEC> v = load_vec<T, VEC>(row + c);
+__device__ __forceinline__ Vec<T, VEC> load_row_vec(const T* row, const T* cs, int c) {
+    Vec<T, VEC> v = load_vec<T, VEC>(row + c);
     if constexpr (SCALE) {
-        const RowVec<T, VEC> sv = load_vec<T, VEC>(cs + c);
+        const Vec<T, VEC> sv = load_vec<T, VEC>(cs + c);
 #pragma unroll
         for (int i = 0; i < VEC; ++i)
             v.v[i] = from_f32<T>(to_f32<T>(v.v[i]) * to_f32<T>(sv.v[i]));
@@ -124,12 +47,12 @@ __device__ __forceinline__ RowVec<T, VEC> load_row_vec(const T* row, const T* cs
 // KEEP_FIRST: `first` receives this lane's first vector, if the lane owns one (sl * VEC < g)
 template <typename T, int VEC, bool SCALE, bool KEEP_FIRST>
 __device__ __forceinline__ void row_minmax(const T* row, const T* cs, int g, int sl, int lpr, float& mn, float& mx,
-                                           RowVec<T, VEC>& first) {
+                                           Vec<T, VEC>& first) {
     mn = INFINITY;
     mx = -INFINITY;
     bool have_first = false;
     for (int c = sl * VEC; c < g; c += lpr * VEC) {
-        RowVec<T, VEC> v = load_row_vec<T, VEC, SCALE>(row, cs, c);
+        Vec<T, VEC> v = load_row_vec<T, VEC, SCALE>(row, cs, c);
         if constexpr (KEEP_FIRST) {
             if (!have_first) {
                 first = v;
@@ -173,26 +96,29 @@ __device__ __forceinline__ void quant_rows(const T* __restrict__ W, const T* __r
         const T* rp = W + rr * g;
         const T* cp = SCALE ? cs + (rr % gpr) * g : nullptr;
         float mn, mx;
-        RowVec<T, VEC> first;
+        Vec<T, VEC> first;
         row_minmax<T, VEC, SCALE, KIND != OUT_NONE>(rp, cp, g, sl, lpr, mn, mx, first);
         const bool lead = valid && sl == 0;         // the lane that stores the row's qparams
         if (KIND == OUT_NONE && !lead) continue;    // qparams only: no other lane needs them
-        const QParams q = qparams_from_minmax(mn, mx, DT, sym, SCALE ? 1 : round_zp, qmin, qmax);
+        const QParams qp = qparams_from_minmax(mn, mx, DT, sym, SCALE ? 1 : round_zp, qmin, qmax);
         if constexpr (!SCALE) {                     // SCALE serves llmc_awq_scale_fakequant: no qparams out, round_zp = 1
             if (lead) {
-                if (KIND == OUT_NONE || scales) scales[row] = from_f32<T>(q.s);     // llmc_minmax_qparams requires scales
-                if (zeros) zeros[row] = from_f32<T>(q.z);
+                if (KIND == OUT_NONE || scales) scales[row] = from_f32<T>(qp.s);    // llmc_minmax_qparams requires scales
+                if (zeros) zeros[row] = from_f32<T>(qp.z);
             }
         }
         if constexpr (KIND != OUT_NONE) {
             if (!valid) continue;
-            const Divisor dv = make_divisor(q.s, fmaxf(fabsf(mn), fabsf(mx)));
+            // The scalar statement, not a GroupQuant: with one in this loop two instantiations measured slower than the parent's
+            // (scalar bf16 +2.5 %, scaled f16 +0.3 %; profiles/quant_group_refactor.txt). No fractional-zero-point arm:
+            // llmc_quant_dynamic refuses round_zp = 0, only the qparams above take it.
+            const Divisor dv = make_divisor(qp.s, fmaxf(fabsf(mn), fabsf(mx)));
             bool use_first = true;
             for (int c = sl * VEC; c < g; c += lpr * VEC) {
-                const RowVec<T, VEC> v = use_first ? first : load_row_vec<T, VEC, SCALE>(rp, cp, c);
+                const Vec<T, VEC> v = use_first ? first : load_row_vec<T, VEC, SCALE>(rp, cp, c);
                 use_first = false;
-                RowVec<typename out_elem<KIND, T>::type, VEC> o;
-                quant_vec<KIND>(o, v, dv, q.s, q.z, DT, DT, qmin, qmax);
+                Vec<typename out_elem<KIND, T>::type, VEC> o;
+                quant_vec<KIND>(o, v, dv, qp.s, qp.z, DT, DT, qmin, qmax);
                 store_out<KIND>(out, rr * g + c, o);
             }
         }
@@ -226,14 +152,14 @@ static constexpr int kChunk = 8192;
 template <typename T, int VEC>
 __global__ __launch_bounds__(kBlock) void k_minmax_partial(const T* __restrict__ W, int64_t G, int64_t g,
                                                            int64_t nch, float2* __restrict__ part) {
-    __shared__ float smn[kBlock / 64], smx[kBlock / 64];
+    __shared__ float red[2 * (kBlock / 64)];
     for (int64_t u = blockIdx.x; u < G * nch; u += gridDim.x) {
         int64_t row = u / nch, ch = u % nch;
         int64_t c0 = ch * kChunk, c1 = c0 + kChunk < g ? c0 + kChunk : g;
         const T* p = W + row * g;
         float mn = INFINITY, mx = -INFINITY;
         for (int64_t c = c0 + (int64_t)threadIdx.x * VEC; c < c1; c += (int64_t)kBlock * VEC) {
-            RowVec<T, VEC> v = load_vec<T, VEC>(p + c);
+            Vec<T, VEC> v = load_vec<T, VEC>(p + c);
 #pragma unroll
             for (int i = 0; i < VEC; ++i) {
                 float f = to_f32<T>(v.v[i]);
@@ -241,48 +167,26 @@ __global__ __launch_bounds__(kBlock) void k_minmax_partial(const T* __restrict__
                 mx = fmaxf(mx, f);
             }
         }
-        mn = wave_min(mn, 64);
-        mx = wave_max(mx, 64);
-        if ((threadIdx.x & 63) == 0) {
-            smn[threadIdx.x >> 6] = mn;
-            smx[threadIdx.x >> 6] = mx;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int i = 1; i < kBlock / 64; ++i) {
-                mn = fminf(mn, smn[i]);
-                mx = fmaxf(mx, smx[i]);
-            }
-            part[u] = make_float2(mn, mx);
-        }
-        __syncthreads();
+        block_minmax<kBlock>(red, mn, mx);
+        if (threadIdx.x == 0) part[u] = make_float2(mn, mx);
     }
 }
+static constexpr int kFinalBlock = 1024;     // threads of k_minmax_final: its stride, its LDS words and its launch
 template <typename T>
 __global__ void k_minmax_final(const float2* __restrict__ part, int64_t G, int64_t nch, int sym,
                                int round_zp, float qmin, float qmax, T* __restrict__ scales,
                                T* __restrict__ zeros) {
     constexpr int DT = dt_of<T>::value;
-    __shared__ float smn[16], smx[16];
+    __shared__ float red[2 * (kFinalBlock / 64)];
     int64_t row = blockIdx.x;
     float mn = INFINITY, mx = -INFINITY;
-    for (int64_t c = threadIdx.x; c < nch; c += 1024) {
+    for (int64_t c = threadIdx.x; c < nch; c += kFinalBlock) {
         float2 p = part[row * nch + c];
         mn = fminf(mn, p.x);
         mx = fmaxf(mx, p.y);
     }
-    mn = wave_min(mn, 64);
-    mx = wave_max(mx, 64);
-    if ((threadIdx.x & 63) == 0) {
-        smn[threadIdx.x >> 6] = mn;
-        smx[threadIdx.x >> 6] = mx;
-    }
-    __syncthreads();
+    block_minmax<kFinalBlock>(red, mn, mx);
     if (threadIdx.x == 0) {
-        for (int i = 1; i < 16; ++i) {
-            mn = fminf(mn, smn[i]);
-            mx = fmaxf(mx, smx[i]);
-        }
         QParams q = qparams_from_minmax(mn, mx, DT, sym, round_zp, qmin, qmax);
         scales[row] = from_f32<T>(q.s);
         if (zeros) zeros[row] = from_f32<T>(q.z);
@@ -296,11 +200,7 @@ __global__ __launch_bounds__(kBlock) void k_quant_static(const T* __restrict__ W
                                                          const void* __restrict__ zeros, int zdt,
                                                          float qmin, float qmax, void* __restrict__ out) {
     constexpr int WDT = dt_of<T>::value;
-    // LLMC_SCALAR_QPARAM: a 0-dim operand keeps its own precision but does not take part in type promotion
     const int sd = sdt & 3, zd = zdt & 3;
-    const bool fz = (zdt & LLMC_FRACTIONAL_ZP) != 0;
-    const int p1 = (sdt & LLMC_SCALAR_QPARAM) ? WDT : promote(WDT, sd);
-    const int p2 = (zeros && !(zdt & LLMC_SCALAR_QPARAM)) ? promote(p1, zd) : p1;
     const int64_t nvec_row = g / VEC;
     const int64_t total = G * nvec_row;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total;
@@ -309,15 +209,13 @@ __global__ __launch_bounds__(kBlock) void k_quant_static(const T* __restrict__ W
         int64_t c = (i - row * nvec_row) * VEC;
         float s = load_as_f32(scales, row, sd);
         float z = zeros ? load_as_f32(zeros, row, zd) : 0.0f;
-        RowVec<T, VEC> v = load_vec<T, VEC>(W + row * g + c);
+        Vec<T, VEC> v = load_vec<T, VEC>(W + row * g + c);
         float am = 0.0f;   // bound of |x| over this thread's elements for the hoisted divisor (quant_math.h)
 #pragma unroll
         for (int k = 0; k < VEC; ++k) am = fmaxf(am, fabsf(to_f32<T>(v.v[k])));
-        // LLMC_FRACTIONAL_ZP (round_zp=False, quant.py:702-707): the divisor is s.clamp_min(1e-9) in the scale's dtype
-        const float sdiv = fz ? fmaxf(s, rnd(1e-9f, sd)) : s;
-        const Divisor dv = make_divisor(sdiv, am);
-        RowVec<typename out_elem<KIND, T>::type, VEC> o;
-        quant_vec<KIND, true>(o, v, dv, s, z, p1, p2, qmin, qmax, fz);
+        const GroupQuant<true> q = GroupQuant<true>::from_qparams(s, z, zeros != nullptr, WDT, sdt, zdt, am);
+        Vec<typename out_elem<KIND, T>::type, VEC> o;
+        quant_vec<KIND>(o, v, q, qmin, qmax);
         store_out<KIND>(out, row * g + c, o);
     }
 }
@@ -339,7 +237,7 @@ __global__ __launch_bounds__(kBlock) void k_quant_dynamic_small(const T* __restr
     const int64_t wave = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
     const int64_t nwaves = (int64_t)gridDim.x * (kBlock / 64);
     for (int64_t r0 = wave * rpw * UNR; r0 < G; r0 += nwaves * rpw * UNR) {
-        RowVec<T, VEC> v[UNR];
+        Vec<T, VEC> v[UNR];
         bool valid[UNR];
         int64_t rows[UNR];
 #pragma unroll
@@ -352,7 +250,7 @@ __global__ __launch_bounds__(kBlock) void k_quant_dynamic_small(const T* __restr
         if (SCALE) {
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
-                RowVec<T, VEC> sv = load_vec<T, VEC>(cs + (rows[u] % gpr) * g + sl * VEC);
+                Vec<T, VEC> sv = load_vec<T, VEC>(cs + (rows[u] % gpr) * g + sl * VEC);
 #pragma unroll
                 for (int i = 0; i < VEC; ++i)
                     v[u].v[i] = from_f32<T>(rndc<DT>(to_f32<T>(v[u].v[i]) * to_f32<T>(sv.v[i])));
@@ -369,17 +267,16 @@ __global__ __launch_bounds__(kBlock) void k_quant_dynamic_small(const T* __restr
             }
             mn = wave_min(mn, lpr);
             mx = wave_max(mx, lpr);
-            const QParams q = qparams_from_minmax(mn, mx, DT, sym, round_zp, qmin, qmax);
+            const GroupQuant<> q = GroupQuant<>::from_minmax(mn, mx, DT, sym, round_zp, qmin, qmax);
             if (valid[u] && sl == 0) {
                 if (scales) scales[rows[u]] = from_f32<T>(q.s);
                 if (zeros) zeros[rows[u]] = from_f32<T>(q.z);
             }
             if (!valid[u] || out == nullptr) continue;
-            const Divisor dv = make_divisor(q.s, fmaxf(fabsf(mn), fabsf(mx)));
             using O = typename out_elem<KIND, T>::type;
-            RowVec<O, VEC> o;
-            quant_vec<KIND>(o, v[u], dv, q.s, q.z, DT, DT, qmin, qmax);
-            store_vec_aligned<O, VEC>((O*)out + rows[u] * g + sl * VEC, o);
+            Vec<O, VEC> o;
+            quant_vec<KIND>(o, v[u], q, qmin, qmax);
+            store_vec_wide<O, VEC>((O*)out + rows[u] * g + sl * VEC, o);   // the launch condition guarantees a 16-B aligned `out`
         }
     }
 }
@@ -541,7 +438,7 @@ static int minmax_two_stage_t(const void* W, int64_t G, int64_t g, int sym, int 
         hipLaunchKernelGGL((k_minmax_partial<T, 1>), dim3(grid), dim3(kBlock), 0, st, (const T*)W, G, g, nch,
                            (float2*)ws);
     LLMC_LAUNCH_CHECK();
-    hipLaunchKernelGGL((k_minmax_final<T>), dim3((unsigned)G), dim3(1024), 0, st, (const float2*)ws, G, nch, sym,
+    hipLaunchKernelGGL((k_minmax_final<T>), dim3((unsigned)G), dim3(kFinalBlock), 0, st, (const float2*)ws, G, nch, sym,
                        round_zp, qmin, qmax, (T*)scales, (T*)zeros);
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;
@@ -714,15 +611,6 @@ static int quant_static_tk(const void* W, int64_t G, int64_t g, const void* scal
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;
 }
-// out_kind -> KIND as a compile-time constant for the statement(s); an unknown kind runs nothing
-#define DISPATCH_OUT_KIND(kind, ...)                                                     \
-    switch (kind) {                                                                      \
-        case LLMC_OUT_FAKE: { constexpr int KIND = LLMC_OUT_FAKE; __VA_ARGS__; break; }  \
-        case LLMC_OUT_I32: { constexpr int KIND = LLMC_OUT_I32; __VA_ARGS__; break; }    \
-        case LLMC_OUT_I8: { constexpr int KIND = LLMC_OUT_I8; __VA_ARGS__; break; }      \
-        case LLMC_OUT_U8: { constexpr int KIND = LLMC_OUT_U8; __VA_ARGS__; break; }      \
-    }
-
 template <typename T>
 static int quant_static_t(const void* W, int64_t G, int64_t g, const void* scales, int sdt,
                           const void* zeros, int zdt, float qmin, float qmax, int kind, void* out,

@@ -1,6 +1,11 @@
 // quant_math.h — the scalar arithmetic of llmc's IntegerQuantizer, stated once for every kernel.
 // Mirrors llmc/compression/quantization/quant.py:545-559 (get_qparams) and :699-717 (quant/dequant);
 // oracle/quant_ref.py restates the same chain in numpy and is pinned to the reference by tests/golden.
+// Scalar ops only. What a kernel builds from them for one quantization group is quant_group.h's.
+// Users: through quant_group.h the row, static, column, mixed and OS+ kernels (listed there); directly, inside chains of their
+// own, store_qparams (quant_cols.hip), the qparams of quant_rows and k_minmax_final and mse_search_row (quant_kernels.hip), the
+// FP8 arm of k_osplus_act_step (smooth_osplus.hip), awq_clip.hip, gptq_block_kernels.h / gptq_block_body.h (and spqr_loop.hip
+// through them), hqq.hip, and fp8_block.hip (rcp_refined / div_tail).
 #pragma once
 #include "common.h"
 

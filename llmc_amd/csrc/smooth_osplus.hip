@@ -10,6 +10,7 @@
 #include "common.h"
 #include "float_quant_math.h"
 #include "fp8_math.h"
+#include "quant_group.h"
 #include "quant_math.h"
 #include "vec_powf.h"
 
@@ -186,62 +187,41 @@ __global__ __launch_bounds__(SB) void k_osplus_act_step(const T* __restrict__ X,
                                                         int sym, float qmin, float qmax, int mode, T* __restrict__ out) {
     constexpr int DT = dt_of<T>::value;
     constexpr int V = 16 / sizeof(T);
-    __shared__ float smn[SB / 64], smx[SB / 64];
+    __shared__ float red[2 * (SB / 64)];
     const int nv = K / V;
     for (int64_t row = blockIdx.x; row < N; row += gridDim.x) {
         const T* xp = X + row * K;
-        uint4 q[MAXV];
+        uint4 q[MAXV];            // the quotients wait as packed 16-byte words: the FP8 arm selects among them by value
         float mn = INFINITY, mx = -INFINITY;
 #pragma unroll
         for (int j = 0; j < MAXV; ++j) {
             const int vi = j * SB + threadIdx.x;
             if (vi < nv) {
-                const uint4 rx = *reinterpret_cast<const uint4*>(xp + vi * V);
-                const uint4 rs = *reinterpret_cast<const uint4*>(s + vi * V);
-                T xv[V], sv[V], ov[V];
-                __builtin_memcpy(xv, &rx, 16);
-                __builtin_memcpy(sv, &rs, 16);
+                const Vec<T, V> xv = load_vec<T, V>(xp + vi * V), sv = load_vec<T, V>(s + vi * V);
+                Vec<T, V> ov;
 #pragma unroll
                 for (int k = 0; k < V; ++k) {
-                    const float f = rndc<DT>(to_f32<T>(xv[k]) / to_f32<T>(sv[k]));     // llmc_div_cols
-                    ov[k] = from_f32<T>(f);
+                    const float f = rndc<DT>(to_f32<T>(xv.v[k]) / to_f32<T>(sv.v[k]));     // llmc_div_cols
+                    ov.v[k] = from_f32<T>(f);
                     mn = fminf(mn, f);
                     mx = fmaxf(mx, f);
                 }
-                __builtin_memcpy(&q[j], ov, 16);
+                __builtin_memcpy(&q[j], &ov, 16);
             }
         }
-        mn = wave_min(mn, 64);
-        mx = wave_max(mx, 64);
-        __syncthreads();                          // the previous row's readers are done
-        if ((threadIdx.x & 63) == 0) {
-            smn[threadIdx.x >> 6] = mn;
-            smx[threadIdx.x >> 6] = mx;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < SB / 64; ++i) {
-            mn = fminf(mn, smn[i]);
-            mx = fmaxf(mx, smx[i]);
-        }
+        block_minmax<SB>(red, mn, mx);
         T* op = out + row * K;
         if constexpr (KIND == ACT_INT) {
-            const QParams qp = qparams_from_minmax(mn, mx, DT, sym, 1, qmin, qmax);
-            const Divisor dv = make_divisor(qp.s, fmaxf(fabsf(mn), fabsf(mx)));
+            // fake_quant_act_dynamic is round_zp = 1 only: no fractional-zero-point arm (GroupQuant<false>)
+            const GroupQuant<> gq = GroupQuant<>::from_minmax(mn, mx, DT, sym, 1, qmin, qmax);
 #pragma unroll
             for (int j = 0; j < MAXV; ++j) {
                 const int vi = j * SB + threadIdx.x;
                 if (vi < nv) {
-                    T v[V], o[V];
-                    __builtin_memcpy(v, &q[j], 16);
-#pragma unroll
-                    for (int k = 0; k < V; ++k) {
-                        const float c = quant_code(to_f32<T>(v[k]), dv, qp.z, DT, DT, qmin, qmax);
-                        o[k] = from_f32<T>(dequant_code(c, qp.s, qp.z, DT));
-                    }
-                    uint4 ro;
-                    __builtin_memcpy(&ro, o, 16);
-                    *reinterpret_cast<uint4*>(op + vi * V) = ro;
+                    Vec<T, V> v, o;
+                    __builtin_memcpy(&v, &q[j], 16);
+                    quant_vec<LLMC_OUT_FAKE>(o, v, gq, qmin, qmax);
+                    store_vec<T, V>(op + vi * V, o);
                 }
             }
         } else {
@@ -257,17 +237,15 @@ __global__ __launch_bounds__(SB) void k_osplus_act_step(const T* __restrict__ X,
 #pragma unroll
                     for (int jj = 1; jj < MAXV; ++jj)
                         if (jj == j) rq = q[jj];
-                    T v[V], o[V];
-                    __builtin_memcpy(v, &rq, 16);
+                    Vec<T, V> v, o;
+                    __builtin_memcpy(&v, &rq, 16);
 #pragma unroll
                     for (int k = 0; k < V; ++k) {
                         float val;
-                        (void)fp8_encode(float_scaled_exact(to_f32<T>(v[k]), sc, DT, false), fmt, sem, &val);
-                        o[k] = float_emit<T>(val, sc);
+                        (void)fp8_encode(float_scaled_exact(to_f32<T>(v.v[k]), sc, DT, false), fmt, sem, &val);
+                        o.v[k] = float_emit<T>(val, sc);
                     }
-                    uint4 ro;
-                    __builtin_memcpy(&ro, o, 16);
-                    *reinterpret_cast<uint4*>(op + vi * V) = ro;
+                    store_vec<T, V>(op + vi * V, o);
                 }
             }
         }

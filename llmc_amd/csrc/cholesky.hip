@@ -11,6 +11,7 @@
 // the reference's 4K^3/3.
 #include <stdlib.h>
 #include "common.h"
+#include "mfma_common.h"
 #include "sgemm.h"
 #include "pipe_lanes.h"
 
@@ -55,7 +56,6 @@ __global__ __launch_bounds__(256) void k_antitranspose(const float* __restrict__
 // of the blocked factorisation. Partial blocks are padded with the identity.
 // ---------------------------------------------------------------------------------------------
 static constexpr int PLD = 132;  // LDS leading dimension (floats)
-typedef __attribute__((ext_vector_type(16))) float pf32x16;
 
 __device__ __forceinline__ float rdlane(float v, int l) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
@@ -80,9 +80,8 @@ __device__ __forceinline__ void wave_potrf32_inv(float* __restrict__ S, float* _
                                                  int* __restrict__ info) {
 #pragma clang fp contract(fast)
     (void)rowbuf;
-    typedef __attribute__((ext_vector_type(16))) float acc16;
     const int j = lane & 31, h = lane >> 5;
-    acc16 A, E;
+    f32x16 A, E;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
@@ -172,7 +171,7 @@ __device__ __forceinline__ void wave_potrf32_inv(float* __restrict__ S, float* _
 
 // 32x32x32 block product on the f32 MFMA: acc += op(A) * B, op(A)[i][k] = TA ? A[k][i] : A[i][k]
 template <bool TA>
-__device__ __forceinline__ pf32x16 blk_mm(const float* __restrict__ A, const float* __restrict__ B, pf32x16 acc,
+__device__ __forceinline__ f32x16 blk_mm(const float* __restrict__ A, const float* __restrict__ B, f32x16 acc,
                                           int lane) {
     const int c = lane & 31, h = lane >> 5;
 #pragma unroll
@@ -184,12 +183,12 @@ __device__ __forceinline__ pf32x16 blk_mm(const float* __restrict__ A, const flo
     }
     return acc;
 }
-__device__ __forceinline__ void blk_store(float* __restrict__ C, const pf32x16& acc, int lane, float sign) {
+__device__ __forceinline__ void blk_store(float* __restrict__ C, const f32x16& acc, int lane, float sign) {
     const int c = lane & 31, h = lane >> 5;
 #pragma unroll
     for (int r = 0; r < 16; ++r) C[((r & 3) + 8 * (r >> 2) + 4 * h) * PLD + c] = sign * acc[r];
 }
-__device__ __forceinline__ void blk_sub(float* __restrict__ C, const pf32x16& acc, int lane) {
+__device__ __forceinline__ void blk_sub(float* __restrict__ C, const f32x16& acc, int lane) {
     const int c = lane & 31, h = lane >> 5;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -221,7 +220,7 @@ __global__ __launch_bounds__(256, 2) void k_potrf_inv(float* __restrict__ W, int
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const pf32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     LLMC_STAMP(0);
     // load the block with 16 independent 16-B loads per thread in flight (a scalar loop here serialises 64
     // dependent global-load latencies and was most of this kernel's time)
@@ -277,7 +276,7 @@ __global__ __launch_bounds__(256, 2) void k_potrf_inv(float* __restrict__ W, int
         {   // panel: S(kb, jb) = V_kk^T * S(kb, jb)
             const int jb = kb + 1 + wv;
             if (jb < 4) {
-                pf32x16 acc = blk_mm<true>(VBLK(kb, kb), PBLK(S, kb, jb), zero, lane);
+                f32x16 acc = blk_mm<true>(VBLK(kb, kb), PBLK(S, kb, jb), zero, lane);
                 blk_store(PBLK(S, kb, jb), acc, lane, 1.0f);
             }
         }
@@ -287,7 +286,7 @@ __global__ __launch_bounds__(256, 2) void k_potrf_inv(float* __restrict__ W, int
             for (int ib = kb + 1; ib < 4; ++ib)
                 for (int jb = ib; jb < 4; ++jb, ++idx)
                     if ((idx & 3) == wv) {
-                        pf32x16 acc = blk_mm<true>(PBLK(S, kb, ib), PBLK(S, kb, jb), zero, lane);
+                        f32x16 acc = blk_mm<true>(PBLK(S, kb, ib), PBLK(S, kb, jb), zero, lane);
                         blk_sub(PBLK(S, ib, jb), acc, lane);
                     }
         }
@@ -315,16 +314,16 @@ __global__ __launch_bounds__(256, 2) void k_potrf_inv(float* __restrict__ W, int
     // ---- V = U^-1 by doubling. Level 32 -> 64: pairs (0,1) and (2,3)
     if (wv < 2) {
         const int a = 2 * wv, b = a + 1;
-        pf32x16 x = blk_mm<false>(VBLK(a, a), PBLK(S, a, b), zero, lane);   // X = V_aa * U_ab
+        f32x16 x = blk_mm<false>(VBLK(a, a), PBLK(S, a, b), zero, lane);   // X = V_aa * U_ab
         blk_store(VBLK(a, b), x, lane, 1.0f);
-        pf32x16 y = blk_mm<false>(VBLK(a, b), VBLK(b, b), zero, lane);   // Y = X * V_bb
+        f32x16 y = blk_mm<false>(VBLK(a, b), VBLK(b, b), zero, lane);   // Y = X * V_bb
         blk_store(VBLK(a, b), y, lane, -1.0f);
     }
     __syncthreads();
     // Level 64 -> 128: X = V[0:64,0:64] * U[0:64,64:128] (into V scratch), then -X * V[64:,64:] (into S scratch)
     {
         const int r = wv >> 1, c = 2 + (wv & 1);
-        pf32x16 x = blk_mm<false>(VBLK(r, r), PBLK(S, r, c), zero, lane);
+        f32x16 x = blk_mm<false>(VBLK(r, r), PBLK(S, r, c), zero, lane);
         if (r == 0) x = blk_mm<false>(VBLK(0, 1), PBLK(S, 1, c), x, lane);
         __syncthreads();  // everyone has read U[0:64,64:128] from S and the level-1 V blocks
         blk_store(VBLK(r, c), x, lane, 1.0f);
@@ -332,7 +331,7 @@ __global__ __launch_bounds__(256, 2) void k_potrf_inv(float* __restrict__ W, int
     __syncthreads();
     {
         const int r = wv >> 1, c = 2 + (wv & 1);
-        pf32x16 y = blk_mm<false>(VBLK(r, 2), VBLK(2, c), zero, lane);
+        f32x16 y = blk_mm<false>(VBLK(r, 2), VBLK(2, c), zero, lane);
         if (c == 3) y = blk_mm<false>(VBLK(r, 3), VBLK(3, 3), y, lane);
         blk_store(PBLK(S, r, c), y, lane, -1.0f);
     }

@@ -5,6 +5,7 @@
 #include <string.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #include "../../include/llmc_hip.h"
 
@@ -193,6 +194,15 @@ __device__ __forceinline__ float wave_min(float v, int width) {
 __device__ __forceinline__ float wave_sum(float v, int width) {
     for (int o = width >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+
+// compile-time loop: static_for<0, N>(f) calls f(integral_constant<int, i>{}) for i = 0 .. N - 1, so that the body can use the index as a template
+// argument, an asm immediate or an `if constexpr` condition (a `#pragma unroll` loop variable is none of these)
+template <int I, int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
+    if constexpr (I < N) {
+        f(std::integral_constant<int, I>{});
+        static_for<I + 1, N>(f);
+    }
 }
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -10,7 +10,6 @@
 // exact in fp32, the 128-deep partial sums accumulate in fp32 inside the MFMA.
 #include "common.h"
 #include <stdlib.h>
-#include <type_traits>
 #include "fp8_math.h"
 #include "quant_math.h"
 #include "mfma_common.h"
@@ -398,9 +397,6 @@ static constexpr int G2_AS = 2 * G2_STAGE;         // a_s of one K block: 256 fl
 static constexpr int G2_LDS = 2 * G2_STAGE + 2 * 1024;   // 130 KiB
 static constexpr int G2_THREADS = 512;
 
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 struct Fp8GemmArgs {
     const uint8_t* A; const float* As; const uint8_t* B; const float* Bs;
     int64_t M, N, K;
@@ -414,57 +410,32 @@ struct Fp8GemmArgs {
 #endif
 };
 
-template <int DST>
-__device__ __forceinline__ void g2_dma(i32x4 rsrc, uint32_t voff, uint32_t soff, uint32_t wvoff) {
-    asm volatile("s_add_u32 m0, %3, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %0 offen lds"
-                 :: "s"(soff), "v"(voff), "s"(rsrc), "s"(wvoff), "n"(DST) : "memory", "scc");
-}
-template <int DST>
-__device__ __forceinline__ void g2_dma4(i32x4 rsrc, uint32_t voff, uint32_t soff, uint32_t m0base) {    // 4 B per lane
-    asm volatile("s_add_u32 m0, %3, %4\n\ts_nop 0\n\tbuffer_load_dword %1, %2, %0 offen lds"
-                 :: "s"(soff), "v"(voff), "s"(rsrc), "s"(m0base), "n"(DST) : "memory", "scc");
-}
-template <int I, int N, typename F> __device__ __forceinline__ void g2_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        g2_for<I + 1, N>(f);
-    }
-}
-
 template <int DT, bool FUSED = false>     // FUSED: LLMC_FP8_GEMM_FUSED_SCALE (a template parameter: as a run-time branch it spilled 102 registers)
 __global__ __launch_bounds__(G2_THREADS) void k_fp8_block_gemm256(Fp8GemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) char g2_smem[];
     LDS_AS char* lds = (LDS_AS char*)g2_smem;
-    if ((uint32_t)(uintptr_t)lds != 0u) __builtin_trap();   // DMA destinations are immediates
+    require_lds_base_zero(lds);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wv >> 2, wn = wv & 3;
     const int nkb = (int)(a.K / 128);
     const uint32_t K32 = (uint32_t)a.K;
 
-    i32x4 ra, rb;
-    {
-        const int64_t ab = a.M * a.K, bb = a.N * a.K;
-        ra[0] = (int)(uint32_t)(uintptr_t)a.A;
-        ra[1] = (int)((uint32_t)((uintptr_t)a.A >> 32) & 0xffffu);
-        ra[2] = (int)(uint32_t)ab;
-        ra[3] = 0x00020000;
-        rb[0] = (int)(uint32_t)(uintptr_t)a.B;
-        rb[1] = (int)((uint32_t)((uintptr_t)a.B >> 32) & 0xffffu);
-        rb[2] = (int)(uint32_t)bb;
-        rb[3] = 0x00020000;
-    }
+    const int64_t ab = a.M * a.K, bb = a.N * a.K;
+    const i32x4 ra = rsrc_words(a.A, ab), rb = rsrc_words(a.B, bb);
     // b_s [N / 128, nkb] fp32: read-only for the whole launch, read through the constant address space = scalar loads (which do
     // not ride on the vector memory counter the DMA is waited on with)
     typedef __attribute__((address_space(4))) const float cfloat_t;
     cfloat_t* bsc = (cfloat_t*)(uintptr_t)a.Bs;
     // a_s [M, nkb] fp32 through a buffer descriptor (rows past M read 0); the 256 scales of a K block go to LDS by DMA like the
     // operands (a compiler-visible vector load in the loop would make hipcc count vmcnt without the asm-issued DMA)
+    // (rsrc_words(a.As, a.M * nkb * 4) written out: as an argument the product is formed before words 0 and 1, not after them,
+    // and the kernel's scalar prologue comes out in another order)
     i32x4 rs;
     rs[0] = (int)(uint32_t)(uintptr_t)a.As;
     rs[1] = (int)((uint32_t)((uintptr_t)a.As >> 32) & 0xffffu);
     rs[2] = (int)(uint32_t)(a.M * nkb * 4);
-    rs[3] = 0x00020000;
+    rs[3] = RSRC_WORD3;
     // DMA: wave wv moves pieces wv + 8 i (i = 0..3) of each panel; a piece = rows 8 p .. 8 p + 7, lane = (row lane >> 3, slot lane & 7)
     const uint32_t voff = (uint32_t)(lane >> 3) * K32 + (uint32_t)((((lane & 7) ^ ((4 * (wv & 1) + (lane >> 4)) & 7))) << 4);
     const uint32_t wvoff = (uint32_t)wv * 1024u;
@@ -503,16 +474,16 @@ __global__ __launch_bounds__(G2_THREADS) void k_fp8_block_gemm256(Fp8GemmArgs a)
         // tile, slot kb & 1; waves 4..7 repeat what waves 0..3 move: no branch in the loop)
         auto dma_piece = [&](auto pc, uint32_t st, int kb) {
             constexpr int P = decltype(pc)::value;
-            if constexpr (P == 8) g2_dma4<G2_AS>(rs, asoff, (uint32_t)kb * 4u, (uint32_t)((wv & 3) * 256 + (kb & 1) * 1024));
+            if constexpr (P == 8) dma_imm_at<G2_AS, 4>(rs, asoff, (uint32_t)kb * 4u, (uint32_t)((wv & 3) * 256 + (kb & 1) * 1024));
             else if constexpr ((P & 1) == 0) {
-                g2_dma<(P >> 1) * 8192>(ra, voff, sA[P >> 1], wvoff + st);
+                dma_imm_at<(P >> 1) * 8192>(ra, voff, sA[P >> 1], wvoff + st);
                 sA[P >> 1] += 128u;
             } else {
-                g2_dma<G2_PANEL + (P >> 1) * 8192>(rb, voff, sB[P >> 1], wvoff + st);
+                dma_imm_at<G2_PANEL + (P >> 1) * 8192>(rb, voff, sB[P >> 1], wvoff + st);
                 sB[P >> 1] += 128u;
             }
         };
-        auto stage_dma = [&](uint32_t st, int kb) { g2_for<0, 9>([&](auto pc) { dma_piece(pc, st, kb); }); };
+        auto stage_dma = [&](uint32_t st, int kb) { static_for<0, 9>([&](auto pc) { dma_piece(pc, st, kb); }); };
         // scales: a_s of this lane's four m rows (one per 32-row tile; rows past M read 0 through the descriptor's bound),
         // b_s of this wave's 128-column block
         const int nblk = __builtin_amdgcn_readfirstlane((int)((n0 + wn * 64) / 128));
@@ -556,7 +527,7 @@ __global__ __launch_bounds__(G2_THREADS) void k_fp8_block_gemm256(Fp8GemmArgs a)
             fa[0][0] = frag(adA, 0, 0);
             fa[0][1] = frag(adA, 0, 1);
         };
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        vm_wait<0>();
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         first_frags(0u);
@@ -610,7 +581,7 @@ __global__ __launch_bounds__(G2_THREADS) void k_fp8_block_gemm256(Fp8GemmArgs a)
                 asm volatile("" : "+v"(acc[i][j][0]), "+v"(acc[i][j][1]), "+v"(acc[i][j][2]), "+v"(acc[i][j][3]),
                              "+v"(acc[i][j][4]), "+v"(acc[i][j][5]), "+v"(acc[i][j][6]), "+v"(acc[i][j][7]));
             };
-            g2_for<0, 8>([&](auto tc) {
+            static_for<0, 8>([&](auto tc) {
                 constexpr int t = decltype(tc)::value, j = t >> 1, i = t & 1;
                 f32x16 pz;
 #pragma unroll
@@ -656,7 +627,7 @@ __global__ __launch_bounds__(G2_THREADS) void k_fp8_block_gemm256(Fp8GemmArgs a)
                 if constexpr (more && t == 7) {
                     // every fragment of this slot is in registers: publish the next slot (my pieces landed, then everybody's)
                     // and fetch its first fragments while updates 6 and 7 are still to run
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    vm_wait<0>();
 #ifdef LLMC_LAB
                     if (!(a.abl & 64))
 #endif
@@ -694,7 +665,7 @@ __global__ __launch_bounds__(G2_THREADS) void k_fp8_block_gemm256(Fp8GemmArgs a)
         const bool full = m0 + G2_T <= a.M && n0 + G2_T <= a.N && (a.N & 7) == 0 && a.bias == nullptr;   // block-uniform
         if (full) {
             constexpr int ES = DT == LLMC_F32 ? 4 : 2;
-            g2_for<0, 4>([&](auto jc) {
+            static_for<0, 4>([&](auto jc) {
                 constexpr int j = decltype(jc)::value;
                 if constexpr (DT == LLMC_F32) {
                     char* crow = (char*)a.C + ((m0 + wm * 128 + j * 32 + (lane & 31)) * a.N + n0 + wn * 64 + 4 * h) * ES;
@@ -729,7 +700,7 @@ __global__ __launch_bounds__(G2_THREADS) void k_fp8_block_gemm256(Fp8GemmArgs a)
                 }
             });
         } else {
-            g2_for<0, 4>([&](auto jc) {
+            static_for<0, 4>([&](auto jc) {
                 constexpr int j = decltype(jc)::value;
                 const int64_t row = m0 + wm * 128 + j * 32 + (lane & 31);
                 if (row < a.M) {

@@ -17,7 +17,6 @@
 // P in `T -= P^T P`. A workgroup owns a 128x128 tile; per K-step of 32 it stages both 32x128 panels through
 // registers (split there) into three bf16 planes each, k-major in LDS exactly like hessian_syrk.hip's token-major
 // panels (64-B units XOR-swizzled by k & 3), and feeds the MFMAs with ds_read_b64_tr_b16 transposing reads.
-#include <type_traits>
 #include "sgemm.h"
 #include "mfma_common.h"
 
@@ -28,57 +27,9 @@ static constexpr int G3ROW = G3B * 2;         // bytes per k-row of one plane
 static constexpr int G3PLANE = G3K * G3ROW;   // 8 KiB
 static constexpr int G3PANEL = 3 * G3PLANE;   // hi | mid | lo
 
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ s16x8 tr_frag256(LDS_AS char* p, int imm0) {
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(p + imm0));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(p + imm0 + 4 * G3ROW));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
-// split 4 fp32 values into three packed-bf16 quadruples and write them to the three planes
-__device__ __forceinline__ void split_store(float4 v, LDS_AS char* plane0, int off) {
-    f32x2_t a0 = {v.x, v.y}, a1 = {v.z, v.w};
-    u32x2_t out[3];
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        const bf16x2_t h0 = __builtin_convertvector(a0, bf16x2_t);
-        const bf16x2_t h1 = __builtin_convertvector(a1, bf16x2_t);
-        out[t].x = __builtin_bit_cast(uint32_t, h0);
-        out[t].y = __builtin_bit_cast(uint32_t, h1);
-        if (t < 2) {
-            a0 = a0 - __builtin_convertvector(h0, f32x2_t);
-            a1 = a1 - __builtin_convertvector(h1, f32x2_t);
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 3; ++t) *(LDS_AS u32x2_t*)(plane0 + t * G3PLANE + off) = out[t];
-}
-
 static constexpr int G3AROW = 80;                 // bytes per row of a row-major A plane: 32 bf16 + 16 B pad
 static constexpr int G3APLANE = G3B * G3AROW;     // 10 KiB
 static constexpr int G3APANEL = 3 * G3APLANE;     // 30 KiB (TA = false); k-major A uses G3PANEL = 24 KiB
-
-// 4 consecutive k of one row -> three bf16 quadruples into the row-major A planes
-__device__ __forceinline__ void split_store_rows(float4 v, LDS_AS char* plane0, int off) {
-    f32x2_t a0 = {v.x, v.y}, a1 = {v.z, v.w};
-    u32x2_t out[3];
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        const bf16x2_t h0 = __builtin_convertvector(a0, bf16x2_t);
-        const bf16x2_t h1 = __builtin_convertvector(a1, bf16x2_t);
-        out[t].x = __builtin_bit_cast(uint32_t, h0);
-        out[t].y = __builtin_bit_cast(uint32_t, h1);
-        if (t < 2) {
-            a0 = a0 - __builtin_convertvector(h0, f32x2_t);
-            a1 = a1 - __builtin_convertvector(h1, f32x2_t);
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 3; ++t) *(LDS_AS u32x2_t*)(plane0 + t * G3APLANE + off) = out[t];
-}
 
 // TA = true : op(A)[i][k] = A[k][i], A stored [Kd x M] (k-major, transposing LDS reads)
 // TA = false: op(A)[i][k] = A[i][k], A stored [M x Kd] (row-major, 16-B LDS reads of 8 consecutive k)
@@ -162,9 +113,9 @@ __global__ __launch_bounds__(256, 2) void k_gemm3(SgemmArgs a) {
     for (int k0 = kb; k0 < ke; k0 += G3K) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            if (TA) split_store(ra[q], lds, lds_off(sk + 8 * q));
-            else split_store_rows(ra[q], lds, (ar + 32 * q) * G3AROW + ak * 2);
-            split_store(rb[q], ldsB, lds_off(sk + 8 * q));
+            if (TA) split3_store<G3PLANE>(__builtin_bit_cast(f32x4, ra[q]), lds, lds_off(sk + 8 * q));
+            else split3_store<G3APLANE>(__builtin_bit_cast(f32x4, ra[q]), lds, (ar + 32 * q) * G3AROW + ak * 2);    // 4 consecutive k of one row
+            split3_store<G3PLANE>(__builtin_bit_cast(f32x4, rb[q]), ldsB, lds_off(sk + 8 * q));
         }
         __syncthreads();
         if (k0 + G3K < ke) gload(k0 + G3K);
@@ -175,11 +126,11 @@ __global__ __launch_bounds__(256, 2) void k_gemm3(SgemmArgs a) {
             for (int t = 0; t < 3; ++t) {
 #pragma unroll
                 for (int m = 0; m < 2; ++m) {
-                    if (TA) fa[m][t] = tr_frag256(lds + t * G3PLANE + offA[m], kk * 16 * G3ROW);
+                    if (TA) fa[m][t] = tr_frag<G3ROW>(lds + t * G3PLANE + offA[m], kk * 16 * G3ROW);
                     else fa[m][t] = *(LDS_AS s16x8*)(lds + t * G3APLANE + offA[m] + kk * 32);
                 }
 #pragma unroll
-                for (int n = 0; n < 2; ++n) fb[n][t] = tr_frag256(ldsB + t * G3PLANE + offB[n], kk * 16 * G3ROW);
+                for (int n = 0; n < 2; ++n) fb[n][t] = tr_frag<G3ROW>(ldsB + t * G3PLANE + offB[n], kk * 16 * G3ROW);
             }
 #pragma unroll
             for (int m = 0; m < 2; ++m)
@@ -231,7 +182,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm3(SgemmArgs a) {
 // two jobs of k_gemm3 given to DIFFERENT waves: waves 0..3 (one per SIMD) only read fragments and issue MFMAs, waves 4..7
 // (their SIMD partners) only bring the three bf16 planes of the NEXT K-step into the other LDS buffer. One barrier per
 // K-step.
-//   PRE = false: the producers fetch the fp32 panels and split them (the arithmetic of split_store);
+//   PRE = false: the producers fetch the fp32 panels and split them (split3, mfma_common.h);
 //   PRE = true : the panels were split ONCE into bf16 planes in memory (k_split3_planes: the same arithmetic), the producers
 //                only copy. In k_gemm3 every 128 x 128 tile splits its two panels again: a panel of a 13312-column far
 //                update is split 104 times.
@@ -265,29 +216,6 @@ static constexpr int R_SLOT = 3 * R_APLANE + 3 * R_BPLANE;                    //
 static constexpr int R_SLOTS = 4;
 static_assert(R_SLOTS * R_SLOT == S_LDS, "the ring takes the two buffers' LDS");
 
-template <int ROW>
-__device__ __forceinline__ s16x8 tr_frag_row(LDS_AS char* p, int imm0) {
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(p + imm0));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(p + imm0 + 4 * ROW));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
-// the three bf16 terms of four fp32 values (split_store's arithmetic), as three packed quadruples
-__device__ __forceinline__ void split3(f32x4 v, u32x2_t (&out)[3]) {
-    f32x2_t a0 = {v[0], v[1]}, a1 = {v[2], v[3]};
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        const bf16x2_t h0 = __builtin_convertvector(a0, bf16x2_t);
-        const bf16x2_t h1 = __builtin_convertvector(a1, bf16x2_t);
-        out[t].x = __builtin_bit_cast(uint32_t, h0);
-        out[t].y = __builtin_bit_cast(uint32_t, h1);
-        if (t < 2) {
-            a0 = a0 - __builtin_convertvector(h0, f32x2_t);
-            a1 = a1 - __builtin_convertvector(h1, f32x2_t);
-        }
-    }
-}
-
 // P [rows x n] fp32 (ld) -> planes [3][rows][ldp] bf16: hi | mid | lo of every element. n % 8 == 0; one thread per 8 columns.
 __global__ __launch_bounds__(256) void k_split3_planes(const float* __restrict__ P, int64_t ld, int rows, int n,
                                                        uint16_t* __restrict__ planes, int64_t ldp, int64_t ps) {
@@ -296,14 +224,12 @@ __global__ __launch_bounds__(256) void k_split3_planes(const float* __restrict__
     if (8 * c8 >= n) return;
     const float* src = P + (int64_t)r * ld + 8 * c8;
     const f32x4 v0 = *reinterpret_cast<const f32x4*>(src), v1 = *reinterpret_cast<const f32x4*>(src + 4);
-    u32x2_t o0[3], o1[3];
+    u32x2 o0[3], o1[3];
     split3(v0, o0);
     split3(v1, o1);
 #pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-        *reinterpret_cast<u32x4_t*>(planes + t * ps + (int64_t)r * ldp + 8 * c8) = u32x4_t{o0[t].x, o0[t].y, o1[t].x, o1[t].y};
-    }
+    for (int t = 0; t < 3; ++t)
+        *reinterpret_cast<u32x4*>(planes + t * ps + (int64_t)r * ldp + 8 * c8) = u32x4{o0[t].x, o0[t].y, o1[t].x, o1[t].y};
 }
 
 __device__ long long g_g3s_stamps[8 * 128];
@@ -341,17 +267,10 @@ __global__ __launch_bounds__(512, 1) void k_gemm3s(SgemmArgs a) {
         // the LDS image is lane-linear, the rows' 64-B-unit XOR swizzle (unit ^ (k & 3), what the fragment reads undo) is
         // applied to the per-lane SOURCE column instead. Same planes, same LDS image, same MFMA order: the same bits.
         const int pw = wv - 4;
-        auto mk = [](const void* p, uint32_t bytes) {     // from provably wave-uniform inputs
-            const uint64_t u = (uint64_t)p;
-            const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u);
-            const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(u >> 32));
-            return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), (short)0,
-                                                     __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
-        };
         const uint16_t* pA = (const uint16_t*)a.planesA + (int64_t)z * a.sA;
         const uint16_t* pB = (const uint16_t*)a.planesB + (int64_t)z * a.sB;
-        const auto dA = mk(pA + i0, (uint32_t)((2 * a.plane_stride + ((int64_t)(Kd - 1)) * a.ldp + min(S_BM, M - i0)) * 2));
-        const auto dB = mk(pB + j0, (uint32_t)((2 * a.plane_stride + ((int64_t)(Kd - 1)) * a.ldp + min(S_BN, N - j0)) * 2));
+        const auto dA = uniform_rsrc(pA + i0, (uint32_t)((2 * a.plane_stride + ((int64_t)(Kd - 1)) * a.ldp + min(S_BM, M - i0)) * 2));
+        const auto dB = uniform_rsrc(pB + j0, (uint32_t)((2 * a.plane_stride + ((int64_t)(Kd - 1)) * a.ldp + min(S_BN, N - j0)) * 2));
         // A pieces of this wave are p = pw, pw + 4, ..: k = 2 p, so (k + r) & 3 = 2 (pw & 1) + r for the lane's row r
         uint32_t voA, voB;
         {
@@ -366,10 +285,6 @@ __global__ __launch_bounds__(512, 1) void k_gemm3s(SgemmArgs a) {
         }
         const uint32_t lds0 = (uint32_t)(uintptr_t)lds;
         const uint32_t row2 = (uint32_t)(a.ldp * 2), ps2 = (uint32_t)(a.plane_stride * 2);
-        auto dma = [&](const decltype(dA)& d, uint32_t vo, uint32_t so, uint32_t dst) {
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds"
-                         :: "v"(vo), "s"(d), "s"(dst), "s"(so) : "memory");
-        };
         const int rsteps = Kd / R_K;                      // 16-k ring steps (Kd % 64 == 0, >= 128: an even number >= 8)
         auto issue = [&](int j) {
             const uint32_t slot = lds0 + (uint32_t)(j & (R_SLOTS - 1)) * R_SLOT;
@@ -377,19 +292,19 @@ __global__ __launch_bounds__(512, 1) void k_gemm3s(SgemmArgs a) {
 #pragma unroll
             for (int t = 0; t < 6; ++t) {                  // A: piece index 4 t + pw = 8 plane + p (two k-rows each)
                 const int idx = 4 * t + pw, pl = idx >> 3, pp = idx & 7;
-                dma(dA, voA, (uint32_t)pl * ps2 + (k0 + 2u * pp) * row2, slot + (uint32_t)pl * R_APLANE + (uint32_t)pp * 1024u);
+                dma16_to(dA, voA, (uint32_t)pl * ps2 + (k0 + 2u * pp) * row2, slot + (uint32_t)pl * R_APLANE + (uint32_t)pp * 1024u);
             }
 #pragma unroll
             for (int t = 0; t < 3; ++t) {                  // B: piece index 4 t + pw = 4 plane + q (four k-rows each)
                 const int idx = 4 * t + pw, pl = idx >> 2, q = idx & 3;
-                dma(dB, voB, (uint32_t)pl * ps2 + (k0 + 4u * q) * row2, slot + 3u * R_APLANE + (uint32_t)pl * R_BPLANE + (uint32_t)q * 1024u);
+                dma16_to(dB, voB, (uint32_t)pl * ps2 + (k0 + 4u * q) * row2, slot + 3u * R_APLANE + (uint32_t)pl * R_BPLANE + (uint32_t)q * 1024u);
             }
         };
         // the old C values: this thread's 32 quadruples (row (t >> 5) + 8 q, columns 4 (t & 31)), four per step behind steps 0 .. 7
         const int t = tid - 256;
         const int c4 = 4 * (t & 31), r0 = t >> 5;
         const int col = j0 + c4;
-        const auto dC = mk(C + (int64_t)i0 * a.ldc + j0, (uint32_t)((((int64_t)(min(S_BM, M - i0) - 1)) * a.ldc + min(S_BN, N - j0)) * 4));
+        const auto dC = uniform_rsrc(C + (int64_t)i0 * a.ldc + j0, (uint32_t)((((int64_t)(min(S_BM, M - i0) - 1)) * a.ldc + min(S_BN, N - j0)) * 4));
         const int row_lim = col >= N ? 0 : (a.c_upper_only ? min(M, (col & ~31) + 32) : M) - i0 - r0;
         const uint32_t c_base = (uint32_t)(((int64_t)r0 * a.ldc + c4) * 4), c_step = (uint32_t)(a.ldc * 32);
         auto c_off = [&](int q) { return (c_base + (uint32_t)q * c_step) | (8 * q < row_lim ? 0u : 0x80000000u); };
@@ -397,7 +312,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm3s(SgemmArgs a) {
         issue(0);
         issue(1);
         issue(2);
-        asm volatile("s_waitcnt vmcnt(18)" ::: "memory");     // step 0's nine pieces of this wave have landed (18 younger ones may fly)
+        vm_wait<18>();     // step 0's nine pieces of this wave have landed (18 younger ones may fly)
         __syncthreads();                 // step 0 is in its slot
         // Loop body j: the MFMA waves work on step j; slot (j + 3) & 3 = (j - 1) & 3 was read in step j - 1, which every MFMA wave
         // had finished at the barrier before: request step j + 3 into it, wait for step j + 1, publish it. The counted waits
@@ -411,8 +326,8 @@ __global__ __launch_bounds__(512, 1) void k_gemm3s(SgemmArgs a) {
             for (int e = 0; e < 4; ++e)
                 old[4 * u + e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(dC, c_off(4 * u + e), 0, 0));
             if (j + 1 < rsteps) {
-                if (j + 3 < rsteps) asm volatile("s_waitcnt vmcnt(30)" ::: "memory");        // younger than step j + 1: steps j + 2, j + 3 (18) and the C loads of three bodies (12)
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (j + 3 < rsteps) vm_wait<30>();        // younger than step j + 1: steps j + 2, j + 3 (18) and the C loads of three bodies (12)
+                else vm_wait<0>();
                 __syncthreads();
             }
             ++j;
@@ -420,11 +335,11 @@ __global__ __launch_bounds__(512, 1) void k_gemm3s(SgemmArgs a) {
         for (; j + 1 < rsteps; ++j) {
             if (j + 3 < rsteps) {
                 issue(j + 3);
-                asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
+                vm_wait<18>();
             } else if (j + 2 < rsteps) {
-                asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
+                vm_wait<9>();
             } else {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                vm_wait<0>();
             }
             __syncthreads();
         }
@@ -437,8 +352,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm3s(SgemmArgs a) {
             if (a.epilogue == SG_SUB) w = old[q] - v;
             else if (a.epilogue == SG_SET) w = v;
             else w = -v;
-            typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, w), dC, c_off(q), 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, w), dC, c_off(q), 0, 0);
         }
         return;
       }
@@ -446,13 +360,6 @@ __global__ __launch_bounds__(512, 1) void k_gemm3s(SgemmArgs a) {
     if (wv >= 4) {
         // ---------------- producer waves: bring the planes of step j into buffer j & 1
         const int t = tid - 256;
-        auto mk = [](const void* p, uint32_t bytes) {     // from provably wave-uniform inputs
-            const uint64_t u = (uint64_t)p;
-            const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u);
-            const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(u >> 32));
-            return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), (short)0,
-                                                     __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
-        };
         // NA / NB 16-B loads per thread and K-step. fp32 panels: A float4 q = k-row (t >> 6) + 4 q, columns 4 (t & 63); B: k-row
         // (t >> 5) + 8 q, columns 4 (t & 31). Planes: A 16-B chunk q of plane pl = k-row (t >> 5) + 8 q, columns 8 (t & 31);
         // B: k-row (t >> 4) + 16 q, columns 8 (t & 15).
@@ -460,13 +367,13 @@ __global__ __launch_bounds__(512, 1) void k_gemm3s(SgemmArgs a) {
         uint32_t voA[NA], voB[NB_];
         int loA[NA], loB[NB_];
         uint32_t incA, incB;
-        decltype(mk(nullptr, 0u)) dA, dB;
+        buf_rsrc dA, dB;
         if constexpr (PRE) {
             const uint16_t* pA = (const uint16_t*)a.planesA + (int64_t)z * a.sA;
             const uint16_t* pB = (const uint16_t*)a.planesB + (int64_t)z * a.sB;
             // range: up to the last valid element of row Kd - 1 of the THIRD plane
-            dA = mk(pA + i0, (uint32_t)((2 * a.plane_stride + ((int64_t)(Kd - 1)) * a.ldp + min(S_BM, M - i0)) * 2));
-            dB = mk(pB + j0, (uint32_t)((2 * a.plane_stride + ((int64_t)(Kd - 1)) * a.ldp + min(S_BN, N - j0)) * 2));
+            dA = uniform_rsrc(pA + i0, (uint32_t)((2 * a.plane_stride + ((int64_t)(Kd - 1)) * a.ldp + min(S_BM, M - i0)) * 2));
+            dB = uniform_rsrc(pB + j0, (uint32_t)((2 * a.plane_stride + ((int64_t)(Kd - 1)) * a.ldp + min(S_BN, N - j0)) * 2));
             const int ca = t & 31, cb = t & 15;
             const uint32_t okA = i0 + 8 * ca < M ? 0u : 0x80000000u, okB = j0 + 8 * cb < N ? 0u : 0x80000000u;
 #pragma unroll
@@ -487,8 +394,8 @@ __global__ __launch_bounds__(512, 1) void k_gemm3s(SgemmArgs a) {
             incA = incB = (uint32_t)(a.ldp * G3K * 2);
         } else {
             // range: up to the last valid element of row Kd - 1 of the tile's columns
-            dA = mk(A + i0, (uint32_t)((((int64_t)(Kd - 1)) * a.lda + min(S_BM, M - i0)) * 4));
-            dB = mk(B + j0, (uint32_t)((((int64_t)(Kd - 1)) * a.ldb + min(S_BN, N - j0)) * 4));
+            dA = uniform_rsrc(A + i0, (uint32_t)((((int64_t)(Kd - 1)) * a.lda + min(S_BM, M - i0)) * 4));
+            dB = uniform_rsrc(B + j0, (uint32_t)((((int64_t)(Kd - 1)) * a.ldb + min(S_BN, N - j0)) * 4));
             const int ca = 4 * (t & 63), cb = 4 * (t & 31);
             const uint32_t okA = i0 + ca < M ? 0u : 0x80000000u, okB = j0 + cb < N ? 0u : 0x80000000u;
 #pragma unroll
@@ -516,7 +423,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm3s(SgemmArgs a) {
             for (int q = 0; q < NB_; ++q) sb[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(dB, voB[q] + oB, 0, 0));
         };
         auto produce = [&](f32x4 (&sa)[NA], f32x4 (&sb)[NB_], int j, auto reload) {
-            if (DBG == 4) { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NA + NB_) : "memory"); G3S_STAMP(1 + 4 * j); }
+            if (DBG == 4) { vm_wait<NA + NB_>(); G3S_STAMP(1 + 4 * j); }
             LDS_AS char* bufA = lds + (j & 1) * S_BUF;
             LDS_AS char* bufB = bufA + 3 * S_APLANE;
             if constexpr (PRE) {
@@ -526,23 +433,23 @@ __global__ __launch_bounds__(512, 1) void k_gemm3s(SgemmArgs a) {
                 for (int q = 0; q < NB_; ++q) *(LDS_AS f32x4*)(bufB + loB[q]) = sb[q];
             } else {
 #pragma unroll
-                for (int q = 0; q < NA; ++q) {
-                    u32x2_t o[3];
+                for (int q = 0; q < NA; ++q) {         // split3_store written out: through the helper this kernel's stream moves
+                    u32x2 o[3];
                     split3(sa[q], o);
 #pragma unroll
-                    for (int pl = 0; pl < 3; ++pl) *(LDS_AS u32x2_t*)(bufA + pl * S_APLANE + loA[q]) = o[pl];
+                    for (int pl = 0; pl < 3; ++pl) *(LDS_AS u32x2*)(bufA + pl * S_APLANE + loA[q]) = o[pl];
                 }
 #pragma unroll
                 for (int q = 0; q < NB_; ++q) {
-                    u32x2_t o[3];
+                    u32x2 o[3];
                     split3(sb[q], o);
 #pragma unroll
-                    for (int pl = 0; pl < 3; ++pl) *(LDS_AS u32x2_t*)(bufB + pl * S_BPLANE + loB[q]) = o[pl];
+                    for (int pl = 0; pl < 3; ++pl) *(LDS_AS u32x2*)(bufB + pl * S_BPLANE + loB[q]) = o[pl];
                 }
             }
             if constexpr (decltype(reload)::value) bload(sa, sb, j + 2);
             __builtin_amdgcn_sched_barrier(0);
-            if (DBG == 4) { G3S_STAMP(2 + 4 * j); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); G3S_STAMP(3 + 4 * j); }
+            if (DBG == 4) { G3S_STAMP(2 + 4 * j); lds_wait_all(); G3S_STAMP(3 + 4 * j); }
         };
         bload(sa0, sb0, 0);
         __builtin_amdgcn_sched_barrier(0);     // the two sets in issue order: a step waits for its own set only
@@ -573,7 +480,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm3s(SgemmArgs a) {
         // Through a descriptor of the C tile, a quadruple that is not wanted at an out-of-range offset, and the loads issued
         // whatever the epilogue: straight-line code. Behind branches (per lane or per epilogue) hipcc's vmcnt bookkeeping
         // cannot count them and makes the last plane store wait for every one of them.
-        const auto dC = mk(C + (int64_t)i0 * a.ldc + j0, (uint32_t)((((int64_t)(min(S_BM, M - i0) - 1)) * a.ldc + min(S_BN, N - j0)) * 4));
+        const auto dC = uniform_rsrc(C + (int64_t)i0 * a.ldc + j0, (uint32_t)((((int64_t)(min(S_BM, M - i0) - 1)) * a.ldc + min(S_BN, N - j0)) * 4));
         // wanted rows of this thread's column quadruple: below row_lim (an upper-only update stops above the first 32 x 32
         // block that lies entirely below the diagonal; a column beyond N wants nothing). Few VALU instructions per
         // quadruple: the producers issue them beside MFMA waves that hold the issue priority.
@@ -593,7 +500,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm3s(SgemmArgs a) {
         for (int q = 16; q < 32; ++q) old[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(dC, c_off(q), 0, 0));
         __builtin_amdgcn_sched_barrier(0);
         G3S_STAMP(100);
-        if (DBG == 4) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); G3S_STAMP(101); }
+        if (DBG == 4) { lds_wait_all(); G3S_STAMP(101); }
         __syncthreads();
         G3S_STAMP(4 + 4 * (nsteps - 2));
         produce(sa1, sb1, nsteps - 1, LAST);
@@ -609,10 +516,9 @@ __global__ __launch_bounds__(512, 1) void k_gemm3s(SgemmArgs a) {
             if (a.epilogue == SG_SUB) w = old[q] - v;
             else if (a.epilogue == SG_SET) w = v;
             else w = -v;
-            typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, w), dC, c_off(q), 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, w), dC, c_off(q), 0, 0);
         }
-        if (DBG == 4) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); G3S_STAMP(121); }
+        if (DBG == 4) { vm_wait<0>(); G3S_STAMP(121); }
         return;
     }
 
@@ -649,13 +555,13 @@ __global__ __launch_bounds__(512, 1) void k_gemm3s(SgemmArgs a) {
 #pragma unroll
             for (int t = 0; t < 3; ++t)
 #pragma unroll
-                for (int r = 0; r < 2; ++r) f[r][t] = tr_frag_row<S_AROW>(bA + t * aplane + offA[m0 + r], imm);
+                for (int r = 0; r < 2; ++r) f[r][t] = tr_frag<S_AROW>(bA + t * aplane + offA[m0 + r], imm);
         };
         auto ldB = [&](s16x8 (&f)[2][3], LDS_AS char* bB, int bplane, int imm) {
 #pragma unroll
             for (int t = 0; t < 3; ++t)
 #pragma unroll
-                for (int n = 0; n < 2; ++n) f[n][t] = tr_frag_row<S_BROW>(bB + t * bplane + offB[n], imm);
+                for (int n = 0; n < 2; ++n) f[n][t] = tr_frag<S_BROW>(bB + t * bplane + offB[n], imm);
         };
         auto pair = [&](auto mc, const s16x8 (&fa)[2][3], const s16x8 (&fb)[2][3]) {
             constexpr int m = decltype(mc)::value;
@@ -721,9 +627,9 @@ __global__ __launch_bounds__(512, 1) void k_gemm3s(SgemmArgs a) {
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
 #pragma unroll
-                for (int m = 0; m < 4; ++m) fa[m][t] = tr_frag_row<S_AROW>(bufA + t * S_APLANE + offA[m], kk * 16 * S_AROW);
+                for (int m = 0; m < 4; ++m) fa[m][t] = tr_frag<S_AROW>(bufA + t * S_APLANE + offA[m], kk * 16 * S_AROW);
 #pragma unroll
-                for (int n = 0; n < 2; ++n) fb[n][t] = tr_frag_row<S_BROW>(bufB + t * S_BPLANE + offB[n], kk * 16 * S_BROW);
+                for (int n = 0; n < 2; ++n) fb[n][t] = tr_frag<S_BROW>(bufB + t * S_BPLANE + offB[n], kk * 16 * S_BROW);
             }
 #pragma unroll
             for (int m = 0; m < 4; ++m)

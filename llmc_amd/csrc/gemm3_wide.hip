@@ -21,8 +21,6 @@
 //     busiest XCD the fewest tiles that do work — the update is the upper triangle), as in sgemm_wide.hip.
 // LDS image of a plane's stage: 16 k-rows of 256 B, 64-B units XOR-swizzled by (k & 3) exactly as k_gemm3s's B planes (the swizzle
 // is applied to the DMA's per-lane source column; ds_read_b64_tr_b16 fragment reads undo it).
-#include <type_traits>
-
 #include "mfma_common.h"
 #include "sgemm.h"
 
@@ -50,20 +48,6 @@ struct G3wArgs {
     int upper;                        // c_upper_only
 };
 
-template <int I, int N, typename F> __device__ __forceinline__ void gfor(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        gfor<I + 1, N>(f);
-    }
-}
-template <int N> __device__ __forceinline__ void g_vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-
-__device__ __forceinline__ s16x8 g_frag(LDS_AS char* p, int imm) {
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(p + imm));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(p + imm + 4 * G_ROW));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
 __global__ __launch_bounds__(256, 2) void k_gemm3w(const G3wArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem_g[];
     const int w = blockIdx.x;
@@ -77,21 +61,14 @@ __global__ __launch_bounds__(256, 2) void k_gemm3w(const G3wArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wv >> 1, wn = wv & 1;
-    auto mk = [](const void* p, uint32_t bytes) {
-        const uint64_t u = (uint64_t)p;
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u);
-        const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(u >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), (short)0,
-                                                 __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
-    };
 #if defined(G3W_DBG) && G3W_DBG == 1      // lab (tools/probes/g3w_lab.sh): every tile reads the panels of tile (0, 0) — wrong results, perfect L2 reuse
-    const auto dA = mk(a.PA, a.bytesP);
-    const auto dB = mk(a.PB, a.bytesP);
+    const auto dA = uniform_rsrc(a.PA, a.bytesP);
+    const auto dB = uniform_rsrc(a.PB, a.bytesP);
 #else
-    const auto dA = mk(a.PA + (int64_t)ti * G_B, a.bytesP);
-    const auto dB = mk(a.PB + (int64_t)tj * G_B, a.bytesP);
+    const auto dA = uniform_rsrc(a.PA + (int64_t)ti * G_B, a.bytesP);
+    const auto dB = uniform_rsrc(a.PB + (int64_t)tj * G_B, a.bytesP);
 #endif
-    const auto dC = mk(a.C + (int64_t)ti * G_B * a.ldc + (int64_t)tj * G_B, a.bytesC);
+    const auto dC = uniform_rsrc(a.C + (int64_t)ti * G_B * a.ldc + (int64_t)tj * G_B, a.bytesC);
     LDS_AS char* lds = (LDS_AS char*)smem_g;
     const uint32_t lds0 = (uint32_t)(uintptr_t)lds;
     const int nst = a.nst;
@@ -104,10 +81,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm3w(const G3wArgs a) {
         const int cs = (((c >> 2) ^ r) << 2) | (c & 3);          // the row's 64-B units XOR (k & 3), k & 3 = r
         vo = (uint32_t)r * a.row2 + (uint32_t)cs * 16u;
     }
-    auto dma = [&](const decltype(dA)& d, uint32_t so, uint32_t dst) {
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds"
-                     :: "v"(vo), "s"(d), "s"(dst), "s"(so) : "memory");
-    };
     auto issue = [&](int j, uint32_t slot_off) {
         const uint32_t k0 = (uint32_t)j * G_K;
 #pragma unroll
@@ -115,7 +88,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm3w(const G3wArgs a) {
             const int op = t / 3, pl = t % 3;
             const uint32_t so = (uint32_t)pl * a.ps2 + (k0 + 4u * (uint32_t)wv) * a.row2;
             const uint32_t dst = lds0 + slot_off + (uint32_t)op * G_OPND + (uint32_t)pl * G_PLANE + (uint32_t)wv * 1024u;
-            if (op == 0) dma(dA, so, dst); else dma(dB, so, dst);
+            if (op == 0) dma16_to(dA, vo, so, dst); else dma16_to(dB, vo, so, dst);
         }
     };
 
@@ -136,8 +109,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm3w(const G3wArgs a) {
         constexpr int grp = f >> 2, e = f & 3, b = e & 1;                  // groups: {B hi, A lo} {A hi, B lo} {A mid, B mid}
         constexpr bool isA = grp == 0 ? e >= 2 : e < 2;
         constexpr int pl = grp == 0 ? (isA ? 2 : 0) : grp == 1 ? (isA ? 0 : 2) : 1;
-        if constexpr (isA) fa[S][b][pl] = g_frag(base + offA[b], pl * G_PLANE);
-        else fb[S][b][pl] = g_frag(base + offB[b], pl * G_PLANE);
+        if constexpr (isA) fa[S][b][pl] = tr_frag<G_ROW>(base + offA[b], pl * G_PLANE);
+        else fb[S][b][pl] = tr_frag<G_ROW>(base + offB[b], pl * G_PLANE);
     };
 
     f32x16 acc[2][2];
@@ -152,9 +125,9 @@ __global__ __launch_bounds__(256, 2) void k_gemm3w(const G3wArgs a) {
     issue(0, 0);
     issue(1, G_SLOT);
     issue(2, 2 * G_SLOT);
-    g_vm_wait<12>();
+    vm_wait<12>();
     __builtin_amdgcn_s_barrier();
-    gfor<0, 12>([&](auto fc) { rd(std::integral_constant<int, 0>{}, fc, lds); });
+    static_for<0, 12>([&](auto fc) { rd(std::integral_constant<int, 0>{}, fc, lds); });
     __builtin_amdgcn_sched_barrier(0);
 
     // Stage j (fragment set S = j & 1), its planes in slot j % 3: this wave's pieces of stage j + 1 have landed (stage j + 2's six may
@@ -171,7 +144,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm3w(const G3wArgs a) {
     uint32_t cur = 0;                                   // byte offset of stage j's slot
     auto stage = [&](auto setc, auto cbc, auto youngc, int j) {
         constexpr int S = decltype(setc)::value, CB = decltype(cbc)::value, YOUNG = decltype(youngc)::value;
-        if (j + 2 < nst) g_vm_wait<YOUNG>(); else g_vm_wait<0>();
+        if (j + 2 < nst) vm_wait<YOUNG>(); else vm_wait<0>();
         __builtin_amdgcn_s_barrier();
 #if !(defined(G3W_DBG) && G3W_DBG == 2)    // lab: no operand traffic after the prologue
         if (j + 3 < nst) issue(j + 3, cur);
@@ -179,7 +152,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm3w(const G3wArgs a) {
         const uint32_t nxt = cur + G_SLOT == G_LDS ? 0u : cur + G_SLOT;
         LDS_AS char* nb = lds + nxt;
         __builtin_amdgcn_sched_barrier(0);
-        gfor<0, 24>([&](auto ic) {
+        static_for<0, 24>([&](auto ic) {
             constexpr int i = decltype(ic)::value, q = i >> 2, m = (i >> 1) & 1, n = i & 1;
             constexpr int TA = q == 0 ? 2 : q == 1 ? 0 : q == 2 ? 1 : q == 3 ? 1 : 0;      // lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi
             constexpr int TB = q == 0 ? 0 : q == 1 ? 2 : q == 2 ? 1 : q == 3 ? 0 : q == 4 ? 1 : 0;

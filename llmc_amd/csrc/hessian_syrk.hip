@@ -32,7 +32,6 @@
 // Lab builds (-DLLMC_LAB, tools/probes only; never in the shipped library): ablation instantiations (wrong results
 // by design) and the LLMC_SYRK_* environment overrides.
 #include <stdlib.h>
-#include <type_traits>
 #include "common.h"
 #include "mfma_common.h"
 
@@ -82,13 +81,6 @@ __host__ __device__ inline TileIdx decode_tile(int ti, int nb) {
     return t;
 }
 
-__device__ __forceinline__ s16x8 tr_frag(LDS_AS char* p, int imm0) {
-    // two 4-token transposed reads -> 8 consecutive tokens of one channel per lane
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(p + imm0));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(p + imm0 + 4 * TM * 2));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
 struct SyrkSample {
     uint64_t base;   // device address of the sample's first row
     uint32_t T;      // its tokens (> 0)
@@ -123,11 +115,6 @@ struct SyrkArgs {
     SyrkSample smp[SYRK_MAX_SAMPLES];
 };
 
-template <int N> __device__ __forceinline__ void dma_wait_upto() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void lds_wait_all() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
 // -----------------------------------------------------------------------------------------------------
 // k_syrk4 — one wave per SIMD: 4 waves as 2(M) x 2(N), each wave 128 x 128 = 4 x 4 MFMA 32x32x16 accumulators
 // (256 accumulator registers; the kernel uses the whole 512-entry file of its SIMD).
@@ -153,34 +140,11 @@ static constexpr int S4_STAGE = 2 * S4_PANEL;         // 32 KiB
 static constexpr int NSLOT = 4;
 static_assert(NSLOT * S4_TOK == GROUP_TOK, "a group is one turn of the ring");
 
-template <int I, int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-// One LDS-DMA piece: LDS destination = immediate DST + the wave's KiB offset (an SGPR; M0 is written by the add and
-// is not live across statements in this kernel), source = rsrc.base + soff + voff[lane]; soff then advances by
-// `inc` for the piece's next stage — written a whole stage before it is read again, so no hazard padding.
-template <int DST, bool LOAD, bool ADVANCE>
-__device__ __forceinline__ void dma16w(i32x4 rsrc, uint32_t voff, uint32_t& soff, uint32_t inc, uint32_t wvoff) {
-    if constexpr (LOAD && ADVANCE)
-        asm volatile("s_add_u32 m0, %3, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %0 offen lds\n\ts_add_u32 %0, %0, %5"
-                     : "+s"(soff) : "v"(voff), "s"(rsrc), "s"(wvoff), "n"(DST), "s"(inc) : "memory", "scc");
-    else if constexpr (LOAD)
-        asm volatile("s_add_u32 m0, %3, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %0 offen lds"
-                     : "+s"(soff) : "v"(voff), "s"(rsrc), "s"(wvoff), "n"(DST) : "memory", "scc");
-    else
-        asm volatile("s_add_u32 m0, %1, %2\n\ts_nop 0\n\ts_add_u32 %0, %0, %3"
-                     : "+s"(soff) : "s"(wvoff), "n"(DST), "s"(inc) : "memory", "scc");
-}
-
 template <int DT, int ABL>
 __global__ __launch_bounds__(S4_THREADS) void k_syrk4(const SyrkArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     LDS_AS char* lds = (LDS_AS char*)smem;
-    if ((uint32_t)(uintptr_t)lds != 0u) __builtin_trap();   // DMA destinations are immediates: dynamic LDS must start at 0
+    require_lds_base_zero(lds);
     constexpr int PER = 8;                  // LDS-DMA pieces per stage per wave (4 per panel)
     constexpr bool DMA = !(ABL & 1);
     constexpr bool RD = !(ABL & 2);
@@ -350,8 +314,8 @@ __global__ __launch_bounds__(S4_THREADS) void k_syrk4(const SyrkArgs a) {
                 constexpr int d = decltype(dc)::value;
                 if constexpr (DMA) {
                     constexpr int DSTB = SL * S4_STAGE + (d >> 2) * S4_PANEL + (d & 3) * 4 * 1024;
-                    if constexpr (d < 4) dma16w<DSTB, LOAD, ADV>(rs, vA, sA[d & 3], stage_bytes, wvoff);
-                    else dma16w<DSTB, LOAD, ADV>(rs, vB, sB[d & 3], stage_bytes, wvoff);
+                    if constexpr (d < 4) dma16_imm<DSTB, LOAD, ADV>(rs, vA, sA[d & 3], stage_bytes, wvoff);
+                    else dma16_imm<DSTB, LOAD, ADV>(rs, vB, sB[d & 3], stage_bytes, wvoff);
                 }
             };
             s16x8 fa0[4], fb0[4], fa1[4], fb1[4];
@@ -385,9 +349,9 @@ __global__ __launch_bounds__(S4_THREADS) void k_syrk4(const SyrkArgs a) {
                 constexpr int f = decltype(fc)::value;
                 if constexpr (RD) {
                     constexpr int IMM = (SL & 1) * S4_STAGE;
-                    if constexpr (f == 0) fa[0] = tr_frag(lds + offA[SL >> 1][0], IMM + kk * 16 * TM * 2);
-                    else if constexpr (f <= 4) fb[f - 1] = tr_frag(lds + offBu[SL >> 1][f - 1], IMM + kk * 16 * TM * 2);
-                    else fa[f - 4] = tr_frag(lds + offA[SL >> 1][f - 4], IMM + kk * 16 * TM * 2);
+                    if constexpr (f == 0) fa[0] = tr_frag<TM * 2>(lds + offA[SL >> 1][0], IMM + kk * 16 * TM * 2);
+                    else if constexpr (f <= 4) fb[f - 1] = tr_frag<TM * 2>(lds + offBu[SL >> 1][f - 1], IMM + kk * 16 * TM * 2);
+                    else fa[f - 4] = tr_frag<TM * 2>(lds + offA[SL >> 1][f - 4], IMM + kk * 16 * TM * 2);
                 }
             };
             // one burst: 16 MFMAs on (fa, fb). Behind MFMA i: i in {0,1,2,4,5,6,8,9} -> the next fragment of slice kk
@@ -440,7 +404,7 @@ __global__ __launch_bounds__(S4_THREADS) void k_syrk4(const SyrkArgs a) {
                           J == 0 ? cur : nxt, nothing);
                     // this wave's pieces of stage st+1 have landed (NSLOT-2 later stages may still be in flight);
                     // every wave has read the whole of stage st once its lgkmcnt(0) is behind the barrier
-                    dma_wait_upto<(NSLOT - 2) * (DWG ? PER / 2 : PER)>();
+                    vm_wait<(NSLOT - 2) * (DWG ? PER / 2 : PER)>();
                     lds_wait_all();
                     __builtin_amdgcn_sched_barrier(0);
                     __builtin_amdgcn_s_barrier();
@@ -527,11 +491,11 @@ __global__ __launch_bounds__(S4_THREADS) void k_syrk4(const SyrkArgs a) {
             // prologue: stages 0 .. NSLOT-2 and the A half of stage NSLOT-1 (all of group 0) requested, stage 0 published
             if (dwave) {      // A halves only (see offBu)
                 static_for<0, NSLOT>([&](auto slc) { static_for<0, 4>([&](auto dc) { piece(slc, dc, dA); }); });
-                dma_wait_upto<(NSLOT - 2) * (PER / 2) + PER / 2>();
+                vm_wait<(NSLOT - 2) * (PER / 2) + PER / 2>();
             } else {
                 static_for<0, NSLOT - 1>([&](auto slc) { static_for<0, 8>([&](auto dc) { piece(slc, dc, dA); }); });
                 static_for<0, 4>([&](auto dc) { piece(std::integral_constant<int, NSLOT - 1>{}, dc, dA); });
-                dma_wait_upto<(NSLOT - 2) * PER + PER / 2>();
+                vm_wait<(NSLOT - 2) * PER + PER / 2>();
             }
             __builtin_amdgcn_s_barrier();
             static_for<0, 8>([&](auto fc) { frag(std::integral_constant<int, 0>{}, 0, fc, fa0, fb0); });
@@ -587,7 +551,7 @@ __global__ __launch_bounds__(S4_THREADS) void k_syrk4(const SyrkArgs a) {
                     }
         }
         // the stores share the VM counter with the next unit's LDS-DMA: drain them (and the trailing requests)
-        dma_wait_all();
+        vm_wait<0>();
     }
 }
 

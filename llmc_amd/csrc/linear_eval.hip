@@ -11,7 +11,6 @@
 // products through gemm6 at the end of the file). Persistent grids; each XCD works on one block of tiles per round
 // (lin_tile_order), so the workgroups that share an L2 share few operand panels at the same K position.
 #include <stdlib.h>
-#include <type_traits>
 #include "common.h"
 #include "mfma_common.h"
 #include "sgemm.h"
@@ -107,18 +106,8 @@ __global__ __launch_bounds__(LTHREADS) void k_linear_eval(LinArgs a) {
     const int rowA = (wm * 128 + (lane & 31)) * (LBK * 2);
     const int rowB = (wn * 64 + (lane & 31)) * (LBK * 2);
 
-    i32x4 rx, rw;
-    {
-        const int64_t xb = a.N * row_bytes, wb = a.R * row_bytes;
-        rx[0] = (int)(uint32_t)(uintptr_t)a.X;
-        rx[1] = (int)((uint32_t)((uintptr_t)a.X >> 32) & 0xffffu);
-        rx[2] = (int)(uint32_t)(xb > 0xffffffffll ? 0xffffffffll : xb);
-        rx[3] = 0x00020000;
-        rw[0] = (int)(uint32_t)(uintptr_t)a.W;
-        rw[1] = (int)((uint32_t)((uintptr_t)a.W >> 32) & 0xffffu);
-        rw[2] = (int)(uint32_t)(wb > 0xffffffffll ? 0xffffffffll : wb);
-        rw[3] = 0x00020000;
-    }
+    const int64_t xb = a.N * row_bytes, wb = a.R * row_bytes;
+    const i32x4 rx = rsrc_words<CLAMP_4GIB>(a.X, xb), rw = rsrc_words<CLAMP_4GIB>(a.W, wb);
 
     const int nk = (int)(a.K / LBK);
 
@@ -149,7 +138,7 @@ __global__ __launch_bounds__(LTHREADS) void k_linear_eval(LinArgs a) {
         int cur = 0;
         stage(0, 0);
         for (int ks = 0; ks < nk; ++ks) {
-            dma_wait_all();
+            vm_wait<0>();
             __syncthreads();
             if (ks + 1 < nk) stage(cur ^ 1, ks + 1);
             LDS_AS char* pa = lds + cur * LSTAGE + rowA;
@@ -233,33 +222,13 @@ static constexpr int L4_STAGE = 2 * L4_PANEL;
 static constexpr int L4_RING = 4;
 static constexpr int L4_LDS = L4_RING * L4_STAGE;      // 128 KiB
 
-template <int I, int N, typename F> __device__ __forceinline__ void l4_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        l4_static_for<I + 1, N>(f);
-    }
-}
-
-template <int DST>
-__device__ __forceinline__ void l4_dma(i32x4 rsrc, uint32_t voff, uint32_t& soff, uint32_t wvoff, uint32_t adv) {
-    asm volatile("s_add_u32 m0, %3, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %0 offen lds\n\ts_add_u32 %0, %0, %5"
-                 : "+s"(soff) : "v"(voff), "s"(rsrc), "s"(wvoff), "n"(DST), "s"(adv) : "memory", "scc");
-}
-template <int DST>
-__device__ __forceinline__ void l4_dma_at(i32x4 rsrc, uint32_t voff, uint32_t soff, uint32_t wvoff) {
-    asm volatile("s_add_u32 m0, %3, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %0 offen lds"
-                 :: "s"(soff), "v"(voff), "s"(rsrc), "s"(wvoff), "n"(DST) : "memory", "scc");
-}
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 // (a, b) rounded to bf16 (RNE, one v_cvt_pk_bf16_f32) and widened back
 __device__ __forceinline__ f32x2 round_pair_bf16(f32x2 v) {
-    const bf16x2_t h = __builtin_convertvector(v, bf16x2_t);
+    const bf16x2 h = __builtin_convertvector(v, bf16x2);
     uint32_t u;
     __builtin_memcpy(&u, &h, 4);
     return f32x2{__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u)};
 }
-template <int N> __device__ __forceinline__ void l4_vmwait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // STAGE_Y: loss mode with the Y0 tile staged through LDS: 1 row-major Y0 (a.y0_lds), 2 tile-blocked Y0 (a.yblk)
 template <int DT, int STAGE_Y>
@@ -267,7 +236,7 @@ __global__ __launch_bounds__(L4_THREADS) void k_linear_eval4(LinArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* red = (float*)(smem + L4_LDS);
     LDS_AS char* lds = (LDS_AS char*)smem;
-    if ((uint32_t)(uintptr_t)lds != 0u) __builtin_trap();   // DMA destinations are immediates
+    require_lds_base_zero(lds);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wv >> 1, wn = wv & 1;
@@ -296,24 +265,16 @@ __global__ __launch_bounds__(L4_THREADS) void k_linear_eval4(LinArgs a) {
                 offB[pr][kk][m] = pr * 2 * L4_STAGE + L4_PANEL + rb * 64 + ((cl ^ ((rb >> 2) & 3)) << 4);
             }
 
-    i32x4 rx, rw;
-    {
-        const int64_t xb = a.N * row_bytes, wb = a.R * row_bytes;
-        rx[0] = (int)(uint32_t)(uintptr_t)a.X;
-        rx[1] = (int)((uint32_t)((uintptr_t)a.X >> 32) & 0xffffu);
-        rx[2] = (int)(uint32_t)(xb > 0xffffffffll ? 0xffffffffll : xb);
-        rx[3] = 0x00020000;
-        rw[0] = (int)(uint32_t)(uintptr_t)a.W;
-        rw[1] = (int)((uint32_t)((uintptr_t)a.W >> 32) & 0xffffu);
-        rw[2] = (int)(uint32_t)(wb > 0xffffffffll ? 0xffffffffll : wb);
-        rw[3] = 0x00020000;
-    }
+    const int64_t xb = a.N * row_bytes, wb = a.R * row_bytes;
+    const i32x4 rx = rsrc_words<CLAMP_4GIB>(a.X, xb), rw = rsrc_words<CLAMP_4GIB>(a.W, wb);
     i32x4 ry = rx;
     if (a.mode == 1) {
+        // words 0..2 of rsrc_words<CLAMP_4GIB>(a.Y0, yb) written in place, word 3 stays rx's: taken from the helper's vector
+        // they give the STAGE_Y variants another register allocation and instruction order (profiles/mfma_helpers_refactor.txt)
         const int64_t yb = a.yblk ? (int64_t)a.ntm * a.ntn * 131072 : a.N * a.R * 2;
         ry[0] = (int)(uint32_t)(uintptr_t)a.Y0;
         ry[1] = (int)((uint32_t)((uintptr_t)a.Y0 >> 32) & 0xffffu);
-        ry[2] = (int)(uint32_t)(yb > 0xffffffffll ? 0xffffffffll : yb);
+        ry[2] = (int)clamp_u32(yb);
     }
     for (int round = 0; round < a.nrounds; ++round) {
         int tm, tn;
@@ -365,8 +326,8 @@ __global__ __launch_bounds__(L4_THREADS) void k_linear_eval4(LinArgs a) {
             constexpr int SL = decltype(slc)::value;
             constexpr int d = decltype(dc)::value;
             constexpr int DSTB = SL * L4_STAGE + (d >> 2) * L4_PANEL + (d & 3) * 4 * 1024;
-            if constexpr (d < 4) l4_dma<DSTB>(rx, vA, sA[d & 3], wvoff, advA);
-            else l4_dma<DSTB>(rw, vB, sB[d & 3], wvoff, advB);
+            if constexpr (d < 4) dma16_imm<DSTB>(rx, vA, sA[d & 3], advA, wvoff);
+            else dma16_imm<DSTB>(rw, vB, sB[d & 3], advB, wvoff);
         };
         const uint32_t vy = (uint32_t)((((int64_t)tm * LT + 2 * wv + (lane >> 5)) * a.R + (int64_t)tn * LT + (lane & 31) * 8) * 2);
         const uint32_t advY = (uint32_t)(16 * a.R);        // 8 rows down per piece index
@@ -386,8 +347,8 @@ __global__ __launch_bounds__(L4_THREADS) void k_linear_eval4(LinArgs a) {
         // tile's contiguous 128 KiB -> LDS [I/8 * 32 KiB + wv * 8 KiB + I%8 KiB): 8 pieces of every wave per ring slot
         auto ypiece = [&](auto ic) {
             constexpr int I = decltype(ic)::value;
-            if constexpr (STAGE_Y == 2) l4_dma_at<(I >> 3) * 32768 + (I & 7) * 1024>(ry, vyb, (uint32_t)I * 1024u, wvoff * 8);
-            else l4_dma_at<I * 4096>(ry, vy, (uint32_t)I * advY, wvoff);
+            if constexpr (STAGE_Y == 2) dma_imm_at<(I >> 3) * 32768 + (I & 7) * 1024>(ry, vyb, (uint32_t)I * 1024u, wvoff * 8);
+            else dma_imm_at<I * 4096>(ry, vy, (uint32_t)I * advY, wvoff);
         };
         // REQ: what rides behind the MFMAs. 0 nothing, 1 operand pieces D0.. of slot dslc (the steady state),
         // 2 Y0 pieces D0..D0+3, 3 Y0 pieces D0..D0+7 and no fragment reads (the tile's very last burst)
@@ -395,7 +356,7 @@ __global__ __launch_bounds__(L4_THREADS) void k_linear_eval4(LinArgs a) {
                          auto dslc, auto d0c, auto reqc) {
             constexpr int D0 = decltype(d0c)::value;
             constexpr int REQ = decltype(reqc)::value;
-            l4_static_for<0, 16>([&](auto ic) {
+            static_for<0, 16>([&](auto ic) {
                 constexpr int i = decltype(ic)::value;
                 constexpr int mi = i >> 2, ni = (mi & 1) ? 3 - (i & 3) : (i & 3);
                 acc[mi][ni] = Mfma<DT>::run(fa[mi], fb[ni], acc[mi][ni]);
@@ -411,11 +372,11 @@ __global__ __launch_bounds__(L4_THREADS) void k_linear_eval4(LinArgs a) {
         constexpr std::integral_constant<int, 0> K0{};
         constexpr std::integral_constant<int, 1> K1{};
         if (ngroups > 0) {
-        l4_static_for<0, L4_RING - 1>([&](auto slc) { l4_static_for<0, 8>([&](auto dc) { piece(slc, dc); }); });
-        l4_static_for<0, 4>([&](auto dc) { piece(std::integral_constant<int, L4_RING - 1>{}, dc); });
-        l4_vmwait<(L4_RING - 2) * PER + PER / 2>();
+        static_for<0, L4_RING - 1>([&](auto slc) { static_for<0, 8>([&](auto dc) { piece(slc, dc); }); });
+        static_for<0, 4>([&](auto dc) { piece(std::integral_constant<int, L4_RING - 1>{}, dc); });
+        vm_wait<(L4_RING - 2) * PER + PER / 2>();
         __builtin_amdgcn_s_barrier();
-        l4_static_for<0, 8>([&](auto fc) { frag(std::integral_constant<int, 0>{}, K0, fc, fa0, fb0); });
+        static_for<0, 8>([&](auto fc) { frag(std::integral_constant<int, 0>{}, K0, fc, fa0, fb0); });
         }
         // one ring turn = 4 stages. The LAST turn of a tile (KIND 1) requests only what the tile still needs (the B half
         // of its final stage) and counts the VM counter down to 0, so the ring is quiet and free when the turn ends.
@@ -424,7 +385,7 @@ __global__ __launch_bounds__(L4_THREADS) void k_linear_eval4(LinArgs a) {
         // finds its reference tile in LDS.
         auto turn = [&](auto kindc) {
             constexpr int KIND = decltype(kindc)::value;
-            l4_static_for<0, L4_RING>([&](auto jc) {
+            static_for<0, L4_RING>([&](auto jc) {
                 constexpr int J = decltype(jc)::value;
                 constexpr int JN = (J + 1) % L4_RING, JP = (J + L4_RING - 1) % L4_RING;
                 // requests that may still be in flight when stage J + 1 must have landed
@@ -433,8 +394,8 @@ __global__ __launch_bounds__(L4_THREADS) void k_linear_eval4(LinArgs a) {
                 constexpr int R2 = KIND == 0 ? 1 : KIND == 1 ? 0 : J == 3 ? 3 : 2;
                 burst(fa0, fb0, fa1, fb1, jc, K1, std::integral_constant<int, JP>{},
                       std::integral_constant<int, R1 == 1 ? 4 : 8 * J - 4>{}, std::integral_constant<int, R1>{});
-                if constexpr (!(KIND == 2 && J == 3)) l4_vmwait<AHEAD>();
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                if constexpr (!(KIND == 2 && J == 3)) vm_wait<AHEAD>();
+                lds_wait_all();
                 __builtin_amdgcn_sched_barrier(0);
                 __builtin_amdgcn_s_barrier();
                 __builtin_amdgcn_sched_barrier(0);
@@ -444,7 +405,7 @@ __global__ __launch_bounds__(L4_THREADS) void k_linear_eval4(LinArgs a) {
         };
         for (int g = 0; g < ngroups - 1; ++g) turn(std::integral_constant<int, 0>{});
         if (ngroups > 0) turn(std::integral_constant<int, STAGE_Y != 0 ? 2 : 1>{});
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        lds_wait_all();
 #ifdef LLMC_LAB
         if (a.mode == 2) {   // lab (LLMC_LIN_ABL=1): the main loop alone, nothing stored
             __builtin_amdgcn_s_barrier();
@@ -456,7 +417,7 @@ __global__ __launch_bounds__(L4_THREADS) void k_linear_eval4(LinArgs a) {
             // loss epilogue: the Y0 tile (256 x 512 B) arrived in the ring during the last turn; every lane picks its 256
             // values with immediate-offset ds_read_u16. (Read straight from global, each of the 256 two-byte loads sat
             // behind its own s_waitcnt: ~40 % of the tile time.)
-            l4_vmwait<0>();
+            vm_wait<0>();
             if constexpr (STAGE_Y == 1) __builtin_amdgcn_s_barrier();   // blocked: a wave reads only what it requested itself
 #ifdef LLMC_LAB
             if (a.y0_lds == 2) { __syncthreads(); continue; }   // lab (LLMC_LIN_ABL=3): Y0 staged and waited for, not folded
@@ -472,7 +433,7 @@ __global__ __launch_bounds__(L4_THREADS) void k_linear_eval4(LinArgs a) {
             f32x2 lsum2 = {0.0f, 0.0f};      // even / odd accumulator registers, fused multiply-add in fp32
             auto fold = [&](auto maskedc) {
                 constexpr bool MASKED = decltype(maskedc)::value;
-                l4_static_for<0, 16>([&](auto mnc) {
+                static_for<0, 16>([&](auto mnc) {
                     constexpr int m = decltype(mnc)::value >> 2, n = decltype(mnc)::value & 3;
                     uint16_t yb[16];
                     if constexpr (STAGE_Y == 2) {
@@ -485,7 +446,7 @@ __global__ __launch_bounds__(L4_THREADS) void k_linear_eval4(LinArgs a) {
                             yb[8 + j] = (uint16_t)v1[j];
                         }
                     } else {
-                        l4_static_for<0, 16>([&](auto rc) {
+                        static_for<0, 16>([&](auto rc) {
                             constexpr int r = decltype(rc)::value;
                             constexpr int trow = m * 32 + (r & 3) + 8 * (r >> 2);
                             yb[r] = *(LDS_AS const uint16_t*)(lds + ybase + trow * 512 + n * 64);
@@ -493,7 +454,7 @@ __global__ __launch_bounds__(L4_THREADS) void k_linear_eval4(LinArgs a) {
                     }
                     __builtin_amdgcn_sched_barrier(0);   // 16 reads in flight, one wait (the scheduler pairs each read with its use)
                     // two values per step: one packed conversion per rounding, packed fp32 subtract / multiply-add
-                    l4_static_for<0, 8>([&](auto pc) {
+                    static_for<0, 8>([&](auto pc) {
                         constexpr int r = 2 * decltype(pc)::value;
                         constexpr int trow = m * 32 + (r & 3) + 8 * (r >> 2);      // r + 1 is the next row
                         f32x2 y0, y, d;
@@ -532,7 +493,7 @@ __global__ __launch_bounds__(L4_THREADS) void k_linear_eval4(LinArgs a) {
         if (a.mode == 3) {
             // gemm6 / split-K: C = csign * acc in fp32; a lane's 32 consecutive columns per row segment are one 128-B line
             float* const Cs = a.C + (int64_t)ks * a.N * a.ldc;
-            l4_static_for<0, 16>([&](auto mnc) {
+            static_for<0, 16>([&](auto mnc) {
                 constexpr int m = decltype(mnc)::value >> 2, n = decltype(mnc)::value & 3;
                 const int64_t col = (int64_t)tn * LT + wn * 128 + n * 32 + (lane & 31);
                 const int64_t tok0 = (int64_t)tm * LT + wm * 128 + m * 32 + 4 * (lane >> 5);
@@ -544,14 +505,14 @@ __global__ __launch_bounds__(L4_THREADS) void k_linear_eval4(LinArgs a) {
                     }
                 }
             });
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            vm_wait<0>();
             continue;
         }
         if (a.mode == 0 && a.yblk) {
             // tile-blocked output in fragment order: tile t = 128 KiB, wave wv = 32 KiB, piece I = (m*4 + n)*2 + v = 1 KiB,
             // lane = 16 B = acc[m][n][8v .. 8v+7] rounded (+ bias): one coalesced 16-B store per piece
             char* yt = a.Y + ((int64_t)t * 4 + wv) * 32768 + lane * 16;
-            l4_static_for<0, 16>([&](auto mnc) {
+            static_for<0, 16>([&](auto mnc) {
                 constexpr int m = decltype(mnc)::value >> 2, n = decltype(mnc)::value & 3;
                 const int64_t col = (int64_t)tn * LT + wn * 128 + n * 32 + (lane & 31);
                 const float b = (a.Y0 && col < a.R) ? load_as_f32(a.Y0, col, DT) : 0.0f;
@@ -568,7 +529,7 @@ __global__ __launch_bounds__(L4_THREADS) void k_linear_eval4(LinArgs a) {
                     *reinterpret_cast<uint4*>(yt + ((m * 4 + n) * 2 + v) * 1024) = ov;
                 }
             });
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            vm_wait<0>();
             continue;
         }
         if (a.mode == 0 && (a.R & 7) == 0 && (((uintptr_t)a.Y) & 15) == 0) {
@@ -577,11 +538,11 @@ __global__ __launch_bounds__(L4_THREADS) void k_linear_eval4(LinArgs a) {
             // 256-byte row segments per instruction. Two-byte global stores straight from the accumulators cost 0.65 ms on a
             // 65536 x 4096 output (0.90 against 1.22 PFLOP/s for the tile-blocked form, profiles/r04_linear_paths.txt).
             LDS_AS char* my = lds + wv * 32768;
-            l4_static_for<0, 16>([&](auto mnc) {
+            static_for<0, 16>([&](auto mnc) {
                 constexpr int m = decltype(mnc)::value >> 2, n = decltype(mnc)::value & 3;
                 const int64_t col = (int64_t)tn * LT + wn * 128 + n * 32 + (lane & 31);
                 const float b = (a.Y0 && col < a.R) ? load_as_f32(a.Y0, col, DT) : 0.0f;
-                l4_static_for<0, 16>([&](auto rc) {
+                static_for<0, 16>([&](auto rc) {
                     constexpr int r = decltype(rc)::value;
                     const int row = m * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                     const float y = acc[m][n][r] + b;
@@ -589,26 +550,25 @@ __global__ __launch_bounds__(L4_THREADS) void k_linear_eval4(LinArgs a) {
                         DT == LLMC_BF16 ? f32_to_bf16_bits(y) : f32_to_f16_bits(y);
                 });
             });
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the wave's own writes, before its own reads
+            lds_wait_all();      // the wave's own writes, before its own reads
             const int64_t tok0 = (int64_t)tm * LT + wm * 128, col0 = (int64_t)tn * LT + wn * 128;
 #pragma unroll 2
             for (int i = 0; i < 32; ++i) {
                 const int id = i * 64 + lane, row = id >> 4, c16 = id & 15;
-                typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-                const u32x4_t v = *(LDS_AS u32x4_t*)(my + row * 256 + c16 * 16);
+                const u32x4 v = *(LDS_AS u32x4*)(my + row * 256 + c16 * 16);
                 const int64_t tok = tok0 + row, col = col0 + c16 * 8;
-                if (tok < a.N && col < a.R) *reinterpret_cast<u32x4_t*>(a.Y + (tok * a.R + col) * 2) = v;
+                if (tok < a.N && col < a.R) *reinterpret_cast<u32x4*>(a.Y + (tok * a.R + col) * 2) = v;
             }
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();       // every wave is done with the ring before the next prologue refills it
             continue;
         }
         float lsum = 0.0f;
-        l4_static_for<0, 16>([&](auto mnc) {
+        static_for<0, 16>([&](auto mnc) {
             constexpr int m = decltype(mnc)::value >> 2, n = decltype(mnc)::value & 3;
             const int64_t col = (int64_t)tn * LT + wn * 128 + n * 32 + (lane & 31);
             const int64_t tok0 = (int64_t)tm * LT + wm * 128 + m * 32 + 4 * (lane >> 5);
-            l4_static_for<0, 16>([&](auto rc) {
+            static_for<0, 16>([&](auto rc) {
                 constexpr int r = decltype(rc)::value;
                 const int64_t tok = tok0 + (r & 3) + 8 * (r >> 2);
                 if (tok < a.N && col < a.R) {
@@ -631,7 +591,7 @@ __global__ __launch_bounds__(L4_THREADS) void k_linear_eval4(LinArgs a) {
             if (tid == 0) a.part[t] = (red[0] + red[1]) + (red[2] + red[3]);
             __syncthreads();
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // stores + trailing requests drain before the VM counter is counted again
+        vm_wait<0>();   // stores + trailing requests drain before the VM counter is counted again
     }
 }
 
@@ -900,14 +860,6 @@ extern "C" int llmc_test_linear_route(const int64_t* in, int32_t* out) {
 // block). k_gemm3 re-splits every operand element in every tile that uses it and reads a fragment from LDS per MFMA.
 namespace llmc {
 
-__device__ __forceinline__ void split3(float v, uint16_t (&pl)[3]) {
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        const uint16_t b = f32_to_bf16_bits(v);
-        pl[t] = b;
-        v = v - bf16_bits_to_f32(b);
-    }
-}
 // plane (0 hi, 1 mid, 2 lo) of stacked slice q on the A / B side; compile-time so that the unrolled loops index registers
 __device__ __forceinline__ constexpr int g6_plane(int side, int q) {
     return side ? (q == 1 ? 2 : (q == 2 || q == 4) ? 1 : 0) : (q == 0 ? 2 : (q == 2 || q == 3) ? 1 : 0);

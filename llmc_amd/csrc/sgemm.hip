@@ -6,13 +6,12 @@
 #include <assert.h>
 #include <stdlib.h>
 #include "sgemm.h"
+#include "mfma_common.h"
 
 namespace llmc {
 
 // tile edge GB = 128 and K-step GK = 16: sgemm.h
 static constexpr int GLD = 132;  // LDS row stride (floats): 16-B aligned rows, 2-way at most on transposing writes
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 struct Stage {
     float4 v[2];

@@ -3,8 +3,6 @@
 // (gptq_loop.hip). 256 threads work on one tile; `tid` is the thread's index among them and `smem` their Wide<MB>::LDS bytes.
 // The function synchronises with workgroup barriers: every wave of a workgroup that calls it must call it, with the same `nst`.
 #pragma once
-#include <type_traits>
-
 #include "mfma_common.h"
 #include "sgemm.h"
 
@@ -51,30 +49,15 @@ template <int MB> static inline void wide_operands(const SgemmArgs& a, WideArgs&
     w.tm = a.M / W::BM; w.tn = a.N / W_BN;
 }
 
-template <int I, int N, typename F> __device__ __forceinline__ void wfor(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        wfor<I + 1, N>(f);
-    }
-}
-template <int N> __device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-
 template <int MB>
 __device__ __forceinline__ void wide_tile(const WideArgs& a, const int ti, const int tj, char* smem, const int tid) {
     using W = Wide<MB>;
     const int lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wv >> 1, wn = wv & 1;
-    auto mk = [](const void* p, uint32_t bytes) {
-        const uint64_t u = (uint64_t)p;
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u);
-        const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(u >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), (short)0,
-                                                 __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
-    };
-    const auto dA = mk(a.A + (int64_t)ti * W::BM, a.bytesA);
-    const auto dB = mk(a.B + (int64_t)tj * W_BN, a.bytesB);
-    const auto dC = mk(a.C + (int64_t)ti * W::BM * a.ldc + (int64_t)tj * W_BN, a.bytesC);
+    const auto dA = uniform_rsrc(a.A + (int64_t)ti * W::BM, a.bytesA);
+    const auto dB = uniform_rsrc(a.B + (int64_t)tj * W_BN, a.bytesB);
+    const auto dC = uniform_rsrc(a.C + (int64_t)ti * W::BM * a.ldc + (int64_t)tj * W_BN, a.bytesC);
     LDS_AS char* lds = (LDS_AS char*)smem;
     const uint32_t lds0 = (uint32_t)(uintptr_t)lds;
     const int nst = a.nst;
@@ -83,22 +66,18 @@ __device__ __forceinline__ void wide_tile(const WideArgs& a, const int ti, const
     // (2q + e) * W_ROW; wave wv brings k-quad q = wv. The 256-wide A: one k-row (1 KiB) per piece at k * W_ROW, wave wv brings rows 4 wv ..
     const uint32_t voA = MB == 4 ? (uint32_t)lane * 16u : (uint32_t)(lane >> 5) * 2u * a.rowA + (uint32_t)(lane & 31) * 16u;
     const uint32_t voB = (uint32_t)(lane >> 5) * 2u * a.rowB + (uint32_t)(lane & 31) * 16u;
-    auto dma = [&](const decltype(dA)& d, uint32_t vo, uint32_t so, uint32_t dst) {
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds"
-                     :: "v"(vo), "s"(d), "s"(dst), "s"(so) : "memory");
-    };
     auto issue = [&](int j) {
         const uint32_t slot = lds0 + (uint32_t)(j & (W_SLOTS - 1)) * W::SLOT;
         const uint32_t k = (uint32_t)(j * W_K + 4 * wv);
         if constexpr (MB == 4) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) dma(dA, voA, (k + i) * a.rowA, slot + (uint32_t)(4 * wv + i) * W_ROW);
+            for (int i = 0; i < 4; ++i) dma16_to(dA, voA, (k + i) * a.rowA, slot + (uint32_t)(4 * wv + i) * W_ROW);
         } else {
 #pragma unroll
-            for (int e = 0; e < 2; ++e) dma(dA, voA, (k + e) * a.rowA, slot + (uint32_t)(2 * wv + e) * W_ROW);
+            for (int e = 0; e < 2; ++e) dma16_to(dA, voA, (k + e) * a.rowA, slot + (uint32_t)(2 * wv + e) * W_ROW);
         }
 #pragma unroll
-        for (int e = 0; e < 2; ++e) dma(dB, voB, (k + e) * a.rowB, slot + W::AB + (uint32_t)(2 * wv + e) * W_ROW);
+        for (int e = 0; e < 2; ++e) dma16_to(dB, voB, (k + e) * a.rowB, slot + W::AB + (uint32_t)(2 * wv + e) * W_ROW);
     };
 
     // ---- operand reads: pair kp of a stage = k-rows 2 kp (lanes 0-31) and 2 kp + 1 (lanes 32-63); two base registers per operand
@@ -135,7 +114,7 @@ __device__ __forceinline__ void wide_tile(const WideArgs& a, const int ti, const
     issue(2);
     vm_wait<2 * W::D>();
     __builtin_amdgcn_s_barrier();
-    wfor<0, MB + 2>([&](auto ic) { rd(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, ic); });
+    static_for<0, MB + 2>([&](auto ic) { rd(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, ic); });
     __builtin_amdgcn_sched_barrier(0);
 
     // One phase = 8 stages of 8 pairs of 2 MB MFMAs. Behind MFMA i of pair p: i < MB + 2 -> operand i of the next pair (pair 7: the
@@ -146,12 +125,12 @@ __device__ __forceinline__ void wide_tile(const WideArgs& a, const int ti, const
     constexpr int LASTI = 2 * MB - 1, CPER = 16 / (2 * MB);
     auto phase = [&](auto firstc, int j0) {
         constexpr bool FIRST = decltype(firstc)::value;
-        wfor<0, W_PHASE>([&](auto sc) {
+        static_for<0, W_PHASE>([&](auto sc) {
             constexpr int s = decltype(sc)::value, SL = s & (W_SLOTS - 1), SN = (s + 1) & (W_SLOTS - 1);
             const int j = j0 + s;
-            wfor<0, 8>([&](auto pc) {
+            static_for<0, 8>([&](auto pc) {
                 constexpr int p = decltype(pc)::value, c = p & 1;
-                wfor<0, 2 * MB>([&](auto ic) {
+                static_for<0, 2 * MB>([&](auto ic) {
                     constexpr int i = decltype(ic)::value, m = i >> 1, n = (m & 1) ? 1 - (i & 1) : (i & 1);
                     if constexpr (s == 0 && p == 0) {
                         // a phase's first product starts from +0 (inline constant: no zeroing); the previous phase's block is

@@ -16,7 +16,6 @@
 // The trailing update W[:, i2:] -= Err1 @ U[i1:i2, i2:] is gptq_loop.hip's: sgemm.hip's k-ordered fp32 fma chain.
 // Operation order is oracle/csrc/spqr_canon.c's (pinned bit-exactly against the reference: tests/golden/spqr.npz).
 #include <stdlib.h>
-#include <type_traits>
 #include "common.h"
 #include "sgemm.h"
 
@@ -41,13 +40,6 @@ struct SpqrBlockArgs {
     int use_mask;         // threshold finite
     float sqmin, sqmax, zqmin, zqmax;
 };
-
-template <int I, int N, typename F> __device__ __forceinline__ void sp_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        sp_static_for<I + 1, N>(f);
-    }
-}
 
 // lane po of every 16-lane row (ds_bpermute: po is a loop counter, the 16 steps of a stripe are a real loop — unrolled,
 // the 128 steps with their IEEE divisions and hoisted LDS reads spill hundreds of registers)
@@ -150,7 +142,7 @@ __global__ __launch_bounds__(SNT) void k_spqr_block(SpqrBlockArgs a) {
     float s = 1.0f, z = 0.0f;
     const float thr = a.threshold, qmin = a.qmin, qmax = a.qmax;
 
-    sp_static_for<0, 8>([&](auto ec) {
+    static_for<0, 8>([&](auto ec) {
         constexpr int E = decltype(ec)::value;
         if constexpr (E % M == 0) {
             if (16 * E < a.count) {
@@ -158,7 +150,7 @@ __global__ __launch_bounds__(SNT) void k_spqr_block(SpqrBlockArgs a) {
                 float mn, mx;
                 if (a.detect) {
                     Ext2 lo{INFINITY, INFINITY, 0}, hi{-INFINITY, -INFINITY, 0};
-                    sp_static_for<0, M>([&](auto tc) {
+                    static_for<0, M>([&](auto tc) {
                         constexpr int T = decltype(tc)::value;
 #pragma unroll 1
                         for (int po = 0; po < 16; ++po) {
@@ -177,7 +169,7 @@ __global__ __launch_bounds__(SNT) void k_spqr_block(SpqrBlockArgs a) {
                         qp_asym_nr(lmn, lmx, qmin, qmax, lsj[t], lzj[t]);
                         loo[t] = 0.0f;
                     }
-                    sp_static_for<0, M>([&](auto tc) {
+                    static_for<0, M>([&](auto tc) {
                         constexpr int T = decltype(tc)::value;
 #pragma unroll 1
                         for (int po = 0; po < 16; ++po) {
@@ -197,7 +189,7 @@ __global__ __launch_bounds__(SNT) void k_spqr_block(SpqrBlockArgs a) {
 #pragma unroll
                     for (int t = 0; t < M; ++t) mj[t] = (base - loo[t]) > thr ? 1.0f : 0.0f;
                     float sum_keep = 0.0f, n_keep = 0.0f;
-                    sp_static_for<0, M>([&](auto tc) {
+                    static_for<0, M>([&](auto tc) {
                         constexpr int T = decltype(tc)::value;
 #pragma unroll 1
                         for (int po = 0; po < 16; ++po) {

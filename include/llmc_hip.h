@@ -658,6 +658,70 @@ int llmc_quant_dynamic_cols_path(const void* W, int dt, int64_t R, int64_t K, in
 int llmc_hadamard(const void* x, void* y, int dt, int64_t outer, int64_t n, int64_t inner, const float* hadK, int K0,
                   double scale, llmc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Sparsification (llmc/compression/sparsification/wanda.py, magnitude.py)
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Wanda.get_row_scale (wanda.py:27-31): column sums of squares of X [N, K] (contiguous, dtype dt, N up to 2^31 rows).
+ * acc [K] fp32: acc[k] = sum_n fp32(x[n, k])^2, every square and every add rounded to fp32. init != 0: acc is written;
+ * else the batch is folded into it, acc[k] = acc[k] + batch[k]. out (optional, fp32 [K]): out[k] = acc[k] / (float)nsamples,
+ * one IEEE fp32 division: the reference's scaler_row (which takes the square root of the sum and squares it again before it
+ * divides: the same value up to those two roundings).
+ * Two stages, no float atomics. The order of summation is a function of (N, K, dt) alone, so equal calls give equal bits:
+ * the rows are cut into C = min(ceil(N / 64), max(1, 2048 / ceil(K / (64 * v)))) chunks of ceil(N / C) consecutive rows, v the
+ * elements of a 16-byte vector of dt; in a chunk starting at row r0, wave w of 4 sums the rows r0 + w, r0 + w + 4, ... in
+ * that order from 0, the chunk's value is ((s0 + s1) + s2) + s3, and the chunks are added in chunk order. The alignment of X
+ * changes the loads (16-byte vectors when K % v == 0 and X is 16-byte aligned), not this order.
+ * ws: llmc_col_sqsum_ws_bytes(N, K, dt) bytes (a pure host call; 0 for invalid arguments). */
+size_t llmc_col_sqsum_ws_bytes(int64_t N, int64_t K, int dt);
+int llmc_col_sqsum(const void* X, int dt, int64_t N, int64_t K, int init, float* acc, float* out, int64_t nsamples, void* ws,
+                   llmc_stream_t stream);
+
+/* Wanda.subset_transform's selection (wanda.py:46-56), in place on W [R, K] of dt with row stride ld >= K elements: a row is cut
+ * into groups of m consecutive columns, and in each group the n_prune elements of smallest metric become +0 of dt.
+ *   metric = fp32(|w|) * sqrtf(scaler_row[k]): exactly these two roundings (IEEE square root); scaler_row fp32 [K], null = the
+ *   multiplier 1. A NaN metric (inf * 0 included) orders after +inf whatever its sign bit; ties go by lower column first. This is
+ *   bit for bit the mask of torch.sort(metric, dim=-1, stable=True)[1][:, :n_prune] scattered back.
+ *   m == K is the reference's per-row mode; m in {2, 4, 8, 16} with K % m == 0 is n:m semi-structured pruning (zero n_prune of
+ *   every m); any other m returns LLMC_ENOTSUP.
+ * Elements that are kept retain their own bits (-0, infinities, NaN payloads); columns K .. ld - 1 are never touched. mask_out
+ * (optional): uint8 [R, K] contiguous, 1 where an element was pruned. n_prune == 0 touches no weight and clears mask_out;
+ * n_prune == m zeroes everything. No workspace, no allocation, stream-ordered.
+ * m == K reads W from HBM once and writes it once: the row and its 32-bit keys (the metric's bit pattern, NaN made the largest)
+ * wait in registers while a most-significant-digit radix select (digits of 11, 11 and 9 bits, LDS histograms) finds the key of rank n_prune - 1
+ * and the number of keys below it; a prefix count over the keys equal to it picks the first of them by column. Launch paths
+ * (llmc_prune_rows_path answers which one a call takes, or a negative LLMC_E*, without touching the GPU; llmc_prune_rows_paths
+ * is their number):
+ *   0  one wave per row, four rows per workgroup: rows of up to 256 16-byte vectors (K <= 2048 16-bit, 1024 fp32)
+ *   1  one 256-thread workgroup per row: up to 1024 vectors (K <= 8192 / 4096)
+ *   2  one 1024-thread workgroup per row: up to 8192 vectors, K <= 32768
+ *   3  m == K with operands that do not allow 16-byte vectors (W not 16-byte aligned, ld or K not a multiple of 16 bytes): the
+ *      same three structures one element per lane, K <= 32768
+ *   4  n:m, lane-local: a lane owns whole groups (one 16-byte vector, or m elements when m is wider); no LDS
+ *   5  n:m one element per lane, for the operands of path 3
+ * A row of more than 32768 columns with m == K returns LLMC_ENOTSUP (callers compose the reference's sequence).
+ * LLMC_EINVAL, before anything is launched: bad dt, null W, R or K < 1, ld < K, m in the list but not dividing K, n_prune
+ * outside [0, m]. */
+int llmc_prune_rows(void* W, int dt, int64_t R, int64_t K, int64_t ld, const float* scaler_row, int64_t n_prune, int64_t m,
+                    uint8_t* mask_out, llmc_stream_t stream);
+int llmc_prune_rows_paths(void);
+int llmc_prune_rows_path(int dt, int64_t R, int64_t K, int64_t ld, int64_t m, const void* W);
+
+/* Magnitude.subset_transform (magnitude.py:26-31), in place on the strided view W [R, K] (row stride ld >= K) of dt: with
+ * a = |W| over its R * K elements, thresh = the element of 0-based rank kth in ascending order (torch.sort(a.flatten())[0][kth]),
+ * written to thresh_out (optional, one element of dt), and every element with a <= thresh becomes +0: all ties of the threshold
+ * go, so at least kth + 1 zeros result. mask_out (optional): uint8 [R, K] contiguous, 1 where an element was zeroed. The weights
+ * are assumed to hold no NaN (a NaN would count as larger than every number and survive). R * K < 2^32.
+ * 16-bit dt: one pass builds a 32768-bin histogram of the sign-cleared bit patterns (per-workgroup LDS histograms merged into ws
+ * with integer atomics: exact, hence deterministic), one workgroup scans it for the bin of rank kth, one pass masks. F32: two
+ * 16-bit digits, a second histogram over the elements inside the first digit's bin. The call zeroes its own workspace; no host
+ * synchronisation. ws: llmc_magnitude_prune_ws_bytes(dt, R, K) bytes, 4-byte aligned (a pure host call; 0 for invalid arguments).
+ * LLMC_EINVAL, before anything is launched: bad dt, null W, R or K < 1, ld < K, kth outside [0, R * K) (the reference raises an
+ * IndexError at sparsity 1.0), a missing workspace. */
+size_t llmc_magnitude_prune_ws_bytes(int dt, int64_t R, int64_t K);
+int llmc_magnitude_prune(void* W, int dt, int64_t R, int64_t K, int64_t ld, int64_t kth, void* thresh_out, uint8_t* mask_out,
+                         void* ws, llmc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,13 @@ SIGNATURES = {
     'llmc_quant_dynamic_cols_paths': (_i32, []),
     'llmc_quant_dynamic_cols_path': (_i32, [_vp, _i32, _i64, _i64, _i64, _i64]),
     'llmc_hadamard': (_i32, [_vp, _vp, _i32, _i64, _i64, _i64, _vp, _i32, _f64, _vp]),
+    'llmc_col_sqsum_ws_bytes': (_sz, [_i64, _i64, _i32]),
+    'llmc_col_sqsum': (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp]),
+    'llmc_prune_rows': (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
+    'llmc_prune_rows_paths': (_i32, []),
+    'llmc_prune_rows_path': (_i32, [_i32, _i64, _i64, _i64, _i64, _vp]),
+    'llmc_magnitude_prune_ws_bytes': (_sz, [_i32, _i64, _i64]),
+    'llmc_magnitude_prune': (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     'llmc_test_sgemm': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                _i32, _i32, _vp]),
     'llmc_test_sgemm_phased': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -1,0 +1,3 @@
+from .base_blockwise_sparsification import BaseBlockwiseSparsification  # noqa: F401
+from .wanda import Wanda  # noqa: F401
+from .magnitude import Magnitude  # noqa: F401

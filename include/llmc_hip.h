@@ -722,6 +722,31 @@ size_t llmc_magnitude_prune_ws_bytes(int dt, int64_t R, int64_t K);
 int llmc_magnitude_prune(void* W, int dt, int64_t R, int64_t K, int64_t ld, int64_t kth, void* thresh_out, uint8_t* mask_out,
                          void* ws, llmc_stream_t stream);
 
+/* SparseGPT's fasterprune (Frantar & Alistarh 2023; the reference tree has no counterpart) in fp32 at blocksize 128: GPTQ's
+ * blocked column loop with the quantizer replaced by a mask. Every elementwise operation rounds once, no fma:
+ *   for i1 in 0, 128, ...: i2 = min(i1 + 128, K), count = i2 - i1, W1 = W[:, i1:i2] as it stands, d_c = Hinv[c][c]
+ *     unstructured (prune_m == 0): s = fl(fl(W1 W1) / fl(d d)) of the block-start weights, kth = (int64)((double)(R count) *
+ *       sparsity), thresh = the score of 0-based rank kth among the R * count scores, mask1 = s <= thresh (all ties go);
+ *     n:m (prune_m = m in {2, 4, 8, 16}): at every column i with i % m == 0 the scores of columns i .. i + m - 1 of the RUNNING
+ *       W1; in every row the prune_n lowest are masked, equal scores by lower column;
+ *     per column c = i1 + i: q = mask1 ? +0 : w, Wout[:, c] = q, mask[:, c] = mask1, diff = fl(w - q),
+ *       losses[:, c] = fl(fl(diff diff) / fl(d d)), err = fl(diff / d), W1[:, j] = fl(W1[:, j] - fl(err Hinv[c][i1 + j])), j > i;
+ *     W[:, i2:] -= Err1 @ Hinv[i1:i2, i2:] on sgemm.hip's k-ordered fma chain.
+ * W [R, K] fp32 running weights (in/out, GPTQ's convention: a block's own columns keep their block-start values), Hinv [K, K]
+ * fp32 upper factor, Wout [R, K] fp32; losses [R, K] fp32 and mask [R, K] uint8 may be NULL. A pruned weight is +0, a kept one
+ * keeps its bits. sparsity 0 prunes the minimum-score element(s) of each block, as the published code does. Non-finite weights
+ * are outside the contract (they index nothing out of bounds). Per block: score + first-digit histogram, scan, second-digit
+ * histogram, scan (integer atomics: exact, deterministic; the threshold never leaves the device), the block kernel, the trailing
+ * sgemm; n:m skips the select. Runs on `stream`, complete in stream order; allocates nothing; no host synchronisation.
+ * ws: llmc_sparsegpt_prune_ws_bytes(R, K) bytes, 256-B aligned (a pure host call; 0 for non-positive sizes).
+ * Before anything is launched, LLMC_EINVAL: null W / Hinv / Wout / ws, R or K < 1, R >= 2^24, blocksize != 128, sparsity outside
+ * [0, 1) when unstructured, prune_n outside [0, m]; LLMC_ENOTSUP: K % 4 != 0, m not in {2, 4, 8, 16}, K % m != 0.
+ * Bit-exact against tests/sparsegpt_oracle.py. */
+size_t llmc_sparsegpt_prune_ws_bytes(int64_t R, int64_t K);
+int llmc_sparsegpt_prune(float* W, const float* Hinv, int64_t R, int64_t K, double sparsity, int64_t prune_n,
+                         int64_t prune_m, float* Wout, float* losses, uint8_t* mask, int blocksize, void* ws,
+                         llmc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,8 @@ SIGNATURES = {
     'llmc_prune_rows_path': (_i32, [_i32, _i64, _i64, _i64, _i64, _vp]),
     'llmc_magnitude_prune_ws_bytes': (_sz, [_i32, _i64, _i64]),
     'llmc_magnitude_prune': (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    'llmc_sparsegpt_prune_ws_bytes': (_sz, [_i64, _i64]),
+    'llmc_sparsegpt_prune': (_i32, [_vp, _vp, _i64, _i64, _f64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _vp]),
     'llmc_test_sgemm': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                _i32, _i32, _vp]),
     'llmc_test_sgemm_phased': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -1,3 +1,4 @@
 from .base_blockwise_sparsification import BaseBlockwiseSparsification  # noqa: F401
 from .wanda import Wanda  # noqa: F401
 from .magnitude import Magnitude  # noqa: F401
+from .sparsegpt import SparseGPT  # noqa: F401

@@ -6,7 +6,8 @@ method's `subset_transform`, and the block's output becomes the next block's inp
 Config (the `sparse` section, configs/sparsification/methods/Wanda/wanda.yml):
   sparsity_out            False (default): the next block's input is this block's DENSE output (the forward that captured the
                           inputs); True: a second forward runs after pruning and feeds the next block.
-  weight.sparsity         the fraction of every row (Wanda) or of every tensor (Magnitude) that is zeroed.
+  weight.sparsity         the fraction of every row (Wanda), of every tensor (Magnitude) or of every 128-column block of a
+                          tensor (SparseGPT) that is zeroed.
   weight.n_prune_layers   read and kept, as the reference does (ShortGPT's key; that method is not built here).
   weight.sparsity_type    new key. 'unstructured' (default), or 'n:m' — zero n of every m consecutive input channels, m in
                           {2, 4, 8, 16} ('2:4' is the pattern the CDNA sparse matrix instructions consume). With n:m, `sparsity`

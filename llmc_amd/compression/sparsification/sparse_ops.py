@@ -10,6 +10,8 @@ prune_rows_composed  that sequence from torch ops on the device: a stable sort p
                    back to, announced on stderr, for a row too long to stay resident (LLMC_ENOTSUP: K > 32768 with m == K).
 magnitude_prune    in place: the global |w| threshold of rank kth and w[|w| <= thresh] = 0 (magnitude.py:26-31).
 path               the launch path prune_rows takes, by name (a pure host call).
+sparsegpt_prune    SparseGPT's blocked column loop on an upper factor of the inverse Hessian (csrc/sparsegpt_loop.hip): mask by
+                   score w^2 / d^2, the pruning error fed to the later columns. Timings: profiles/sparsegpt.txt.
 
 Dispatch: the kernel measured 0.04x - 0.15x of the composition's time per row and 0.002x - 0.007x for 2:4 at every shape timed
 (bf16 4096 x 4096, 1024 x 4096, 14336 x 4096, 4096 x 14336; profiles/prune.txt, tools/bench_prune.py), magnitude_prune 0.05x and
@@ -161,3 +163,48 @@ def magnitude_prune(w, kth, want_mask=False):
     if op is not w:
         w.copy_(op)
     return thresh, mask
+
+
+SPARSEGPT_BLOCKSIZE = 128          # csrc/sparsegpt_loop.hip: GBS
+
+
+def sparsegpt_prune(W, Hinv, sparsity=None, nm=None, want_losses=False, want_mask=False):
+    """SparseGPT's blocked column loop (csrc/sparsegpt_loop.hip, llmc_sparsegpt_prune). W [R, K] contiguous fp32 on the GPU,
+    OVERWRITTEN with the running weights (GPTQ's convention); Hinv [K, K] contiguous fp32, the upper factor U with H^-1 = U^T U.
+    Exactly one of sparsity (a float in [0, 1): per 128-column block, every score <= the score of rank int(R * count * sparsity)
+    is pruned) and nm = (n, m) with m in {2, 4, 8, 16} (n of every m consecutive columns, scored on the running weights).
+    -> (Wout fp32 [R, K], losses fp32 [R, K] | None, mask uint8 [R, K] | None). Stream-ordered: nothing is read on the host."""
+    if (sparsity is None) == (nm is None):
+        raise ValueError('sparsegpt_prune takes exactly one of sparsity and nm')
+    if W.dim() != 2 or W.shape[0] < 1 or W.shape[1] < 1:
+        raise ValueError('sparsegpt_prune takes a non-empty 2-D [R, K] weight')
+    R, K = W.shape
+    if tuple(Hinv.shape) != (K, K):
+        raise ValueError(f'sparsegpt_prune: Hinv is {tuple(Hinv.shape)}, W has {K} columns')
+    if W.dtype != torch.float32 or Hinv.dtype != torch.float32 or not W.is_contiguous() or not Hinv.is_contiguous():
+        raise ValueError('sparsegpt_prune: W and Hinv must be contiguous fp32 (the kernel reads row-major [R, K] and [K, K])')
+    n = m = 0
+    if nm is None:
+        sparsity = float(sparsity)
+        if not 0.0 <= sparsity < 1.0:
+            raise ValueError(f'sparsegpt_prune: sparsity = {sparsity} outside [0, 1)')
+    else:
+        n, m = (int(v) for v in nm)
+        sparsity = 0.0
+        if m not in NM_GROUPS:
+            raise NotImplementedError(f'sparsegpt_prune: m is one of {NM_GROUPS}, not {m}')
+        if not 0 <= n <= m:
+            raise ValueError(f'sparsegpt_prune: n = {n} outside [0, {m}]')
+        if K % m:
+            raise NotImplementedError(f'sparsegpt_prune: m = {m} does not divide K = {K}')
+    if K % 4:
+        raise NotImplementedError(f'sparsegpt_prune: K = {K} must be a multiple of 4 (the trailing update\'s GEMM)')
+    _ffi.require_gpu(W, Hinv)
+    L = _ffi.lib()
+    Wout = torch.empty_like(W)
+    losses = torch.empty_like(W) if want_losses else None
+    mask = torch.empty((R, K), dtype=torch.uint8, device=W.device) if want_mask else None
+    ws = _ffi.workspace(L.llmc_sparsegpt_prune_ws_bytes(R, K), W.device)
+    _ffi.check(L.llmc_sparsegpt_prune(_ffi.ptr(W), _ffi.ptr(Hinv), R, K, sparsity, n, m, _ffi.ptr(Wout), _ffi.ptr(losses),
+                                      _ffi.ptr(mask), SPARSEGPT_BLOCKSIZE, _ffi.ptr(ws), _ffi.stream()), 'llmc_sparsegpt_prune')
+    return Wout, losses, mask

@@ -165,7 +165,7 @@ def magnitude_prune(w, kth, want_mask=False):
     return thresh, mask
 
 
-SPARSEGPT_BLOCKSIZE = 128          # csrc/sparsegpt_loop.hip: GBS
+SPARSEGPT_BLOCKSIZE = 128          # csrc/col_block.h: CB_BS
 
 
 def sparsegpt_prune(W, Hinv, sparsity=None, nm=None, want_losses=False, want_mask=False):

@@ -11,6 +11,7 @@
 // lane's registers end up holding exactly `tmp` (the weight of each column at the time it was visited).
 // Trailing update W[:, i2:] -= Err1 @ U[i1:i2, i2:] runs on the fp32 MFMA pipe (sgemm.hip) with the
 // k-ordered fma chain that reproduces the reference's CPU sgemm bit for bit.
+// (The other row-resident column loops, spqr_loop.hip and sparsegpt_loop.hip, share this scaffold through col_block.h.)
 #include "gptq_block_kernels.h"
 #include "pipe_lanes.h"
 

@@ -6,9 +6,10 @@
 //                          registers between its load and its store; the k-th order statistic comes from a most-significant-
 //                          digit radix select over LDS histograms, ties by a prefix count in column order.
 //   llmc_magnitude_prune   global |w| threshold of rank kth and w[|w| <= thresh] = 0 (magnitude.py:26-31): a 32768-bin histogram
-//                          of the sign-cleared bit patterns, a one-workgroup scan, a masking pass.
+//                          of the sign-cleared bit patterns, a one-workgroup scan (radix_select.h), a masking pass.
 // All data passes are HBM-bound; DESIGN.md holds the byte counts they are measured against.
 #include "common.h"
+#include "radix_select.h"
 
 namespace llmc {
 namespace {
@@ -533,18 +534,12 @@ void launch_nm(void* W, int64_t R, int64_t K, int64_t ld, int m, const float* sr
 // ================================================================================================================================
 // global magnitude pruning
 // ================================================================================================================================
-constexpr int MG_BINS = 32768;                 // 15 bits: a sign-cleared 16-bit pattern, or the upper half of a sign-cleared fp32 one
-constexpr int MG_LOW_BINS = 65536;             // fp32, second digit
-constexpr int MG_T = 1024;
-// workspace, in uint32 words: [0, MG_BINS) first histogram, [MG_BINS, MG_BINS + MG_LOW_BINS) fp32 second histogram, then
-// state[0] = bin of the first digit, state[1] = rank left inside it, state[2] = threshold key
-constexpr int MG_STATE = MG_BINS + MG_LOW_BINS;
-constexpr int MG_WORDS = MG_STATE + 4;
-
-__global__ __launch_bounds__(MG_T) void k_mag_zero(uint32_t* __restrict__ ws) {
-    for (int i = blockIdx.x * MG_T + threadIdx.x; i < MG_WORDS; i += gridDim.x * MG_T) ws[i] = 0;
+// The select and its workspace are radix_select.h's; the workspace is fresh memory, zeroed here.
+__global__ __launch_bounds__(RS_T) void k_mag_zero(uint32_t* __restrict__ ws) {
+    for (int i = blockIdx.x * RS_T + threadIdx.x; i < RS_WORDS; i += gridDim.x * RS_T) ws[i] = 0;
 }
 
+// the select key: the sign-cleared bit pattern
 template <typename T> __device__ __forceinline__ uint32_t abs_bits(T v);
 template <> __device__ __forceinline__ uint32_t abs_bits<f16_t>(f16_t v) { return v.u & 0x7FFFu; }
 template <> __device__ __forceinline__ uint32_t abs_bits<bf16_t>(bf16_t v) { return v.u & 0x7FFFu; }
@@ -594,85 +589,48 @@ __device__ __forceinline__ void mag_walk(T* __restrict__ W, int64_t R, int64_t K
     }
 }
 
-// first digit: a histogram per workgroup in LDS (128 KiB), merged into ws with integer atomics — exact, so deterministic
+// first digit (the whole key of a 16-bit dtype)
 template <typename T, int VEC>
-__global__ __launch_bounds__(MG_T) void k_mag_hist(T* __restrict__ W, int64_t R, int64_t K, int64_t ld, uint32_t* __restrict__ ws) {
+__global__ __launch_bounds__(RS_T) void k_mag_hist(T* __restrict__ W, int64_t R, int64_t K, int64_t ld, uint32_t* __restrict__ ws) {
     extern __shared__ uint32_t s_bins[];
-    for (int i = threadIdx.x; i < MG_BINS; i += MG_T) s_bins[i] = 0;
+    rs_clear_bins(s_bins);
     __syncthreads();
+    const auto count = rs_count<sizeof(T) != 4>(s_bins);
     mag_walk<T, VEC, false>(W, R, K, ld, nullptr, 0, [&](T& v) {
-        const uint32_t a = abs_bits<T>(v);
-        atomicAdd(&s_bins[sizeof(T) == 4 ? (a >> 16) : a], 1u);
+        count(abs_bits<T>(v));
         return false;
     });
-    __syncthreads();
-    for (int i = threadIdx.x; i < MG_BINS; i += MG_T) {
-        const uint32_t n = s_bins[i];
-        if (n) atomicAdd(&ws[i], n);
-    }
+    rs_merge_bins(s_bins, ws);
 }
 
-// fp32, second digit: only the elements whose upper half is the first digit's bin count
+// fp32, second digit
 template <int VEC>
 __global__ __launch_bounds__(256) void k_mag_hist_low(float* __restrict__ W, int64_t R, int64_t K, int64_t ld,
                                                       uint32_t* __restrict__ ws) {
-    const uint32_t hi = ws[MG_STATE];
+    const auto count = rs_count_low(ws);
     mag_walk<float, VEC, false>(W, R, K, ld, nullptr, 0, [&](float& v) {
-        const uint32_t a = abs_bits<float>(v);
-        if ((a >> 16) == hi) atomicAdd(&ws[MG_BINS + (a & 0xFFFFu)], 1u);
+        count(abs_bits<float>(v));
         return false;
     });
 }
 
-// one workgroup: the bin that holds the rank. second == 0: rank `kth` in hist[0, MG_BINS); writes state[0], state[1], and for a
-// 16-bit dtype the threshold. second == 1: rank state[1] in the low histogram; threshold = state[0] << 16 | bin.
-__global__ __launch_bounds__(MG_T) void k_mag_scan(uint32_t* __restrict__ ws, uint32_t kth, int second, int dt,
+// a 16-bit dtype is finished after the first digit: its bin is the threshold. The histograms are not cleared: a call zeroes them.
+__global__ __launch_bounds__(RS_T) void k_mag_scan(uint32_t* __restrict__ ws, uint32_t kth, int second, int dt,
                                                    void* __restrict__ thresh_out) {
-    __shared__ uint32_t s_w[MG_T / 64];
-    const uint32_t* hist = ws + (second ? MG_BINS : 0);
-    const int per = (second ? MG_LOW_BINS : MG_BINS) / MG_T;
-    const uint32_t rank = second ? ws[MG_STATE + 1] : kth;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int b0 = threadIdx.x * per;
-    uint32_t sum = 0;
-    for (int i = 0; i < per; ++i) sum += hist[b0 + i];
-    uint32_t incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t n = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += n;
-    }
-    if (lane == 63) s_w[wv] = incl;
-    __syncthreads();
-    uint32_t base = 0;
-    for (int w = 0; w < wv; ++w) base += s_w[w];
-    uint32_t excl = base + incl - sum;
-    if (excl <= rank && rank < excl + sum) {
-        int b = b0;
-        for (;; ++b) {
-            const uint32_t n = hist[b];
-            if (rank < excl + n) break;
-            excl += n;
+    rs_scan<false>(ws, kth, second, [&](int digit, uint32_t v) {
+        if (digit == 1) {
+            if (thresh_out) *(uint32_t*)thresh_out = v;
+        } else if (dt != LLMC_F32) {
+            ws[RS_STATE + 2] = v;
+            if (thresh_out) *(uint16_t*)thresh_out = (uint16_t)v;
         }
-        if (!second) {
-            ws[MG_STATE] = (uint32_t)b;
-            ws[MG_STATE + 1] = rank - excl;
-            if (dt != LLMC_F32) {
-                ws[MG_STATE + 2] = (uint32_t)b;
-                if (thresh_out) *(uint16_t*)thresh_out = (uint16_t)b;
-            }
-        } else {
-            const uint32_t thr = (ws[MG_STATE] << 16) | (uint32_t)b;
-            ws[MG_STATE + 2] = thr;
-            if (thresh_out) *(uint32_t*)thresh_out = thr;
-        }
-    }
+    });
 }
 
 template <typename T, int VEC>
 __global__ __launch_bounds__(256) void k_mag_mask(T* __restrict__ W, int64_t R, int64_t K, int64_t ld, const uint32_t* __restrict__ ws,
                                                   uint8_t* __restrict__ mask, int mask_vec) {
-    const uint32_t thr = ws[MG_STATE + 2];
+    const uint32_t thr = ws[RS_STATE + 2];
     mag_walk<T, VEC, true>(W, R, K, ld, mask, mask_vec, [&](T& v) {
         const bool cut = abs_bits<T>(v) <= thr;
         if (cut) v = zero_of<T>();
@@ -687,19 +645,19 @@ int magnitude_launch(void* W, int dt, int64_t R, int64_t K, int64_t ld, uint32_t
     const int cus = device_cu_count();
     const int mask_vec = ((uintptr_t)mask & 3) == 0;
     const dim3 stream_grid((unsigned)capped_grid(vecs, 256, (int64_t)cus * 16));
-    hipLaunchKernelGGL(k_mag_zero, dim3(16), dim3(MG_T), 0, st, ws);
+    hipLaunchKernelGGL(k_mag_zero, dim3(16), dim3(RS_T), 0, st, ws);
     LLMC_LAUNCH_CHECK();
-    if (int rc = ensure_dynamic_lds((const void*)k_mag_hist<T, VEC>, MG_BINS * 4)) return rc;
-    // a workgroup merges up to MG_BINS counters into ws: no more workgroups than have 4 elements per bin to count, one per CU at most
-    hipLaunchKernelGGL((k_mag_hist<T, VEC>), dim3((unsigned)capped_grid(vecs * VEC, (int64_t)MG_BINS * 4, cus)), dim3(MG_T),
-                       MG_BINS * 4, st, (T*)W, R, K, ld, ws);
+    if (int rc = ensure_dynamic_lds((const void*)k_mag_hist<T, VEC>, RS_BINS * 4)) return rc;
+    // a workgroup merges up to RS_BINS counters into ws: no more workgroups than have 4 elements per bin to count, one per CU at most
+    hipLaunchKernelGGL((k_mag_hist<T, VEC>), dim3((unsigned)capped_grid(vecs * VEC, (int64_t)RS_BINS * 4, cus)), dim3(RS_T),
+                       RS_BINS * 4, st, (T*)W, R, K, ld, ws);
     LLMC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_mag_scan, dim3(1), dim3(MG_T), 0, st, ws, kth, 0, dt, thresh_out);
+    hipLaunchKernelGGL(k_mag_scan, dim3(1), dim3(RS_T), 0, st, ws, kth, 0, dt, thresh_out);
     LLMC_LAUNCH_CHECK();
     if constexpr (sizeof(T) == 4) {
         hipLaunchKernelGGL((k_mag_hist_low<VEC>), stream_grid, dim3(256), 0, st, (float*)W, R, K, ld, ws);
         LLMC_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_mag_scan, dim3(1), dim3(MG_T), 0, st, ws, kth, 1, dt, thresh_out);
+        hipLaunchKernelGGL(k_mag_scan, dim3(1), dim3(RS_T), 0, st, ws, kth, 1, dt, thresh_out);
         LLMC_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL((k_mag_mask<T, VEC>), stream_grid, dim3(256), 0, st, (T*)W, R, K, ld, (const uint32_t*)ws, mask, mask_vec);
@@ -784,7 +742,7 @@ extern "C" int llmc_prune_rows(void* W, int dt, int64_t R, int64_t K, int64_t ld
 
 extern "C" size_t llmc_magnitude_prune_ws_bytes(int dt, int64_t R, int64_t K) {
     if (!dtype_ok(dt) || R <= 0 || K <= 0) return 0;
-    return (size_t)MG_WORDS * sizeof(uint32_t);
+    return (size_t)RS_WORDS * sizeof(uint32_t);
 }
 
 extern "C" int llmc_magnitude_prune(void* W, int dt, int64_t R, int64_t K, int64_t ld, int64_t kth, void* thresh_out,

@@ -2,37 +2,21 @@
 // with the quantizer replaced by a mask. The reference tree has no counterpart; include/llmc_hip.h states the arithmetic and
 // tests/sparsegpt_oracle.py restates it in numpy, which the kernel matches bit for bit.
 //
-// Same ownership as spqr_loop.hip: a wave owns 4 rows, 16 lanes per row, lane p owns columns p, p+16, ..., p+112 of the
-// 128-column block, U[i1:i2, i1:i2] staged in LDS. Per block:
+// Blocks, ownership and the trailing update are col_block.h's. Per block:
 //   unstructured  the score s = fl(fl(w w) / fl(d d)) of every element of the [R, count] panel as the block finds it; the score
-//                 of 0-based rank kth = int(R count sparsity) by a two-digit radix select over the score's bit pattern (never
-//                 negative: it orders like an unsigned integer) — k_sg_hist (upper 15 bits: one LDS histogram per workgroup,
-//                 merged with integer atomics, exact and so deterministic), k_sg_scan, k_sg_hist_low (lower 16 bits of the
-//                 elements in the chosen bin), k_sg_scan. The threshold stays in the workspace; the block kernel reads it there
-//                 and masks every s <= thresh. The idea is prune.hip's magnitude select; its kernels stay as they are.
+//                 of 0-based rank kth = int(R count sparsity) by radix_select.h's two-digit select over the score's bit pattern
+//                 (never negative: it orders like an unsigned integer) — k_sg_hist, k_sg_scan, k_sg_hist_low, k_sg_scan. The
+//                 threshold stays in the workspace; the block kernel reads it there and masks every s <= thresh.
 //   n:m           no select. Since m divides 16 and a group starts at a column i with i % m == 0, its m columns sit in m
 //                 adjacent lanes of the row at one register index: at the group's first column every lane scores its RUNNING
 //                 weight and ranks it among the m lanes (lower score first, equal scores by lower column) by m cross-lane reads.
 //   per column    q = masked ? +0 : w, err = fl(fl(w - q) / d), loss = fl(fl(diff diff) / fl(d d)),
 //                 w_j = fl(w_j - fl(err U[c][j])) for the later columns of the block: one rounding per op, no fma.
-// The trailing update W[:, i2:] -= Err1 @ U[i1:i2, i2:] is gptq_loop.hip's: sgemm.hip's k-ordered fp32 fma chain.
-#include "common.h"
-#include "sgemm.h"
+#include "col_block.h"
+#include "radix_select.h"
 
 namespace llmc {
 namespace {
-
-constexpr int GBS = 128;   // blocksize
-constexpr int GNT = 256;   // threads per workgroup of the block kernel: 4 waves x 4 rows
-
-constexpr int SG_BINS = 32768;             // first digit: bits 30..16 of the score
-constexpr int SG_LOW_BINS = 65536;         // second digit: bits 15..0
-constexpr int SG_T = 1024;
-// select workspace behind Err, in uint32 words: [0, SG_BINS) first histogram, [SG_BINS, SG_BINS + SG_LOW_BINS) second histogram,
-// then state[0] = bin of the first digit, state[1] = rank left inside it, state[2] = threshold key. Zeroed once per call; a scan
-// clears the histogram it has read, so the next block finds it empty.
-constexpr int SG_STATE = SG_BINS + SG_LOW_BINS;
-constexpr int SG_WORDS = SG_STATE + 4;
 
 // the select key of a weight: the bits of its score. dd = fl(d d). The sign bit is cleared so that a NaN score of either sign
 // still names a bin inside the histogram (non-finite weights are outside the contract; they must not index out of bounds).
@@ -58,66 +42,25 @@ __device__ __forceinline__ void sg_walk(const float* __restrict__ W, const float
     }
 }
 
-__global__ __launch_bounds__(SG_T) void k_sg_hist(const float* __restrict__ W, const float* __restrict__ U, int64_t R, int K, int i1,
+__global__ __launch_bounds__(RS_T) void k_sg_hist(const float* __restrict__ W, const float* __restrict__ U, int64_t R, int K, int i1,
                                                   int count, uint32_t* __restrict__ ws) {
     extern __shared__ uint32_t s_bins[];
-    __shared__ float s_dd[GBS];
-    for (int i = threadIdx.x; i < SG_BINS; i += SG_T) s_bins[i] = 0;
-    sg_walk(W, U, R, K, i1, count, s_dd, [&](uint32_t key) { atomicAdd(&s_bins[key >> 16], 1u); });
-    __syncthreads();
-    for (int i = threadIdx.x; i < SG_BINS; i += SG_T) {
-        const uint32_t n = s_bins[i];
-        if (n) atomicAdd(&ws[i], n);
-    }
+    __shared__ float s_dd[CB_BS];
+    rs_clear_bins(s_bins);
+    sg_walk(W, U, R, K, i1, count, s_dd, rs_count<false>(s_bins));          // the barrier behind s_dd covers the clearing
+    rs_merge_bins(s_bins, ws);
 }
 
 __global__ __launch_bounds__(256) void k_sg_hist_low(const float* __restrict__ W, const float* __restrict__ U, int64_t R, int K, int i1,
                                                      int count, uint32_t* __restrict__ ws) {
-    __shared__ float s_dd[GBS];
-    const uint32_t hi = ws[SG_STATE];
-    sg_walk(W, U, R, K, i1, count, s_dd, [&](uint32_t key) {
-        if ((key >> 16) == hi) atomicAdd(&ws[SG_BINS + (key & 0xFFFFu)], 1u);
-    });
+    __shared__ float s_dd[CB_BS];
+    sg_walk(W, U, R, K, i1, count, s_dd, rs_count_low(ws));
 }
 
-// one workgroup: the bin that holds the rank, then the histogram is cleared. second == 0: rank `kth` in the first histogram ->
-// state[0], state[1]. second == 1: rank state[1] in the second -> state[2] = state[0] << 16 | bin.
-__global__ __launch_bounds__(SG_T) void k_sg_scan(uint32_t* __restrict__ ws, uint32_t kth, int second) {
-    __shared__ uint32_t s_w[SG_T / 64];
-    uint32_t* hist = ws + (second ? SG_BINS : 0);
-    const int per = (second ? SG_LOW_BINS : SG_BINS) / SG_T;
-    const uint32_t rank = second ? ws[SG_STATE + 1] : kth;
-    const uint32_t hi = second ? ws[SG_STATE] : 0u;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int b0 = threadIdx.x * per;
-    uint32_t sum = 0;
-    for (int i = 0; i < per; ++i) sum += hist[b0 + i];
-    uint32_t incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t n = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += n;
-    }
-    if (lane == 63) s_w[wv] = incl;
-    __syncthreads();
-    uint32_t base = 0;
-    for (int w = 0; w < wv; ++w) base += s_w[w];
-    uint32_t excl = base + incl - sum;
-    if (excl <= rank && rank < excl + sum) {          // one thread: the bins are its own
-        int b = b0;
-        for (; b < b0 + per - 1; ++b) {
-            const uint32_t n = hist[b];
-            if (rank < excl + n) break;
-            excl += n;
-        }
-        if (!second) {
-            ws[SG_STATE] = (uint32_t)b;
-            ws[SG_STATE + 1] = rank - excl;
-        } else {
-            ws[SG_STATE + 2] = (hi << 16) | (uint32_t)b;
-        }
-    }
-    for (int i = 0; i < per; ++i) hist[b0 + i] = 0;
+// the select's words lie behind Err and are zeroed once per call: every scan clears the histogram it has read, so the next block
+// finds it empty. The threshold stays in state[2], where the block kernel reads it.
+__global__ __launch_bounds__(RS_T) void k_sg_scan(uint32_t* __restrict__ ws, uint32_t kth, int second) {
+    rs_scan<true>(ws, kth, second, [](int, uint32_t) {});
 }
 
 struct SgBlockArgs {
@@ -132,47 +75,10 @@ struct SgBlockArgs {
     int K, i1, count, prune_n;
 };
 
-// lane po of every 16-lane row (ds_bpermute, as in spqr_loop.hip: the 16 steps of a stripe are a real loop)
-__device__ __forceinline__ float sg_bcast(float v, int po) {
-    const int src = ((int)(threadIdx.x & 48) | po) << 2;
-    return __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(v)));
-}
-
 // M = 0: unstructured (mask from the block-start scores and the selected threshold); M in {2, 4, 8, 16}: prune_n of every M
 template <int M>
-__global__ __launch_bounds__(GNT) void k_sparsegpt_block(SgBlockArgs a) {
-    __shared__ __attribute__((aligned(16))) float Us[GBS * GBS];   // Us[i][p*8 + e] = U[i1+i][i1+p+16e] above the diagonal, else 0
-    __shared__ float dg[GBS];
-    const int tid = threadIdx.x;
-    {
-        constexpr int NV = GBS * GBS / 4 / GNT;
-        float4 v[NV];
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int idx = tid + GNT * j;
-            const int i = idx >> 5, c4 = (idx & 31) * 4;
-            v[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (i < a.count && c4 < a.count) v[j] = *reinterpret_cast<const float4*>(a.U + (int64_t)(a.i1 + i) * a.K + a.i1 + c4);
-        }
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int idx = tid + GNT * j;
-            const int i = idx >> 5, c4 = (idx & 31) * 4;
-            const float vv[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int c = c4 + t;
-                if (c == i) dg[i] = i < a.count ? vv[t] : 1.0f;
-                Us[i * GBS + (c & 15) * 8 + (c >> 4)] = c > i ? vv[t] : 0.0f;
-            }
-        }
-    }
-    __syncthreads();
-
-    const int lane = tid & 63;
-    const int p = lane & 15;
-    const int64_t row = ((int64_t)blockIdx.x * (GNT / 64) + (tid >> 6)) * 4 + (lane >> 4);
-    const bool active = row < a.R;
+__global__ __launch_bounds__(CB_NT) void k_sparsegpt_block(SgBlockArgs a) {
+#include "col_block_stage.h"
 
     float w[8], wf[8];                     // running weights; the weight as its own column step found it
     unsigned mk = 0;                       // bit e: column p + 16 e is pruned
@@ -208,8 +114,7 @@ __global__ __launch_bounds__(GNT) void k_sparsegpt_block(SgBlockArgs a) {
                         int rank = 0;
 #pragma unroll
                         for (int t = 0; t < M; ++t) {
-                            const int src = ((int)(tid & 48) | (gb + t)) << 2;
-                            const uint32_t kt = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)key);
+                            const uint32_t kt = __float_as_uint(row_lane(__uint_as_float(key), gb + t));
                             rank += (kt < key || (kt == key && t < tm)) ? 1 : 0;
                         }
                         if (gb == po && rank < a.prune_n) mk |= 1u << E;
@@ -219,14 +124,9 @@ __global__ __launch_bounds__(GNT) void k_sparsegpt_block(SgBlockArgs a) {
                 const float wo = w[E];
                 const float q = ((mk >> E) & 1u) ? 0.0f : wo;
                 const float diff = wo - q;
-                const float e1 = sg_bcast(diff / dE, po);
+                const float e1 = row_lane(diff / dE, po);
                 if (p == po) wf[E] = wo;
-                const float* ur = us + i * GBS;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float t = e1 * ur[e];
-                    w[e] = w[e] - t;
-                }
+                col_rank1(w, e1, us, i);
             }
         }
     });
@@ -247,7 +147,7 @@ __global__ __launch_bounds__(GNT) void k_sparsegpt_block(SgBlockArgs a) {
             if (a.losses) a.losses[o] = (diff * diff) / (d * d);
             if (a.mask) a.mask[o] = cut ? 1 : 0;
         }
-        a.Err[row * GBS + c] = err;
+        a.Err[row * CB_BS + c] = err;
     }
 }
 
@@ -258,7 +158,7 @@ using namespace llmc;
 
 extern "C" size_t llmc_sparsegpt_prune_ws_bytes(int64_t R, int64_t K) {
     if (R <= 0 || K <= 0) return 0;
-    return (size_t)R * GBS * sizeof(float) + (size_t)SG_WORDS * sizeof(uint32_t);
+    return (size_t)R * CB_BS * sizeof(float) + (size_t)RS_WORDS * sizeof(uint32_t);
 }
 
 extern "C" int llmc_sparsegpt_prune(float* W, const float* Hinv, int64_t R, int64_t K, double sparsity, int64_t prune_n,
@@ -266,7 +166,7 @@ extern "C" int llmc_sparsegpt_prune(float* W, const float* Hinv, int64_t R, int6
                                     llmc_stream_t stream) {
     LLMC_REQUIRE(W && Hinv && Wout && ws && R > 0 && K > 0, "sparsegpt_prune: null/empty argument");
     LLMC_REQUIRE(R < (1ll << 24) && K < (1ll << 30), "sparsegpt_prune: R below 2^24, K below 2^30");
-    LLMC_REQUIRE(blocksize == GBS, "sparsegpt_prune: blocksize must be 128");
+    LLMC_REQUIRE(blocksize == CB_BS, "sparsegpt_prune: blocksize must be 128");
     const bool nm = prune_m != 0;
     if (!nm) {
         LLMC_REQUIRE(sparsity >= 0.0 && sparsity < 1.0, "sparsegpt_prune: sparsity outside [0, 1)");
@@ -287,53 +187,41 @@ extern "C" int llmc_sparsegpt_prune(float* W, const float* Hinv, int64_t R, int6
     }
     hipStream_t st = (hipStream_t)stream;
     float* Err = (float*)ws;
-    uint32_t* sel = (uint32_t*)(Err + R * GBS);
+    uint32_t* sel = (uint32_t*)(Err + R * CB_BS);
     const int cus = device_cu_count();
     if (!nm) {
-        if (int rc = ensure_dynamic_lds((const void*)k_sg_hist, SG_BINS * 4)) return rc;
-        LLMC_HIP_CHECK(hipMemsetAsync(sel, 0, (size_t)SG_WORDS * sizeof(uint32_t), st));
+        if (int rc = ensure_dynamic_lds((const void*)k_sg_hist, RS_BINS * 4)) return rc;
+        LLMC_HIP_CHECK(hipMemsetAsync(sel, 0, (size_t)RS_WORDS * sizeof(uint32_t), st));
     }
-    for (int64_t i1 = 0; i1 < K; i1 += GBS) {
-        const int count = (int)(K - i1 < GBS ? K - i1 : GBS);
+    return col_blocks(W, Hinv, Err, R, K, st, [&](int i1, int count) {
         if (!nm) {
             const int64_t numel = R * count;
             const uint32_t kth = (uint32_t)(int64_t)((double)numel * sparsity);
             // 8 elements per thread: the walk is a chain of dependent loads, so the panel is spread over many workgroups (one per CU
             // at most); a workgroup merges only the bins it filled, and the scores of a panel share a few exponents
-            hipLaunchKernelGGL(k_sg_hist, dim3((unsigned)capped_grid(numel, (int64_t)SG_T * 8, cus)), dim3(SG_T), SG_BINS * 4, st,
-                               (const float*)W, Hinv, R, (int)K, (int)i1, count, sel);
+            hipLaunchKernelGGL(k_sg_hist, dim3((unsigned)capped_grid(numel, (int64_t)RS_T * 8, cus)), dim3(RS_T), RS_BINS * 4, st,
+                               (const float*)W, Hinv, R, (int)K, i1, count, sel);
             LLMC_LAUNCH_CHECK();
-            hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(SG_T), 0, st, sel, kth, 0);
+            hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(RS_T), 0, st, sel, kth, 0);
             LLMC_LAUNCH_CHECK();
             hipLaunchKernelGGL(k_sg_hist_low, dim3((unsigned)capped_grid(numel, 256 * 8, (int64_t)cus * 8)), dim3(256), 0, st,
-                               (const float*)W, Hinv, R, (int)K, (int)i1, count, sel);
+                               (const float*)W, Hinv, R, (int)K, i1, count, sel);
             LLMC_LAUNCH_CHECK();
-            hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(SG_T), 0, st, sel, kth, 1);
+            hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(RS_T), 0, st, sel, kth, 1);
             LLMC_LAUNCH_CHECK();
         }
         SgBlockArgs a;
-        a.W = W; a.U = Hinv; a.Wout = Wout; a.losses = losses; a.mask = mask; a.Err = Err; a.state = sel + SG_STATE;
-        a.R = R; a.K = (int)K; a.i1 = (int)i1; a.count = count; a.prune_n = (int)prune_n;
-        const dim3 grid((unsigned)ceil_div64(R, GNT / 16));
+        a.W = W; a.U = Hinv; a.Wout = Wout; a.losses = losses; a.mask = mask; a.Err = Err; a.state = sel + RS_STATE;
+        a.R = R; a.K = (int)K; a.i1 = i1; a.count = count; a.prune_n = (int)prune_n;
+        const dim3 grid((unsigned)ceil_div64(R, CB_NT / 16));
         switch ((int)prune_m) {
-            case 0: hipLaunchKernelGGL((k_sparsegpt_block<0>), grid, dim3(GNT), 0, st, a); break;
-            case 2: hipLaunchKernelGGL((k_sparsegpt_block<2>), grid, dim3(GNT), 0, st, a); break;
-            case 4: hipLaunchKernelGGL((k_sparsegpt_block<4>), grid, dim3(GNT), 0, st, a); break;
-            case 8: hipLaunchKernelGGL((k_sparsegpt_block<8>), grid, dim3(GNT), 0, st, a); break;
-            default: hipLaunchKernelGGL((k_sparsegpt_block<16>), grid, dim3(GNT), 0, st, a); break;
+            case 0: hipLaunchKernelGGL((k_sparsegpt_block<0>), grid, dim3(CB_NT), 0, st, a); break;
+            case 2: hipLaunchKernelGGL((k_sparsegpt_block<2>), grid, dim3(CB_NT), 0, st, a); break;
+            case 4: hipLaunchKernelGGL((k_sparsegpt_block<4>), grid, dim3(CB_NT), 0, st, a); break;
+            case 8: hipLaunchKernelGGL((k_sparsegpt_block<8>), grid, dim3(CB_NT), 0, st, a); break;
+            default: hipLaunchKernelGGL((k_sparsegpt_block<16>), grid, dim3(CB_NT), 0, st, a); break;
         }
         LLMC_LAUNCH_CHECK();
-        const int64_t i2 = i1 + count;
-        if (i2 < K) {   // W[:, i2:] -= Err1 @ Hinv[i1:i2, i2:], the exact fp32 chain of sgemm.hip
-            SgemmArgs g{};
-            g.A = Err; g.lda = GBS;
-            g.B = Hinv + i1 * K + i2; g.ldb = K;
-            g.C = W + i2; g.ldc = K;
-            g.M = g.M_last = (int)R; g.N = g.N_last = (int)(K - i2); g.Kd = g.Kd_last = count;
-            g.epilogue = SG_SUB; g.batch = 1;
-            int rc = sgemm_launch(g, false, false, st);
-            if (rc) return rc;
-        }
-    }
-    return LLMC_OK;
+        return (int)LLMC_OK;
+    });
 }

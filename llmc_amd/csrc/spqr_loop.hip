@@ -1,9 +1,8 @@
 // spqr_loop.hip — SpQR.weight_transform (spqr.py:185-254): the blocked column loop with leave-one-out outlier detection
 // and the round_zp=False quantizer, as the reference executes it on asymmetric per-group weights.
 //
-// Same ownership as gptq_loop.hip: a wave owns 4 rows, 16 lanes per row, lane p owns columns p, p+16, ..., p+112 of the
-// 128-column block, so the 16 columns of a detection stripe sit in the 16 lanes of the row (one register index) and a
-// group of g = 16 M columns is M registers per lane. Per group start (spqr.py:214-229):
+// Blocks, ownership and the trailing update are col_block.h's: the 16 columns of a detection stripe sit in the 16 lanes of the
+// row (one register index) and a group of g = 16 M columns is M registers per lane. Per group start (spqr.py:214-229):
 //   pass A  min / second min / multiplicity (and max) of the group by 16-lane broadcasts -> min / max WITHOUT column j
 //           is the second extreme iff j holds the only copy of the first (spqr.py:187-189: LooG = G without column j);
 //   pass B  Base = sum_k ((qdq(G_k) - G_k) / d_k)^2 and, per owned column j, Loo_j = the same sum without k = j under
@@ -12,17 +11,13 @@
 //   (s, z)  asym round_zp=False qparams of G', then the reference's second-level quantizers, which see [R, 1] tensors,
 //           leave them ungrouped and return fl(fl(v / ss) * ss), ss = 1e-5 / (qmax - qmin) (spqr.py:323-345).
 // Per column (spqr.py:233-250): q, err = (w - q) / d, mask = err^2 > threshold, a masked weight keeps its value
-// (err = (w - w) / d), tmp = w, loss = err^2, w_j -= fl(err * U[i][j]) for the later columns of the block.
-// The trailing update W[:, i2:] -= Err1 @ U[i1:i2, i2:] is gptq_loop.hip's: sgemm.hip's k-ordered fp32 fma chain.
+// (err = (w - w) / d), tmp = w, loss = err^2, w_j -= fl(err * U[i][j]) for the later columns of the block; after the block
+// W[:, i2:] -= Err1 @ U[i1:i2, i2:] (spqr.py:254).
 // Operation order is oracle/csrc/spqr_canon.c's (pinned bit-exactly against the reference: tests/golden/spqr.npz).
 #include <stdlib.h>
-#include "common.h"
-#include "sgemm.h"
+#include "col_block.h"
 
 namespace llmc {
-
-static constexpr int SBS = 128;   // blocksize
-static constexpr int SNT = 256;   // threads per workgroup: 4 waves x 4 rows
 
 struct SpqrBlockArgs {
     const float* W;       // [R, K] running weights
@@ -40,13 +35,6 @@ struct SpqrBlockArgs {
     int use_mask;         // threshold finite
     float sqmin, sqmax, zqmin, zqmax;
 };
-
-// lane po of every 16-lane row (ds_bpermute: po is a loop counter, the 16 steps of a stripe are a real loop — unrolled,
-// the 128 steps with their IEEE divisions and hoisted LDS reads spill hundreds of registers)
-__device__ __forceinline__ float sp_bcast(float v, int po) {
-    const int src = ((int)(threadIdx.x & 48) | po) << 2;
-    return __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(v)));
-}
 
 __device__ __forceinline__ void qp_asym_nr(float mn, float mx, float qmin, float qmax, float& s, float& z) {
     float d = mx - mn;
@@ -93,40 +81,9 @@ __device__ __forceinline__ void ext_max(Ext2& e, float x) {
 
 // GSZ = group size (16 M); one workgroup = 16 rows
 template <int GSZ>
-__global__ __launch_bounds__(SNT) void k_spqr_block(SpqrBlockArgs a) {
+__global__ __launch_bounds__(CB_NT) void k_spqr_block(SpqrBlockArgs a) {
     constexpr int M = GSZ / 16;
-    __shared__ __attribute__((aligned(16))) float Us[SBS * SBS];   // Us[i][p*8 + e] = U[i1+i][i1+p+16e] above the diagonal, else 0
-    __shared__ float dg[SBS];
-    const int tid = threadIdx.x;
-    {
-        constexpr int NV = SBS * SBS / 4 / SNT;
-        float4 v[NV];
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int idx = tid + SNT * j;
-            const int i = idx >> 5, c4 = (idx & 31) * 4;
-            v[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (i < a.count && c4 < a.count) v[j] = *reinterpret_cast<const float4*>(a.U + (int64_t)(a.i1 + i) * a.K + a.i1 + c4);
-        }
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int idx = tid + SNT * j;
-            const int i = idx >> 5, c4 = (idx & 31) * 4;
-            const float vv[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int c = c4 + t;
-                if (c == i) dg[i] = i < a.count ? vv[t] : 1.0f;
-                Us[i * SBS + (c & 15) * 8 + (c >> 4)] = c > i ? vv[t] : 0.0f;
-            }
-        }
-    }
-    __syncthreads();
-
-    const int lane = tid & 63;
-    const int p = lane & 15;
-    const int64_t row = ((int64_t)blockIdx.x * (SNT / 64) + (tid >> 6)) * 4 + (lane >> 4);
-    const bool active = row < a.R;
+#include "col_block_stage.h"
     const int64_t rr = active ? row : a.R - 1;
 
     float w[8], er[8], ls[8];
@@ -154,7 +111,7 @@ __global__ __launch_bounds__(SNT) void k_spqr_block(SpqrBlockArgs a) {
                         constexpr int T = decltype(tc)::value;
 #pragma unroll 1
                         for (int po = 0; po < 16; ++po) {
-                            const float x = sp_bcast(w[E + T], po);
+                            const float x = row_lane(w[E + T], po);
                             ext_min(lo, x);
                             ext_max(hi, x);
                         }
@@ -173,7 +130,7 @@ __global__ __launch_bounds__(SNT) void k_spqr_block(SpqrBlockArgs a) {
                         constexpr int T = decltype(tc)::value;
 #pragma unroll 1
                         for (int po = 0; po < 16; ++po) {
-                            const float x = sp_bcast(w[E + T], po);
+                            const float x = row_lane(w[E + T], po);
                             const float d = dg[16 * (E + T) + po];
                             const float eb = (qdq_nr(x, bs, bz, qmin, qmax) - x) / d;
                             base = base + eb * eb;
@@ -193,8 +150,8 @@ __global__ __launch_bounds__(SNT) void k_spqr_block(SpqrBlockArgs a) {
                         constexpr int T = decltype(tc)::value;
 #pragma unroll 1
                         for (int po = 0; po < 16; ++po) {
-                            const float x = sp_bcast(w[E + T], po);
-                            const float m = sp_bcast(mj[T], po);
+                            const float x = row_lane(w[E + T], po);
+                            const float m = row_lane(mj[T], po);
                             sum_keep = sum_keep + x * (1.0f - m);
                             n_keep = n_keep + (1.0f - m);
                         }
@@ -234,7 +191,7 @@ __global__ __launch_bounds__(SNT) void k_spqr_block(SpqrBlockArgs a) {
 #pragma unroll 1
         for (int po = 0; po < 16; ++po) {
             const int i = 16 * E + po;
-            const float wv = sp_bcast(w[E], po);
+            const float wv = row_lane(w[E], po);
             const float d = dg[i];
             const float q = qdq_nr(wv, s, z, qmin, qmax);
             float e1 = (wv - q) / d;
@@ -250,12 +207,7 @@ __global__ __launch_bounds__(SNT) void k_spqr_block(SpqrBlockArgs a) {
                 ls[E] = e1 * e1;
                 mk |= out ? (1u << E) : 0u;
             }
-            const float* ur = us + i * SBS;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float t = e1 * ur[e];
-                w[e] = w[e] - t;
-            }
+            col_rank1(w, e1, us, i);
         }
     });
 
@@ -269,7 +221,7 @@ __global__ __launch_bounds__(SNT) void k_spqr_block(SpqrBlockArgs a) {
             a.losses[o] = ls[e];
             a.mask[o] = (mk >> e) & 1u;
         }
-        a.Err[row * SBS + c] = (c < a.count) ? er[e] : 0.0f;
+        a.Err[row * CB_BS + c] = (c < a.count) ? er[e] : 0.0f;
     }
 }
 
@@ -279,7 +231,7 @@ using namespace llmc;
 
 extern "C" size_t llmc_spqr_quantize_ws_bytes(int64_t R, int64_t K) {
     if (R <= 0 || K <= 0) return 0;
-    return (size_t)R * SBS * sizeof(float);
+    return (size_t)R * CB_BS * sizeof(float);
 }
 
 extern "C" int llmc_spqr_quantize(float* W, const float* Hinv, int64_t R, int64_t K, float qmin, float qmax,
@@ -289,7 +241,7 @@ extern "C" int llmc_spqr_quantize(float* W, const float* Hinv, int64_t R, int64_
                                   llmc_stream_t stream) {
     LLMC_REQUIRE(W && Hinv && Wout && losses && mask && scales && zeros && ws && R > 0 && K > 0,
                  "spqr_quantize: null/empty argument");
-    LLMC_REQUIRE(blocksize == SBS, "spqr_quantize: blocksize must be 128");
+    LLMC_REQUIRE(blocksize == CB_BS, "spqr_quantize: blocksize must be 128");
     LLMC_REQUIRE(K % 4 == 0 && K < (1 << 30), "spqr_quantize: K must be a multiple of 4");
     LLMC_REQUIRE(threshold == threshold && threshold >= 0.0f, "spqr_quantize: threshold must be >= 0 (inf = no outliers)");
     const int gsz = (int)group_size;
@@ -300,33 +252,21 @@ extern "C" int llmc_spqr_quantize(float* W, const float* Hinv, int64_t R, int64_
     hipStream_t st = (hipStream_t)stream;
     float* Err = (float*)ws;
     const bool finite = !(threshold > 3.0e38f);
-    for (int64_t i1 = 0; i1 < K; i1 += SBS) {
-        const int count = (int)(K - i1 < SBS ? K - i1 : SBS);
+    return col_blocks(W, Hinv, Err, R, K, st, [&](int i1, int count) {
         SpqrBlockArgs a;
         a.W = W; a.U = Hinv; a.Wout = Wout; a.losses = losses; a.mask = mask; a.Err = Err;
-        a.scales = scales; a.zeros = zeros; a.R = R; a.K = (int)K; a.i1 = (int)i1; a.count = count; a.ng = (int)(K / gsz);
+        a.scales = scales; a.zeros = zeros; a.R = R; a.K = (int)K; a.i1 = i1; a.count = count; a.ng = (int)(K / gsz);
         a.qmin = qmin; a.qmax = qmax; a.threshold = finite ? threshold : INFINITY;
         a.detect = finite && !simplified_outliers; a.use_mask = finite;
         a.sqmin = scale_qmin; a.sqmax = scale_qmax; a.zqmin = zero_qmin; a.zqmax = zero_qmax;
-        const int grid = (int)ceil_div64(R, SNT / 16);
+        const int grid = (int)ceil_div64(R, CB_NT / 16);
         switch (gsz) {
-            case 16: hipLaunchKernelGGL((k_spqr_block<16>), dim3(grid), dim3(SNT), 0, st, a); break;
-            case 32: hipLaunchKernelGGL((k_spqr_block<32>), dim3(grid), dim3(SNT), 0, st, a); break;
-            case 64: hipLaunchKernelGGL((k_spqr_block<64>), dim3(grid), dim3(SNT), 0, st, a); break;
-            default: hipLaunchKernelGGL((k_spqr_block<128>), dim3(grid), dim3(SNT), 0, st, a); break;
+            case 16: hipLaunchKernelGGL((k_spqr_block<16>), dim3(grid), dim3(CB_NT), 0, st, a); break;
+            case 32: hipLaunchKernelGGL((k_spqr_block<32>), dim3(grid), dim3(CB_NT), 0, st, a); break;
+            case 64: hipLaunchKernelGGL((k_spqr_block<64>), dim3(grid), dim3(CB_NT), 0, st, a); break;
+            default: hipLaunchKernelGGL((k_spqr_block<128>), dim3(grid), dim3(CB_NT), 0, st, a); break;
         }
         LLMC_LAUNCH_CHECK();
-        const int64_t i2 = i1 + count;
-        if (i2 < K) {   // W[:, i2:] -= Err1 @ Hinv[i1:i2, i2:]  (spqr.py:254), the exact fp32 chain of sgemm.hip
-            SgemmArgs g{};
-            g.A = Err; g.lda = SBS;
-            g.B = Hinv + i1 * K + i2; g.ldb = K;
-            g.C = W + i2; g.ldc = K;
-            g.M = g.M_last = (int)R; g.N = g.N_last = (int)(K - i2); g.Kd = g.Kd_last = count;
-            g.epilogue = SG_SUB; g.batch = 1;
-            int rc = sgemm_launch(g, false, false, st);
-            if (rc) return rc;
-        }
-    }
-    return LLMC_OK;
+        return (int)LLMC_OK;
+    });
 }

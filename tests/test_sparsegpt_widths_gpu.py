@@ -2,7 +2,8 @@
 select's edges (one first-digit bin, a threshold of +0, the last rank, subnormal and +inf scores), a single ragged block and
 row counts around the 16-row workgroup and the 4-row wave, tall panels (k_sg_hist's capped grid, a trailing update of 4 columns
 under 20000 rows), model widths (K = 4096, 11008) on a factor from chol_inv_upper, a NaN lower triangle under U, and calls of
-different shape and mode back to back on the one cached workspace. The inputs are tests/sparsegpt_cases.py's, whose
+different shape and mode back to back on the one cached workspace, also in turn with magnitude_prune, whose select is the same
+code (csrc/radix_select.h). The inputs are tests/sparsegpt_cases.py's, whose
 conditions tests/test_sparsegpt_cases.py proves on the CPU. Every comparison with tests/sparsegpt_oracle.py is bit for bit:
 test_sparsegpt_gpu.py's assert_same on Wout, losses and the running W as uint32 views and on the mask as uint8."""
 import numpy as np
@@ -120,3 +121,37 @@ def test_calls_of_other_shapes_and_modes_on_the_one_workspace():
         W, U = C.build(name, R, K)
         got.append(check(('sequence', name, R, K, mode), W, U, mode)[0])
     assert_same(got[-1], got[0], 'the first call again')
+
+
+def test_magnitude_and_sparsegpt_calls_interleaved_on_the_shared_select():
+    """csrc/radix_select.h serves both with two clearing conventions: magnitude_prune zeroes its workspace at the start of a call
+    and leaves the histograms filled, sparsegpt_prune zeroes the select's words once and every scan clears what it read. What the
+    two share is code, not memory (magnitude_prune gets a fresh workspace per call, sparsegpt_prune its cached one behind Err):
+    this checks each convention on the one scan, not a histogram leaking from one call into another. In turn on one device: magnitude fp32 (64, 256) (both digits), sparsegpt 0.5 at (40, 260) (one full and one ragged block), magnitude
+    bf16 (384, 256) (finished after the first digit), then the second and the first again. Every result bit for bit the oracle's
+    (sparse_oracle.magnitude_prune at kth = numel / 2, sparsegpt_oracle.prune); a repeated call equals its first occurrence."""
+    import sparse_oracle as SO
+    from llmc_amd.compression.sparsification import sparse_ops
+    g = torch.Generator().manual_seed(64 + 256)
+    mag_w = {}
+    for dt, (R, K) in ((torch.float32, (64, 256)), (torch.bfloat16, (384, 256))):
+        w = (torch.randn(R, K, generator=g) * 0.05).to(dt)
+        w[0, :7], w[1, :7] = 0.0, -0.0
+        mag_w[dt] = (w, R * K // 2, SO.magnitude_prune(w, R * K // 2))
+
+    def magnitude(dt):
+        w, kth, (want, want_thresh, want_mask) = mag_w[dt]
+        view = w.cuda()
+        thresh, mask = sparse_ops.magnitude_prune(view, kth, want_mask=True)
+        got = (SO.bits(view.cpu()), SO.bits(thresh.reshape(1).cpu()), mask.cpu())
+        assert torch.equal(got[0], SO.bits(want)) and torch.equal(got[1], SO.bits(want_thresh.reshape(1))), dt
+        assert torch.equal(got[2], want_mask), dt
+        return got
+
+    def sparsegpt():
+        W, U = C.general(40, 260)
+        return check(('interleaved', 40, 260), W, U, 's0.5')[0]
+
+    m1, s1, _, s2, m2 = magnitude(torch.float32), sparsegpt(), magnitude(torch.bfloat16), sparsegpt(), magnitude(torch.float32)
+    assert_same(s2, s1, 'sparsegpt again')
+    assert all(torch.equal(a, b) for a, b in zip(m2, m1)), 'magnitude fp32 again'

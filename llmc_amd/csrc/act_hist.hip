@@ -4,6 +4,7 @@
 // HBM-bound: one read of the sample; counts are taken in LDS (one private histogram per workgroup, integer atomics),
 // merged with integer atomics in a workspace and converted to fp32 counts (exact below 2^24 per bin).
 #include "common.h"
+#include "vec16.h"
 
 namespace llmc {
 
@@ -19,12 +20,10 @@ __global__ __launch_bounds__(HB) void k_histc(const T* __restrict__ x, int64_t n
     constexpr int V = 16 / sizeof(T);
     const int64_t nv = n / V;
     for (int64_t i = (int64_t)blockIdx.x * HB + threadIdx.x; i < nv; i += (int64_t)gridDim.x * HB) {
-        const uint4 r = *reinterpret_cast<const uint4*>(x + i * V);
-        T v[V];
-        __builtin_memcpy(v, &r, 16);
+        const Vec<T, V> v = load_vec<T, V>(x + i * V);
 #pragma unroll
         for (int k = 0; k < V; ++k) {
-            const float f = to_f32<T>(v[k]);
+            const float f = to_f32<T>(v.v[k]);
             if (f >= lo && f <= hi) {
                 int p = (int)((f - lo) * fb / w);
                 p = p < bins - 1 ? p : bins - 1;
@@ -83,16 +82,14 @@ __global__ __launch_bounds__(HB) void k_minmax_samples(MinmaxSamplesArgs a) {
         // four 16-byte loads in flight per thread (one per turn left the kernel at 3.8 TB/s on the 18 inputs of a Mixtral block)
         int64_t i = c0 + (int64_t)threadIdx.x * V;
         for (; i + 3 * (int64_t)HB * V < v1; i += 4 * (int64_t)HB * V) {
-            uint4 r[4];
+            Vec<T, V> v[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) r[u] = *reinterpret_cast<const uint4*>(x + i + u * (int64_t)HB * V);
+            for (int u = 0; u < 4; ++u) v[u] = load_vec<T, V>(x + i + u * (int64_t)HB * V);
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                T v[V];
-                __builtin_memcpy(v, &r[u], 16);
 #pragma unroll
                 for (int k = 0; k < V; ++k) {
-                    const float f = to_f32<T>(v[k]);
+                    const float f = to_f32<T>(v[u].v[k]);
                     mn = fminf(mn, f);
                     mx = fmaxf(mx, f);
                     bad = f != f ? 1.0f : bad;
@@ -100,12 +97,10 @@ __global__ __launch_bounds__(HB) void k_minmax_samples(MinmaxSamplesArgs a) {
             }
         }
         for (; i < v1; i += (int64_t)HB * V) {
-            const uint4 r = *reinterpret_cast<const uint4*>(x + i);
-            T v[V];
-            __builtin_memcpy(v, &r, 16);
+            const Vec<T, V> v = load_vec<T, V>(x + i);
 #pragma unroll
             for (int k = 0; k < V; ++k) {
-                const float f = to_f32<T>(v[k]);
+                const float f = to_f32<T>(v.v[k]);
                 mn = fminf(mn, f);
                 mx = fmaxf(mx, f);
                 bad = f != f ? 1.0f : bad;

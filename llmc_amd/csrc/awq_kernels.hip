@@ -2,6 +2,7 @@
 // scaling_input (base_blockwise_quantization.py:597-611, 877-897). All arithmetic in the tensor dtype with
 // ATen's per-op rounding; reductions accumulate in fp32 in a fixed order (deterministic).
 #include "common.h"
+#include "vec16.h"
 
 namespace llmc {
 
@@ -20,20 +21,13 @@ __global__ __launch_bounds__(AB) void k_abs_colsum_partial(const T* __restrict__
     float acc[V];
 #pragma unroll
     for (int i = 0; i < V; ++i) acc[i] = 0.0f;
-    const bool vec = c0 + V <= K;
-    for (int64_t t = t0; t < t1; ++t) {
-        const T* p = X + t * K + c0;
-        if (vec) {
-            uint4 raw = *reinterpret_cast<const uint4*>(p);
-            T v[V];
-            __builtin_memcpy(v, &raw, 16);
+    for (int64_t t = t0; t < t1; ++t) {          // llmc_awq_act_mean takes rows of whole vectors only: c0 + V <= K
+        const Vec<T, V> v = load_vec<T, V>(X + t * K + c0);
 #pragma unroll
-            for (int i = 0; i < V; ++i) acc[i] += fabsf(to_f32<T>(v[i]));
-        } else {
-            for (int i = 0; i < V && c0 + i < K; ++i) acc[i] += fabsf(to_f32<T>(p[i]));
-        }
+        for (int i = 0; i < V; ++i) acc[i] += fabsf(to_f32<T>(v.v[i]));
     }
-    for (int i = 0; i < V && c0 + i < K; ++i) part[(int64_t)blockIdx.y * K + c0 + i] = acc[i];
+#pragma unroll
+    for (int i = 0; i < V; ++i) part[(int64_t)blockIdx.y * K + c0 + i] = acc[i];
 }
 template <typename T>
 __global__ __launch_bounds__(AB) void k_colsum_final(const float* __restrict__ part, int64_t nchunk, int64_t K,
@@ -61,13 +55,11 @@ __global__ __launch_bounds__(AB) void k_wscale_partial(const T* __restrict__ W, 
 #pragma unroll
         for (int i = 0; i < V; ++i) acc[i] = 0.0f;
         for (int64_t r = r0; r < r1; ++r) {
-            uint4 raw = *reinterpret_cast<const uint4*>(W + r * K + c0);
-            T v[V];
-            __builtin_memcpy(v, &raw, 16);
+            const Vec<T, V> v = load_vec<T, V>(W + r * K + c0);
             float a[V], m = 0.0f;
 #pragma unroll
             for (int i = 0; i < V; ++i) {
-                a[i] = fabsf(to_f32<T>(v[i]));
+                a[i] = fabsf(to_f32<T>(v.v[i]));
                 m = fmaxf(m, a[i]);
             }
             m = wave_max(m, lpr);
@@ -88,16 +80,9 @@ static constexpr int WS_TILE_GROUPS = 256;   // groups per column tile: LDS of W
 
 template <typename T, int VEC>
 __device__ __forceinline__ void load_abs(const T* p, float (&a)[VEC]) {
-    T v[VEC];
-    if constexpr (VEC * sizeof(T) == 16) {
-        uint4 raw = *reinterpret_cast<const uint4*>(p);
-        __builtin_memcpy(v, &raw, 16);
-    } else {
+    const Vec<T, VEC> v = load_vec<T, VEC>(p);
 #pragma unroll
-        for (int i = 0; i < VEC; ++i) v[i] = p[i];
-    }
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) a[i] = fabsf(to_f32<T>(v[i]));
+    for (int i = 0; i < VEC; ++i) a[i] = fabsf(to_f32<T>(v.v[i]));
 }
 
 template <typename T, int VEC>  // VEC > 1 needs g % VEC == 0 and 16-B aligned rows: a vector never straddles two groups
@@ -201,19 +186,14 @@ __global__ __launch_bounds__(AB) void k_cols_op(const T* __restrict__ X, const T
     const int64_t total = N * nv;
     for (int64_t i = (int64_t)blockIdx.x * AB + threadIdx.x; i < total; i += (int64_t)gridDim.x * AB) {
         const int64_t r = i / nv, c = (i - r * nv) * V;
-        uint4 rx = *reinterpret_cast<const uint4*>(X + r * K + c);
-        uint4 rs = *reinterpret_cast<const uint4*>(s + c);
-        T xv[V], sv[V], ov[V];
-        __builtin_memcpy(xv, &rx, 16);
-        __builtin_memcpy(sv, &rs, 16);
+        const Vec<T, V> xv = load_vec<T, V>(X + r * K + c), sv = load_vec<T, V>(s + c);
+        Vec<T, V> ov;
 #pragma unroll
         for (int k = 0; k < V; ++k) {
-            const float a = to_f32<T>(xv[k]), b = to_f32<T>(sv[k]);
-            ov[k] = from_f32<T>(rndc<DT>(OP == 0 ? a / b : a * b));
+            const float a = to_f32<T>(xv.v[k]), b = to_f32<T>(sv.v[k]);
+            ov.v[k] = from_f32<T>(rndc<DT>(OP == 0 ? a / b : a * b));
         }
-        uint4 ro;
-        __builtin_memcpy(&ro, ov, 16);
-        *reinterpret_cast<uint4*>(out + r * K + c) = ro;
+        store_vec<T, V>(out + r * K + c, ov);
     }
 }
 // x / s[col] written K-TILED (T[K/32][rows][32], linear_eval.hip): block = 64 rows x two 32-k slices, thread = one 16-B
@@ -230,16 +210,11 @@ __global__ __launch_bounds__(256) void k_div_cols_kt(const T* __restrict__ X, co
         const int64_t kt = (int64_t)blockIdx.y * 2 + j;
         if (kt * 32 >= K) break;
         const int64_t col = kt * 32 + c * 8;
-        uint4 rx = *reinterpret_cast<const uint4*>(X + row * K + col);
-        uint4 rs = *reinterpret_cast<const uint4*>(s + col);
-        T xv[8], sv[8], ov[8];
-        __builtin_memcpy(xv, &rx, 16);
-        __builtin_memcpy(sv, &rs, 16);
+        const Vec<T, 8> xv = load_vec<T, 8>(X + row * K + col), sv = load_vec<T, 8>(s + col);
+        Vec<T, 8> ov;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) ov[k] = from_f32<T>(rndc<DT>(to_f32<T>(xv[k]) / to_f32<T>(sv[k])));
-        uint4 ro;
-        __builtin_memcpy(&ro, ov, 16);
-        *reinterpret_cast<uint4*>(out + (kt * N + row) * 32 + c * 8) = ro;
+        for (int k = 0; k < 8; ++k) ov.v[k] = from_f32<T>(rndc<DT>(to_f32<T>(xv.v[k]) / to_f32<T>(sv.v[k])));
+        store_vec<T, 8>(out + (kt * N + row) * 32 + c * 8, ov);
     }
 }
 template <typename T>
@@ -352,8 +327,8 @@ extern "C" int llmc_div_cols_kt(const void* X, const void* s, int dt, int64_t N,
                      ((uintptr_t)s & 15) == 0, "div_cols_kt: needs K % 32 == 0 and 16-B aligned buffers");
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)ceil_div64(N, 64), (unsigned)ceil_div64(K, 64));
-    if (dt == LLMC_F16) hipLaunchKernelGGL((k_div_cols_kt<f16_t>), grid, dim3(256), 0, st, (const f16_t*)X, (const f16_t*)s, N, K, (f16_t*)out);
-    else hipLaunchKernelGGL((k_div_cols_kt<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)X, (const bf16_t*)s, N, K, (bf16_t*)out);
+    DISPATCH_DT(dt, if constexpr (sizeof(T) == 2) hipLaunchKernelGGL((k_div_cols_kt<T>), grid, dim3(256), 0, st, (const T*)X,
+                                                                     (const T*)s, N, K, (T*)out));
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;
 }

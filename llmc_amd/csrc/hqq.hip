@@ -16,8 +16,8 @@
 #include <math.h>
 
 #include "common.h"
-#include "quant_group.h"
 #include "quant_math.h"
+#include "vec16.h"
 
 namespace llmc {
 namespace {

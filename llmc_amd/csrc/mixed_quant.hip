@@ -45,11 +45,6 @@ template <int V> __device__ __forceinline__ RoleVec<V> load_role(const uint8_t* 
     }
     return r;
 }
-template <typename T> __device__ __forceinline__ T zero_of() {
-    T z;
-    __builtin_memset(&z, 0, sizeof(T));
-    return z;
-}
 
 // A group takes either branch of round_zp at run time (GroupQuant<true>): round_zp = 0 is the reference's fractional zero point,
 // exactly as k_quant_static evaluates LLMC_FRACTIONAL_ZP. The select is written out here, fractional arm first, as it always

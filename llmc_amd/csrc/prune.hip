@@ -8,8 +8,10 @@
 //   llmc_magnitude_prune   global |w| threshold of rank kth and w[|w| <= thresh] = 0 (magnitude.py:26-31): a 32768-bin histogram
 //                          of the sign-cleared bit patterns, a one-workgroup scan (radix_select.h), a masking pass.
 // All data passes are HBM-bound; DESIGN.md holds the byte counts they are measured against.
+#include "col_reduce.h"
 #include "common.h"
 #include "radix_select.h"
+#include "vec16.h"
 
 namespace llmc {
 namespace {
@@ -21,74 +23,30 @@ constexpr int SQ_B = 256;             // threads per workgroup
 constexpr int SQ_ROWS = 64;           // fewest rows worth a chunk of their own
 constexpr int SQ_MAX_BLOCKS = 2048;
 
-// The number of row chunks depends on (N, K, dt) only, never on the alignment of X: the order of summation is a function of
-// the shape (include/llmc_hip.h).
-inline int64_t sq_chunks(int64_t N, int64_t K, int dt) {
-    const int64_t colblocks = ceil_div64(K, 64 * (int64_t)(16 / dtype_size(dt)));
-    int64_t cap = SQ_MAX_BLOCKS / colblocks;
-    if (cap < 1) cap = 1;
-    int64_t n = ceil_div64(N, SQ_ROWS);
-    if (n > cap) n = cap;
-    return n < 1 ? 1 : n;
-}
+// The number of row chunks depends on (N, K, dt) only, never on the alignment of X (the dtype's vector width, whatever the loads):
+// with col_reduce.h's walk the order of summation is a function of the shape, the one include/llmc_hip.h promises.
+inline int64_t sq_chunks(int64_t N, int64_t K, int dt) { return col_chunks(N, K, 16 / dtype_size(dt), SQ_ROWS, SQ_MAX_BLOCKS); }
 
-// stage 1: grid (column blocks, row chunks); a wave reads 64 consecutive vectors of one row; wave w of a workgroup owns the rows
-// r0 + w, r0 + w + 4, ... of the chunk and adds their squares in that order; the four waves' sums are added in wave order.
+struct SqSum {
+    static constexpr int NS = 1;
+    static __device__ __forceinline__ float identity(int) { return 0.0f; }
+    static __device__ __forceinline__ void step(float (&a)[1], float f) { a[0] = a[0] + f * f; }          // two roundings: the build turns contraction off
+    static __device__ __forceinline__ float join(int, float a, float b) { return a + b; }
+};
+
 template <typename T, int VEC>
 __global__ __launch_bounds__(SQ_B) void k_col_sqsum_partial(const T* __restrict__ X, int64_t N, int64_t K, int64_t rows_per_chunk,
                                                             float* __restrict__ part) {
-    __shared__ float ssum[SQ_B / 64 - 1][64 * VEC];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t c = ((int64_t)blockIdx.x * 64 + lane) * VEC;
-    const int64_t r0 = (int64_t)blockIdx.y * rows_per_chunk;
-    const int64_t r1 = r0 + rows_per_chunk < N ? r0 + rows_per_chunk : N;
-    float acc[VEC];
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) acc[i] = 0.0f;
-    if (c < K) {
-#pragma unroll 4
-        for (int64_t r = r0 + wv; r < r1; r += SQ_B / 64) {
-            T v[VEC];
-            if constexpr (VEC * sizeof(T) == 16) {
-                const uint4 raw = *reinterpret_cast<const uint4*>(X + r * K + c);
-                __builtin_memcpy(v, &raw, 16);
-            } else {
-                v[0] = X[r * K + c];
-            }
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                const float f = to_f32<T>(v[i]);
-                acc[i] = acc[i] + f * f;          // two roundings: the build turns contraction off
-            }
-        }
-    }
-    if (wv > 0) {
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) ssum[wv - 1][lane * VEC + i] = acc[i];
-    }
-    __syncthreads();
-    if (wv == 0 && c < K) {
-        float* p = part + (int64_t)blockIdx.y * K;
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) {
-            float a = acc[i];
-#pragma unroll
-            for (int w = 0; w < SQ_B / 64 - 1; ++w) a = a + ssum[w][lane * VEC + i];
-            p[c + i] = a;
-        }
-    }
+    col_reduce_partial<SqSum, T, VEC, SQ_B>(X, N, K, rows_per_chunk, part);
 }
 
-// stage 2: the chunks of one column in chunk order, folded into the running sum
 __global__ __launch_bounds__(SQ_B) void k_col_sqsum_fold(const float* __restrict__ part, int64_t nchunk, int64_t K, int init,
                                                          float* __restrict__ acc, float* __restrict__ out, float nsamples) {
     const int64_t k = (int64_t)blockIdx.x * SQ_B + threadIdx.x;
     if (k >= K) return;
-    float a = part[k];
-    for (int64_t ch = 1; ch < nchunk; ++ch) a = a + part[ch * K + k];
-    if (!init) a = acc[k] + a;
-    acc[k] = a;
-    if (out) out[k] = a / nsamples;
+    float a[1];
+    col_reduce_fold<SqSum>(part, nchunk, K, k, init, acc, a);
+    if (out) out[k] = a[0] / nsamples;
 }
 
 // ================================================================================================================================
@@ -103,9 +61,6 @@ __device__ __forceinline__ uint32_t metric_key(float w, float sq, bool has_s) {
     const uint32_t b = __float_as_uint(m);
     return (m != m) ? 0x7FFFFFFFu : (b & 0x7FFFFFFFu);
 }
-
-template <typename T> __device__ __forceinline__ T zero_of() { return T{0}; }
-template <> __device__ __forceinline__ float zero_of<float>() { return 0.0f; }
 
 constexpr int PR_BINS = 2048;                              // 11-bit digits
 constexpr int PR_HIST = PR_BINS + PR_BINS / 32 * 4;        // every 32 bins are followed by 4 words of padding: the scan's lanes, which own
@@ -135,7 +90,7 @@ __global__ __launch_bounds__(TPR < 256 ? 256 : TPR) void k_prune_rows(T* __restr
     const bool has_s = srow != nullptr;
     T* wrow = W + (active ? row : 0) * ld;
 
-    T raw[VEC > 1 ? NV : 1][VEC];
+    Vec<T, VEC> raw[VEC > 1 ? NV : 1];
     uint32_t key[NV][VEC];
 #pragma unroll
     for (int ii = 0; ii < NV; ++ii) {
@@ -144,10 +99,9 @@ __global__ __launch_bounds__(TPR < 256 ? 256 : TPR) void k_prune_rows(T* __restr
         if (active && v < nvec) {
             float sq[VEC];
             if constexpr (VEC > 1) {
-                const uint4 q = *reinterpret_cast<const uint4*>(wrow + (int64_t)v * VEC);
-                __builtin_memcpy(raw[i], &q, 16);
+                raw[i] = load_vec<T, VEC>(wrow + (int64_t)v * VEC);
                 if (has_s) {
-                    if (s_vec) {
+                    if (s_vec) {          // fp32 scaler entries, four per load: written out (with load_vec the streams moved)
 #pragma unroll
                         for (int j = 0; j < VEC; j += 4) {
                             const float4 s4 = *reinterpret_cast<const float4*>(srow + (int64_t)v * VEC + j);
@@ -159,15 +113,15 @@ __global__ __launch_bounds__(TPR < 256 ? 256 : TPR) void k_prune_rows(T* __restr
                     }
                 }
             } else {
-                raw[i][0] = wrow[v];          // the one-element form keeps the key only: it stores nothing but the zeros
+                raw[i].v[0] = wrow[v];          // the one-element form keeps the key only: it stores nothing but the zeros
                 if (has_s) sq[0] = srow[v];
             }
 #pragma unroll
-            for (int j = 0; j < VEC; ++j) key[ii][j] = metric_key(to_f32<T>(raw[i][j]), has_s ? sqrtf(sq[j]) : 1.0f, has_s);
+            for (int j = 0; j < VEC; ++j) key[ii][j] = metric_key(to_f32<T>(raw[i].v[j]), has_s ? sqrtf(sq[j]) : 1.0f, has_s);
         } else {
 #pragma unroll
             for (int j = 0; j < VEC; ++j) {
-                raw[i][j] = zero_of<T>();
+                raw[i].v[j] = zero_of<T>();
                 key[ii][j] = 0xFFFFFFFFu;
             }
         }
@@ -198,7 +152,8 @@ __global__ __launch_bounds__(TPR < 256 ? 256 : TPR) void k_prune_rows(T* __restr
         }
         __syncthreads();
         if (wv == 0) {
-            // lane l of the row's first wave owns bins 32 l .. 32 l + 31: eight 16-byte groups
+            // lane l of the row's first wave owns bins 32 l .. 32 l + 31: eight 16-byte groups of LDS counters (no vector of
+            // elements: with load_vec here the one-element forms compiled to another instruction stream)
             const uint4* p = reinterpret_cast<const uint4*>(&s_hist[g][hist_slot(32u * lane)]);
             uint32_t s8[8], sum = 0;
 #pragma unroll
@@ -312,7 +267,7 @@ __global__ __launch_bounds__(TPR < 256 ? 256 : TPR) void k_prune_rows(T* __restr
             }
         }
         if (!(active && v < nvec)) continue;
-        uint8_t mk[VEC];
+        Vec<uint8_t, VEC> mk;
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
             const uint32_t k = key[i][j];
@@ -322,47 +277,25 @@ __global__ __launch_bounds__(TPR < 256 ? 256 : TPR) void k_prune_rows(T* __restr
                 ++e;
             }
             if constexpr (VEC > 1) {
-                if (cut) raw[i][j] = zero_of<T>();
+                if (cut) raw[i].v[j] = zero_of<T>();
             }
-            mk[j] = cut ? 1 : 0;
+            mk.v[j] = cut ? 1 : 0;
         }
         if constexpr (VEC > 1) {
-            uint4 q;
-            __builtin_memcpy(&q, raw[i], 16);
-            *reinterpret_cast<uint4*>(wrow + (int64_t)v * VEC) = q;
+            store_vec<T, VEC>(wrow + (int64_t)v * VEC, raw[i]);
         } else {
-            if (mk[0]) wrow[v] = zero_of<T>();
+            if (mk.v[0]) wrow[v] = zero_of<T>();
         }
-        if (mask) {
-            uint8_t* mp = mask + row * K + (int64_t)v * VEC;
-            if constexpr (VEC == 8) {
-                if (mask_vec) {
-                    uint2 q;
-                    __builtin_memcpy(&q, mk, 8);
-                    *reinterpret_cast<uint2*>(mp) = q;
-                } else {
-#pragma unroll
-                    for (int j = 0; j < VEC; ++j) mp[j] = mk[j];
-                }
-            } else if constexpr (VEC == 4) {
-                if (mask_vec) {
-                    uint32_t q;
-                    __builtin_memcpy(&q, mk, 4);
-                    *reinterpret_cast<uint32_t*>(mp) = q;
-                } else {
-#pragma unroll
-                    for (int j = 0; j < VEC; ++j) mp[j] = mk[j];
-                }
-            } else {
-                mp[0] = mk[0];
-            }
-        }
+        if (mask) store_bytes<VEC == 8 ? 8 : VEC>(mask + row * K + (int64_t)v * VEC, mk, mask_vec);          // one store of the vector's mask
     }
 }
 
 // n:m. A thread owns E consecutive columns of one row, whole groups of M: E = max(M, elements of a 16-byte vector) in the vector
 // form, E = M in the one-element-per-lane form. The rank of an element in its group is the count of the elements that sort
 // before it (smaller key, or the same key at a lower column); no LDS.
+// Its 16-byte accesses and its mask store stay written out here: with vec16.h's Vec / load_vec / store_vec / store_bytes every
+// instantiation compiled to another instruction stream (<float, 16, true> 68 -> 81 VGPRs) and two rows measured slower than the
+// parent commit's, above its spread (bf16 4096 x 4096 2:4 with a mask +1.9 %, fp32 8:16 +1.1 %; profiles/stream_refactor.txt).
 template <typename T, int M, bool VECM>
 __global__ __launch_bounds__(256) void k_prune_nm(T* __restrict__ W, int64_t R, int64_t K, int64_t ld, const float* __restrict__ srow,
                                                   int s_vec, int n_prune, uint8_t* __restrict__ mask, int mask_vec) {
@@ -553,38 +486,13 @@ __device__ __forceinline__ void mag_walk(T* __restrict__ W, int64_t R, int64_t K
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t r = i / vpr, k0 = (i - r * vpr) * VEC;
         T* p = W + r * ld + k0;
-        T v[VEC];
-        if constexpr (VEC > 1) {
-            const uint4 q = *reinterpret_cast<const uint4*>(p);
-            __builtin_memcpy(v, &q, 16);
-        } else {
-            v[0] = *p;
-        }
-        uint8_t mk[VEC];
+        Vec<T, VEC> v = load_vec<T, VEC>(p);
+        Vec<uint8_t, VEC> mk;
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) mk[j] = f(v[j]) ? 1 : 0;
+        for (int j = 0; j < VEC; ++j) mk.v[j] = f(v.v[j]) ? 1 : 0;
         if constexpr (WRITE) {
-            if constexpr (VEC > 1) {
-                uint4 q;
-                __builtin_memcpy(&q, v, 16);
-                *reinterpret_cast<uint4*>(p) = q;
-            } else {
-                *p = v[0];
-            }
-            if (mask) {
-                uint8_t* mp = mask + r * K + k0;
-                if (VEC > 1 && mask_vec) {
-#pragma unroll
-                    for (int j = 0; j < VEC; j += 4) {
-                        uint32_t q;
-                        __builtin_memcpy(&q, &mk[j], 4);
-                        *reinterpret_cast<uint32_t*>(mp + j) = q;
-                    }
-                } else {
-#pragma unroll
-                    for (int j = 0; j < VEC; ++j) mp[j] = mk[j];
-                }
-            }
+            store_vec<T, VEC>(p, v);
+            if (mask) store_bytes<(VEC > 1 ? 4 : 1)>(mask + r * K + k0, mk, mask_vec);
         }
     }
 }
@@ -683,22 +591,12 @@ extern "C" int llmc_col_sqsum(const void* X, int dt, int64_t N, int64_t K, int i
     LLMC_REQUIRE(N < (1ll << 31) + 1 && K < (1ll << 31), "col_sqsum: N up to 2^31 rows, K below 2^31");
     LLMC_REQUIRE(!out || nsamples > 0, "col_sqsum: nsamples must be positive when out is given");
     hipStream_t st = (hipStream_t)stream;
-    const int V = 16 / dtype_size(dt);
-    const bool vec = K % V == 0 && ((uintptr_t)X & 15) == 0;
-    const int v = vec ? V : 1;
     const int64_t nchunk = sq_chunks(N, K, dt);
-    const int64_t rpc = ceil_div64(N, nchunk);
-    const dim3 grid((unsigned)ceil_div64(K, 64 * (int64_t)v), (unsigned)nchunk);
     float* part = (float*)ws;
-    if (vec) {
-        if (dt == LLMC_F16) hipLaunchKernelGGL((k_col_sqsum_partial<f16_t, 8>), grid, dim3(SQ_B), 0, st, (const f16_t*)X, N, K, rpc, part);
-        else if (dt == LLMC_BF16) hipLaunchKernelGGL((k_col_sqsum_partial<bf16_t, 8>), grid, dim3(SQ_B), 0, st, (const bf16_t*)X, N, K, rpc, part);
-        else hipLaunchKernelGGL((k_col_sqsum_partial<float, 4>), grid, dim3(SQ_B), 0, st, (const float*)X, N, K, rpc, part);
-    } else {
-        if (dt == LLMC_F16) hipLaunchKernelGGL((k_col_sqsum_partial<f16_t, 1>), grid, dim3(SQ_B), 0, st, (const f16_t*)X, N, K, rpc, part);
-        else if (dt == LLMC_BF16) hipLaunchKernelGGL((k_col_sqsum_partial<bf16_t, 1>), grid, dim3(SQ_B), 0, st, (const bf16_t*)X, N, K, rpc, part);
-        else hipLaunchKernelGGL((k_col_sqsum_partial<float, 1>), grid, dim3(SQ_B), 0, st, (const float*)X, N, K, rpc, part);
-    }
+    col_reduce_launch(dt, col_vec(X, dt, K), N, K, nchunk, [&](auto t, auto vec, dim3 grid, int64_t rpc) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_col_sqsum_partial<T, decltype(vec)::value>), grid, dim3(SQ_B), 0, st, (const T*)X, N, K, rpc, part);
+    });
     LLMC_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_col_sqsum_fold, dim3((unsigned)ceil_div64(K, SQ_B)), dim3(SQ_B), 0, st, (const float*)part, nchunk, K, init,
                        acc, out, (float)nsamples);

@@ -1,64 +1,16 @@
-// quant_group.h — what every kernel of the IntegerQuantizer builds from quant_math.h's scalar ops, stated once: the 16-byte
-// vector of a lane, the container of an output kind, the step of one quantization group (min / max or given qparams -> hoisted
-// divisor -> code or fake value) and the workgroup's min / max. quant_math.h is the arithmetic; this is how a group runs it.
-// Users: k_quant_static, k_quant_dynamic_small, k_minmax_partial, k_minmax_final (quant_kernels.hip), k_cols_tile, k_cols_apply,
-// k_cols_partial (the vector only) (quant_cols.hip), k_mixed_mask, k_mixed_idx (mixed_quant.hip; they spell the code / fake
-// select themselves), k_osplus_act_step (smooth_osplus.hip). quant_rows (quant_kernels.hip) takes Vec, out_elem and the scalar
-// form of quant_vec, not GroupQuant; load_group (hqq.hip) the vector type alone. Each exception is measured:
-// profiles/quant_group_refactor.txt.
+// quant_group.h — what every kernel of the IntegerQuantizer builds from quant_math.h's scalar ops, stated once: the container of
+// an output kind, the step of one quantization group (min / max or given qparams -> hoisted divisor -> code or fake value) and the
+// workgroup's min / max. quant_math.h is the arithmetic; this is how a group runs it. The 16-byte vector of a lane is vec16.h's.
+// Users: k_quant_static, k_quant_dynamic_small, k_minmax_partial, k_minmax_final (quant_kernels.hip), k_cols_tile, k_cols_apply
+// (quant_cols.hip; k_cols_partial takes vec16.h's vector only), k_mixed_mask, k_mixed_idx (mixed_quant.hip; they spell the code /
+// fake select themselves), k_osplus_act_step (smooth_osplus.hip). quant_rows (quant_kernels.hip) takes Vec, out_elem and the
+// scalar form of quant_vec, not GroupQuant. Each exception is measured: profiles/quant_group_refactor.txt.
 #pragma once
 #include "common.h"
 #include "quant_math.h"
+#include "vec16.h"
 
 namespace llmc {
-
-// ---- N consecutive elements of a lane: one 16-byte access where N * sizeof(T) == 16 (the caller checked the alignment),
-// element by element otherwise ----------------------------------------------------------------------------------------------
-template <typename T, int N> struct Vec {
-    T v[N];
-};
-template <typename T, int N> __device__ __forceinline__ Vec<T, N> load_vec(const T* p) {
-    Vec<T, N> r;
-    if constexpr (N * sizeof(T) == 16) {
-        const uint4 raw = *reinterpret_cast<const uint4*>(p);
-        __builtin_memcpy(&r, &raw, 16);
-    } else {
-#pragma unroll
-        for (int i = 0; i < N; ++i) r.v[i] = p[i];
-    }
-    return r;
-}
-template <typename T, int N> __device__ __forceinline__ void store_vec(T* p, const Vec<T, N>& r) {
-    if constexpr (N * sizeof(T) == 16) {
-        uint4 raw;
-        __builtin_memcpy(&raw, &r, 16);
-        *reinterpret_cast<uint4*>(p) = raw;
-    } else {
-#pragma unroll
-        for (int i = 0; i < N; ++i) p[i] = r.v[i];
-    }
-}
-// the vector of a code container (N int32 / int8 / uint8 beside N elements of T) to a 16-byte aligned p: 32 / 16 / 8-byte stores
-template <typename O, int N> __device__ __forceinline__ void store_vec_wide(O* p, const Vec<O, N>& o) {
-    if constexpr (sizeof(O) * N == 32) {
-        uint4 lo, hi;
-        __builtin_memcpy(&lo, &o.v[0], 16);
-        __builtin_memcpy(&hi, &o.v[N / 2], 16);
-        reinterpret_cast<uint4*>(p)[0] = lo;
-        reinterpret_cast<uint4*>(p)[1] = hi;
-    } else if constexpr (sizeof(O) * N == 16) {
-        uint4 lo;
-        __builtin_memcpy(&lo, &o.v[0], 16);
-        reinterpret_cast<uint4*>(p)[0] = lo;
-    } else if constexpr (sizeof(O) * N == 8) {
-        uint2 lo;
-        __builtin_memcpy(&lo, &o.v[0], 8);
-        reinterpret_cast<uint2*>(p)[0] = lo;
-    } else {
-#pragma unroll
-        for (int k = 0; k < N; ++k) p[k] = o.v[k];
-    }
-}
 
 // what a kernel of output kind KIND writes per element: fake values in the tensor dtype, or codes in KIND's container
 template <int KIND, typename T> struct out_elem;

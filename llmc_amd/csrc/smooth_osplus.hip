@@ -7,6 +7,7 @@
 //                          registers between the range reduction and the quantize. Same bits as llmc_div_cols followed by
 //                          llmc_quant_dynamic (integer) or llmc_fp8_quant (FP8, dynamic per-row scales).
 // All three data passes are HBM-bound; DESIGN.md holds the byte counts they are measured against.
+#include "col_reduce.h"
 #include "common.h"
 #include "float_quant_math.h"
 #include "fp8_math.h"
@@ -20,88 +21,33 @@ static constexpr int SB = 256;            // threads per workgroup, every kernel
 static constexpr int CS_ROWS = 16;        // rows one workgroup of k_col_stats_partial folds per turn (4 per wave)
 static constexpr int CS_MAX_BLOCKS = 2048;
 
-// ---- column statistics, stage 1: grid (column blocks, row chunks); a wave reads 64 consecutive vectors of one row ------
-template <typename T, int VEC>
-__global__ __launch_bounds__(SB) void k_col_stats_partial(const T* __restrict__ X, int64_t N, int64_t K, int64_t rows_per_chunk,
-                                                          float* __restrict__ part) {
-    __shared__ float smx[3][SB / 64 - 1][64 * VEC];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t c = ((int64_t)blockIdx.x * 64 + lane) * VEC;
-    const int64_t r0 = (int64_t)blockIdx.y * rows_per_chunk;
-    const int64_t r1 = r0 + rows_per_chunk < N ? r0 + rows_per_chunk : N;
-    float mx[VEC], mn[VEC], am[VEC];
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) {
-        mx[i] = -INFINITY;
-        mn[i] = INFINITY;
-        am[i] = 0.0f;
-    }
-    if (c < K) {
-#pragma unroll 4
-        for (int64_t r = r0 + wv; r < r1; r += SB / 64) {
-            T v[VEC];
-            if constexpr (VEC * sizeof(T) == 16) {
-                const uint4 raw = *reinterpret_cast<const uint4*>(X + r * K + c);
-                __builtin_memcpy(v, &raw, 16);
-            } else {
-                v[0] = X[r * K + c];
-            }
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                const float f = to_f32<T>(v[i]);
-                // torch.amax / amin / max propagate NaN; fmaxf drops it
-                mx[i] = (f != f || mx[i] != mx[i]) ? NAN : fmaxf(mx[i], f);
-                mn[i] = (f != f || mn[i] != mn[i]) ? NAN : fminf(mn[i], f);
-                am[i] = (f != f || am[i] != am[i]) ? NAN : fmaxf(am[i], fabsf(f));
-            }
-        }
-    }
-    if (wv > 0) {
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) {
-            smx[0][wv - 1][lane * VEC + i] = mx[i];
-            smx[1][wv - 1][lane * VEC + i] = mn[i];
-            smx[2][wv - 1][lane * VEC + i] = am[i];
-        }
-    }
-    __syncthreads();
-    if (wv == 0 && c < K) {
-        float* p = part + (int64_t)blockIdx.y * 3 * K;
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) {
-            float a = mx[i], b = mn[i], d = am[i];
-#pragma unroll
-            for (int w = 0; w < SB / 64 - 1; ++w) {
-                const float a2 = smx[0][w][lane * VEC + i], b2 = smx[1][w][lane * VEC + i], d2 = smx[2][w][lane * VEC + i];
-                a = (a != a || a2 != a2) ? NAN : fmaxf(a, a2);
-                b = (b != b || b2 != b2) ? NAN : fminf(b, b2);
-                d = (d != d || d2 != d2) ? NAN : fmaxf(d, d2);
-            }
-            p[c + i] = a;
-            p[K + c + i] = b;
-            p[2 * K + c + i] = d;
-        }
-    }
-}
-
 __device__ __forceinline__ float nan_max(float a, float b) { return (a != a || b != b) ? NAN : fmaxf(a, b); }
 __device__ __forceinline__ float nan_min(float a, float b) { return (a != a || b != b) ? NAN : fminf(a, b); }
 
-// stage 2: the chunks of one column, folded into the running buffers (init: the running buffers are written, not read)
+// ---- column statistics: col_reduce.h's two stages over max, min and max|x|. torch.amax / amin / max propagate NaN; fmaxf drops it
+struct Extremes {
+    static constexpr int NS = 3;
+    static __device__ __forceinline__ float identity(int s) { return s == 0 ? -INFINITY : (s == 1 ? INFINITY : 0.0f); }
+    static __device__ __forceinline__ void step(float (&a)[3], float f) {
+        a[0] = nan_max(a[0], f);
+        a[1] = nan_min(a[1], f);
+        a[2] = nan_max(a[2], fabsf(f));
+    }
+    static __device__ __forceinline__ float join(int s, float a, float b) { return s == 1 ? nan_min(a, b) : nan_max(a, b); }
+};
+
+template <typename T, int VEC>
+__global__ __launch_bounds__(SB) void k_col_stats_partial(const T* __restrict__ X, int64_t N, int64_t K, int64_t rows_per_chunk,
+                                                          float* __restrict__ part) {
+    col_reduce_partial<Extremes, T, VEC, SB>(X, N, K, rows_per_chunk, part);
+}
+
 __global__ __launch_bounds__(SB) void k_col_stats_fold(const float* __restrict__ part, int64_t nchunk, int64_t K, int init,
                                                        float* __restrict__ run) {
     const int64_t k = (int64_t)blockIdx.x * SB + threadIdx.x;
     if (k >= K) return;
-    float a = init ? -INFINITY : run[k], b = init ? INFINITY : run[K + k], d = init ? 0.0f : run[2 * K + k];
-    for (int64_t ch = 0; ch < nchunk; ++ch) {
-        const float* p = part + ch * 3 * K;
-        a = nan_max(a, p[k]);
-        b = nan_min(b, p[K + k]);
-        d = nan_max(d, p[2 * K + k]);
-    }
-    run[k] = a;
-    run[K + k] = b;
-    run[2 * K + k] = d;
+    float a[3];
+    col_reduce_fold<Extremes>(part, nchunk, K, k, init, run, a);
 }
 
 // stage 3 (optional): glob[0] = max(0, max_k run_max), glob[1] = min(0, min_k run_min) — osplus.py:97-102
@@ -268,14 +214,7 @@ static inline int act_step_tier(int dt, int64_t K) {
 
 using namespace llmc;
 
-static inline int64_t cs_chunks(int64_t N, int64_t K, int vec) {
-    const int64_t colblocks = ceil_div64(K, 64 * (int64_t)vec);
-    int64_t cap = CS_MAX_BLOCKS / colblocks;
-    if (cap < 1) cap = 1;
-    int64_t n = ceil_div64(N, CS_ROWS);
-    if (n > cap) n = cap;
-    return n < 1 ? 1 : n;
-}
+static inline int64_t cs_chunks(int64_t N, int64_t K, int vec) { return col_chunks(N, K, vec, CS_ROWS, CS_MAX_BLOCKS); }
 
 extern "C" size_t llmc_col_stats_ws_bytes(int64_t N, int64_t K) {
     if (N <= 0 || K <= 0) return 0;
@@ -292,22 +231,13 @@ extern "C" int llmc_col_stats(const void* X, int dt, int64_t N, int64_t K, int i
     LLMC_REQUIRE(X && run && ws && N > 0 && K > 0, "col_stats: null/empty argument");
     LLMC_REQUIRE(N < (1ll << 31) + 1 && K < (1ll << 31), "col_stats: N up to 2^31 rows, K below 2^31");
     hipStream_t st = (hipStream_t)stream;
-    const int V = 16 / dtype_size(dt);
-    const bool vec = K % V == 0 && ((uintptr_t)X & 15) == 0;
-    const int v = vec ? V : 1;
-    const int64_t nchunk = cs_chunks(N, K, v);
-    const int64_t rpc = ceil_div64(N, nchunk);
-    const dim3 grid((unsigned)ceil_div64(K, 64 * (int64_t)v), (unsigned)nchunk);
+    const int v = col_vec(X, dt, K);
+    const int64_t nchunk = cs_chunks(N, K, v);          // the form's vector width: max and min do not depend on the order
     float* part = (float*)ws;
-    if (vec) {
-        if (dt == LLMC_F16) hipLaunchKernelGGL((k_col_stats_partial<f16_t, 8>), grid, dim3(SB), 0, st, (const f16_t*)X, N, K, rpc, part);
-        else if (dt == LLMC_BF16) hipLaunchKernelGGL((k_col_stats_partial<bf16_t, 8>), grid, dim3(SB), 0, st, (const bf16_t*)X, N, K, rpc, part);
-        else hipLaunchKernelGGL((k_col_stats_partial<float, 4>), grid, dim3(SB), 0, st, (const float*)X, N, K, rpc, part);
-    } else {
-        if (dt == LLMC_F16) hipLaunchKernelGGL((k_col_stats_partial<f16_t, 1>), grid, dim3(SB), 0, st, (const f16_t*)X, N, K, rpc, part);
-        else if (dt == LLMC_BF16) hipLaunchKernelGGL((k_col_stats_partial<bf16_t, 1>), grid, dim3(SB), 0, st, (const bf16_t*)X, N, K, rpc, part);
-        else hipLaunchKernelGGL((k_col_stats_partial<float, 1>), grid, dim3(SB), 0, st, (const float*)X, N, K, rpc, part);
-    }
+    col_reduce_launch(dt, v, N, K, nchunk, [&](auto t, auto vec, dim3 grid, int64_t rpc) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_col_stats_partial<T, decltype(vec)::value>), grid, dim3(SB), 0, st, (const T*)X, N, K, rpc, part);
+    });
     LLMC_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_col_stats_fold, dim3((unsigned)ceil_div64(K, SB)), dim3(SB), 0, st, (const float*)part, nchunk, K,
                        init, run);
@@ -325,9 +255,8 @@ extern "C" int llmc_smooth_scales(const float* x_absmax, const float* w_absmax, 
     LLMC_REQUIRE(x_absmax && w_absmax && out && K > 0, "smooth_scales: null/empty argument");
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)ceil_div64(K, SB));
-    if (dt == LLMC_F16) hipLaunchKernelGGL((k_smooth_scales<f16_t>), grid, dim3(SB), 0, st, x_absmax, w_absmax, K, (float)alpha, (float)one_minus_alpha, (f16_t*)out);
-    else if (dt == LLMC_BF16) hipLaunchKernelGGL((k_smooth_scales<bf16_t>), grid, dim3(SB), 0, st, x_absmax, w_absmax, K, (float)alpha, (float)one_minus_alpha, (bf16_t*)out);
-    else hipLaunchKernelGGL((k_smooth_scales<float>), grid, dim3(SB), 0, st, x_absmax, w_absmax, K, (float)alpha, (float)one_minus_alpha, (float*)out);
+    DISPATCH_DT(dt, hipLaunchKernelGGL((k_smooth_scales<T>), grid, dim3(SB), 0, st, x_absmax, w_absmax, K, (float)alpha,
+                                       (float)one_minus_alpha, (T*)out));
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;
 }
@@ -339,9 +268,7 @@ extern "C" int llmc_osplus_scale(const float* cmx, const float* cmn, const void*
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)ceil_div64(K, SB));
     const char* thr = (const char*)thresholds + (size_t)index * dtype_size(dt);
-    if (dt == LLMC_F16) hipLaunchKernelGGL((k_osplus_scale<f16_t>), grid, dim3(SB), 0, st, cmx, cmn, (const f16_t*)thr, K, (f16_t*)out);
-    else if (dt == LLMC_BF16) hipLaunchKernelGGL((k_osplus_scale<bf16_t>), grid, dim3(SB), 0, st, cmx, cmn, (const bf16_t*)thr, K, (bf16_t*)out);
-    else hipLaunchKernelGGL((k_osplus_scale<float>), grid, dim3(SB), 0, st, cmx, cmn, (const float*)thr, K, (float*)out);
+    DISPATCH_DT(dt, hipLaunchKernelGGL((k_osplus_scale<T>), grid, dim3(SB), 0, st, cmx, cmn, (const T*)thr, K, (T*)out));
     LLMC_LAUNCH_CHECK();
     return LLMC_OK;
 }

@@ -256,6 +256,46 @@ def test_col_sqsum_is_deterministic_and_within_the_fp32_summation_bound():
         assert torch.equal(S.col_sqsum(y).view(torch.int32), S.col_sqsum(y).view(torch.int32))
 
 
+@pytest.mark.parametrize('N,K,dname', O.SQSUM_ORDER_CASES)
+def test_col_sqsum_adds_in_the_order_the_header_promises(N, K, dname):
+    """bit for bit against O.col_sqsum_ordered, the numpy restatement of include/llmc_hip.h's order, on inputs on which other
+    orders give other bits (test_sparse_oracle.py)"""
+    dt = DTYPES[dname]
+    S = ops()
+    x = O.sqsum_order_input(N, K, dt)
+    want = O.col_sqsum_ordered(x, dt)
+    acc, out = S.col_sqsum(x.cuda(), nsamples=7)
+    assert torch.equal(O.bits(acc.cpu()), O.bits(want)), (N, K, dname)
+    assert torch.equal(O.bits(out.cpu()), O.bits(want / 7.0))
+
+
+@pytest.mark.parametrize('dname', ['bf16', 'f32'])
+def test_col_sqsum_keeps_its_order_on_scalar_loads_and_folds_a_second_batch(dname):
+    dt = DTYPES[dname]
+    S = ops()
+    # the same data at an address that is no multiple of 16 bytes: other loads, the same order
+    x = O.sqsum_order_input(130, 64, dt)
+    want = O.col_sqsum_ordered(x, dt)
+    buf = torch.empty(130 * 64 + 1, dtype=dt, device='cuda')
+    view = buf[1:].view(130, 64)
+    view.copy_(x)
+    assert view.data_ptr() % 16 != 0
+    assert torch.equal(O.bits(S.col_sqsum(view).cpu()), O.bits(want))
+    assert torch.equal(O.bits(S.col_sqsum(x.cuda()).cpu()), O.bits(want))
+    # a K that is no whole number of vectors: scalar loads again, and the chunk count still takes the dtype's vector width
+    y = O.sqsum_order_input(300, 70, dt, seed=32)
+    first = O.col_sqsum_ordered(y, dt)
+    acc = S.col_sqsum(y.cuda())
+    assert torch.equal(O.bits(acc.cpu()), O.bits(first))
+    # init=False: acc + batch, one fp32 add, and out = acc / float32(nsamples)
+    z = O.sqsum_order_input(65, 70, dt, seed=33)
+    acc2, out = S.col_sqsum(z.cuda(), acc, init=False, nsamples=3)
+    assert acc2 is acc
+    both = first + O.col_sqsum_ordered(z, dt)
+    assert torch.equal(O.bits(acc.cpu()), O.bits(both))
+    assert torch.equal(O.bits(out.cpu()), O.bits(both / 3.0))
+
+
 # ---- global magnitude pruning ----------------------------------------------------------------------------------------------------
 MAG_CASES = [('bf16', 384, 256, None, 0), ('f16', 384, 256, None, 0), ('f32', 64, 250, None, 0), ('f32', 64, 256, None, 0),
              ('bf16', 384, 256, 264, 0), ('f32', 64, 256, 260, 0), ('f16', 100, 250, 251, 0), ('bf16', 384, 256, None, 1)]

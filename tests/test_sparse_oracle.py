@@ -81,6 +81,27 @@ def test_magnitude_reproduces_the_reference(name):
     assert int(mask.sum()) >= int(G[f'{name}/kth']) + 1
 
 
+@pytest.mark.parametrize('N,K,dname', O.SQSUM_ORDER_CASES)
+def test_the_ordered_column_sum_tells_its_order_from_others(N, K, dname):
+    """col_sqsum_ordered on the inputs of the GPU order test: another order of the same fp32 adds gives other bits there, so a
+    kernel that passes the GPU test has the header's order and not merely a sum within the fp32 bound."""
+    dt = DT[dname]
+    x = O.sqsum_order_input(N, K, dt)
+    want = O.col_sqsum_ordered(x, dt)
+    assert want.dtype == torch.float32 and want.shape == (K,)
+    f = x.float().numpy()
+    plain = np.zeros(K, dtype=np.float32)
+    for r in range(N):
+        plain = plain + f[r] * f[r]
+    if N > 4:          # up to four rows, one per wave: ((x0 + x1) + x2) + x3 is the row order
+        assert (plain != want.numpy()).any()
+    else:
+        assert np.array_equal(plain, want.numpy())
+    assert not torch.equal(O.col_sqsum_ordered(x, dt, waves=2), want)
+    if K == 262144:          # the block cap binds: the chunk count depends on the vector width
+        assert not torch.equal(O.col_sqsum_ordered(x, dt, v=8), want)
+
+
 def test_n_m_groups_and_nan_order():
     w = torch.tensor([[0.5, -0.5, 0.25, float('nan'), float('inf'), 1.0, -0.0, 0.0]])
     out, mask = O.prune_rows(w, None, 2, 4)

@@ -747,6 +747,31 @@ int llmc_sparsegpt_prune(float* W, const float* Hinv, int64_t R, int64_t K, doub
                          int64_t prune_m, float* Wout, float* losses, uint8_t* mask, int blocksize, void* ws,
                          llmc_stream_t stream);
 
+/* NaiveQuantKVCache.update / KiviQuantKVCache.update (kvquant.py:44-87, 233-289) for keys and values in one launch: the stored
+ * rows are dequantized, the new rows appended, and with LLMC_KV_REQUANT every row's codes and qparams are derived again from those
+ * values, in place, as the reference's quantize(cat(dequantize(cache), new)) does. Per tensor (k_*, v_*; the v_* set may be all
+ * NULL):
+ *   codes   [B * H, cap, D] one code per byte: int8 when qmin < 0, uint8 otherwise (qmin >= -128, qmax <= 255 / 127)
+ *   scales  [B * H, cap, D / g] of dt; zeros the same, NULL exactly when sym
+ *   new     the rows [B, H, n_new, D] of dt with the element strides new_stride_b / _h / _t shared by both tensors (the
+ *           [B, T, H, D].transpose(1, 2) view of an attention module is read in place); unit stride along D
+ *   out     [B, H, T_old + n_new, D] contiguous of dt: what update() returns; may be NULL with LLMC_KV_REQUANT
+ * Rows t < T_old: out = rnd(rnd(q - z) * s) (quant.py:709-712). Rows t >= T_old: out = the new row, or with LLMC_KV_NEW_FAKE
+ * (needs LLMC_KV_REQUANT) its dequant(quant(.)) (the Naive cache's prefill). LLMC_KV_REQUANT: per group of g elements, min / max of
+ * the row's `out` values before NEW_FAKE -> get_qparams (quant.py:545-559, minmax) -> codes and qparams stored to row t of the
+ * same slots. Without it nothing in the store is written (Kivi between two flushes).
+ * An old element costs 1 byte read and 2 + 1 written. Stream-ordered, no workspace, no allocation.
+ * LLMC_EINVAL, before anything is launched: bad dt or flags, B, H, D, g < 1, D % g != 0, T_old + n_new < 1, cap < T_old (or
+ * < T_old + n_new with REQUANT), a missing pointer, zeros given when sym or missing when not, codes / new / out not 16-byte aligned.
+ * LLMC_ENOTSUP (callers compose the update from the quantizer's operators): round_zp != 1, codes of more than 8 bits, g not 16
+ * bytes times a power of two <= 64, new-row strides that are not multiples of 16 bytes, B * H > 65535, T * D / g >= 2^31. */
+#define LLMC_KV_REQUANT 1
+#define LLMC_KV_NEW_FAKE 2
+int llmc_kv_cache_update(int dt, int64_t B, int64_t H, int64_t T_old, int64_t n_new, int64_t cap, int64_t D, int64_t g, int sym,
+                         int round_zp, float qmin, float qmax, int flags, void* k_codes, void* k_scales, void* k_zeros,
+                         const void* k_new, void* k_out, void* v_codes, void* v_scales, void* v_zeros, const void* v_new,
+                         void* v_out, int64_t new_stride_b, int64_t new_stride_h, int64_t new_stride_t, llmc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

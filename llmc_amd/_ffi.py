@@ -14,6 +14,7 @@ OUT_FAKE, OUT_I32, OUT_I8, OUT_U8 = 0, 1, 2, 3
 SCALAR_QPARAM = 16   # LLMC_SCALAR_QPARAM
 LINEAR_YBLOCKED = 4   # LLMC_LINEAR_YBLOCKED
 FRACTIONAL_ZP = 32    # LLMC_FRACTIONAL_ZP
+KV_REQUANT, KV_NEW_FAKE = 1, 2   # LLMC_KV_REQUANT, LLMC_KV_NEW_FAKE
 
 _DT = {torch.float16: F16, torch.bfloat16: BF16, torch.float32: F32}
 
@@ -134,6 +135,8 @@ SIGNATURES = {
     'llmc_magnitude_prune': (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     'llmc_sparsegpt_prune_ws_bytes': (_sz, [_i64, _i64]),
     'llmc_sparsegpt_prune': (_i32, [_vp, _vp, _i64, _i64, _f64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _vp]),
+    'llmc_kv_cache_update': (_i32, [_i32, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
     'llmc_test_sgemm': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                _i32, _i32, _vp]),
     'llmc_test_sgemm_phased': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -58,6 +58,32 @@ class BlockwiseOpt(ABC):
         (inp,) = captured
         feat_dict[name].append(inp.unsqueeze(0) if inp.dim() == 2 else inp)
 
+    def kv_cache_input_hook(self, attn_layer):
+        """blockwise_optimization.py:63-101 without its KV-sparse branch: a forward pre-hook that hands the attention module
+        its `kvcache` under the keyword its forward accepts (past_key_value, renamed past_key_values in later transformers
+        releases). With eval.type decode_ppl the positions are re-derived from the cache's length."""
+        import inspect
+        params = inspect.signature(attn_layer.forward).parameters
+        names = [n for n in ('past_key_values', 'past_key_value') if n in params]
+        key = names[0] if names else 'past_key_value'
+
+        def hook_fn(module, args, kwargs):
+            kvcache = getattr(module, 'kvcache')
+            kwargs[key] = kvcache
+            ev = (self.config.get('eval') if isinstance(self.config, dict) else getattr(self.config, 'eval', None)) or {}
+            if ev.get('type', None) == 'decode_ppl':
+                past_seen_tokens = kvcache.get_seq_length()
+                cache_position = torch.arange(past_seen_tokens, past_seen_tokens + kwargs['hidden_states'].shape[1],
+                                              device=kwargs['hidden_states'].device)
+                kwargs['cache_position'] = cache_position
+                position_ids = cache_position.unsqueeze(0)
+                kwargs['position_ids'] = position_ids
+                if 'position_embeddings' in kwargs:
+                    kwargs['position_embeddings'] = self.model.rotary_emb(kwargs['hidden_states'], position_ids)
+            return args, kwargs
+
+        return hook_fn
+
     @abstractmethod
     def block_opt(self, block):
         ...

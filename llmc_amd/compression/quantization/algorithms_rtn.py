@@ -19,6 +19,8 @@ class RTN(BaseBlockwiseQuantization):
 
     @torch.no_grad()
     def block_opt(self, block, *opt_kwargs):
+        if self.quant_kvcache:                      # rtn.py:16-17
+            self.register_kv_cache(block)
         # static activation quantization is the one case that needs the hooks and a forward pass
         if not self.act_static:
             return None

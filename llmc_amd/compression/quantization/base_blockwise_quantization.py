@@ -4,8 +4,10 @@ subclasses registered in ALGO_REGISTRY ('GPTQ', 'Awq', 'RTN') drop into llmc's `
 
 In scope: quantizer selection, collect_block_qparams, the block / subset loop with
 true_sequential re-hooking and quant_out, apply_scale (LN->fc and fc->fc), scaling_input/update_input_feat,
-static per-tensor activation qparams, deploy to fake / real-quant wrappers. Out of scope and rejected loudly:
-KV-cache quantization, quantized attention / act-fn modules, token reduction, FP8
+static per-tensor activation qparams, deploy to fake / real-quant wrappers, the `kvcache` section (base_…:200-216, 540-546,
+973-981: a Naive or Kivi quantized KV cache from kvquant.py, registered on every block's attention module and switched by the
+deploy format; refused when static, under act.static, or without bit / symmetric / granularity). Out of scope and rejected
+loudly: quantized attention / act-fn modules, token reduction, FP8
 block-wise checkpoints (DeepSeek). Mixed precision (`ignored_layers`) is in since round 4. QuaRot's rotations
 (rotate_* / fuse_ln_fcs / replace_rotate_linears, base_…:286-300, 780-874) run on the Walsh-Hadamard kernel
 (hadamard_utils.py); `special.online_rotate` is taken by the classes that set `supports_online_rotate` (Quarot, GPTQ).
@@ -160,9 +162,7 @@ class BaseBlockwiseQuantization(BlockwiseOpt):
             self.aquantizer = None
             self.act_static = False
         self.quant_attn = self.quant_softmax = self.quant_act_fn = False
-        if 'kvcache' in qc:
-            raise NotImplementedError('KV-cache quantization is outside the hot path')
-        self.quant_kvcache = False
+        self.set_kvcache_config(qc)
 
         special = _get(qc, 'special', {}) or {}
         self.true_sequential = special.get('true_sequential', False)
@@ -209,6 +209,54 @@ class BaseBlockwiseQuantization(BlockwiseOpt):
                     raise NotImplementedError(f'online rotation needs model_config.{k}')
             get_hadK(self.intermediate_size)
             get_hadK(self.num_heads)
+
+    def set_kvcache_config(self, qc):
+        """base_…:200-216: a `kvcache` section builds the cache every attention module of the model will share (kvquant.py)
+        and hands it to the model's kvcache_buffer. The reference has no defaults for bit / symmetric / granularity (its
+        quantizer's constructor fails without them); here such a section is refused by name. act.static would make the
+        cache static too (base_…:202), which the reference cannot construct itself (:206 calls dict.update with an int)."""
+        if 'kvcache' not in qc:
+            self.quant_kvcache = False
+            return
+        kv = qc['kvcache']
+        missing = [k for k in ('method', 'bit', 'symmetric', 'granularity') if _get(kv, k) is None]
+        if missing:
+            raise NotImplementedError(f"KV-cache quantization needs kvcache.{' / kvcache.'.join(missing)}: the section has no "
+                                      'defaults for them')
+        if _get(kv, 'granularity') not in ('per_token', 'per_group', 'per_tensor'):
+            raise NotImplementedError(f"KV-cache quantization with granularity {_get(kv, 'granularity')!r}: per_token, per_group "
+                                      'and per_tensor are the cache\'s granularities (kvquant.py:15)')
+        if self.act_static:
+            raise NotImplementedError('KV-cache quantization under act.static is outside the hot path: it makes the cache static '
+                                      "(base_blockwise_quantization.py:202), and the reference's own route to a static cache "
+                                      'cannot be constructed (:206 calls dict.update with an int)')
+        from llmc_amd.utils.registry_factory import KV_REGISTRY
+        from . import kvquant  # noqa: F401  (registers 'Naive' and 'Kivi')
+        method = _get(kv, 'method')
+        if method not in KV_REGISTRY:
+            raise NotImplementedError(f'KV-cache method {method!r} is not implemented (have: {sorted(KV_REGISTRY)})')
+        kv = dict(kv)
+        kv['static'] = self.act_static
+        mc = getattr(self.model, 'model_config', None)
+        num_layers = getattr(mc, 'num_hidden_layers', None) or self.num_blocks
+        self.kv_module = KV_REGISTRY[method](kv.get('quant_type', 'int-quant'), kv, num_layers, **(kv.get('special') or {}))
+        self.quant_kvcache = True
+        self.model.kvcache_buffer.append(self.kv_module)
+
+    @torch.no_grad()
+    def register_kv_cache(self, block):
+        """base_…:540-546: the block's attention module carries the shared cache and receives it as a keyword on every call."""
+        if hasattr(self.model, 'get_attn_in_block'):
+            attn_layers = self.model.get_attn_in_block(block)
+            attn_layer = attn_layers[list(attn_layers.keys())[0]]
+        else:
+            found = [m for n, m in block.named_modules() if n.split('.')[-1] in ('self_attn', 'attn', 'attention')]
+            if not found:
+                raise NotImplementedError('register_kv_cache: the model adapter has no get_attn_in_block and the block no '
+                                          'self_attn / attn / attention module')
+            attn_layer = found[0]
+        setattr(attn_layer, 'kvcache', self.kv_module)
+        attn_layer.register_forward_pre_hook(self.kv_cache_input_hook(attn_layer), with_kwargs=True)
 
     def set_model_config(self):
         mc = getattr(self.model, 'model_config', None)
@@ -272,6 +320,8 @@ class BaseBlockwiseQuantization(BlockwiseOpt):
         modules = {**named_linears, **extra_modules}
         input_feat = defaultdict(list)
         handles = self.register_hooks(modules, input_feat)
+        if self.quant_kvcache:                      # base_…:394-395
+            self.register_kv_cache(block)
         self.block_init(block)
         self.run(block, input_feat, handles)
         block = block.cpu()
@@ -586,6 +636,11 @@ class BaseBlockwiseQuantization(BlockwiseOpt):
         self.model.replace_language_module_all(mapping[quant_format],
                                                self.get_replacement_params(quant_format, self.w_only),
                                                keep_device=keep_device)
+        if self.quant_kvcache:                      # base_…:973-981 (a static cache's `calib` switch has no counterpart here)
+            if quant_format in ('origin_float', 'fake_quant_wo_kv'):
+                self.kv_module.use_org_kv = True
+            elif quant_format == 'fake_quant':
+                self.kv_module.use_org_kv = False
 
     @torch.no_grad()
     def save_model(self, path):

@@ -96,6 +96,7 @@ int llmc_hip_set_cu_reserve(int n_cus);
  *   no_riders         without helper streams, a column group's far update as one launch over all later columns; default: the
  *                     128 x 128 tiles of its last columns ride on the next group's in-block launches instead (k_gptq_block_riders,
  *                     one tile per CU the chain leaves free); same bits
+ *   kv_sink_max_grid  n > 0: llmc_kv_sink_update launches at most n blocks per tensor and grid-strides the rest (tests); same bits
  * set: returns the previous value, or LLMC_EINVAL for an unknown key / negative value. get: the value, or LLMC_EINVAL.
  * option_name: the key of index 0, 1, ... (copied into buf), LLMC_EINVAL past the last one. No reference counterpart. */
 int llmc_hip_set_option(const char* key, int value);
@@ -771,6 +772,29 @@ int llmc_kv_cache_update(int dt, int64_t B, int64_t H, int64_t T_old, int64_t n_
                          int round_zp, float qmin, float qmax, int flags, void* k_codes, void* k_scales, void* k_zeros,
                          const void* k_new, void* k_out, void* v_codes, void* v_scales, void* v_zeros, const void* v_new,
                          void* v_out, int64_t new_stride_b, int64_t new_stride_h, int64_t new_stride_t, llmc_stream_t stream);
+
+/* SinkKVCache.update (kvsparse.py:569-648: StreamingLLM's attention-sink window) for keys and values in one launch. src and dst
+ * are [B * H, src_cap, D] and [B * H, dst_cap, D] buffers of dt per tensor (k_*, v_*; the v_* set may be all NULL). Per (b, h),
+ * destination rows from dst_row0 on:
+ *   [0, n_sink)             <- source rows [0, n_sink), copied
+ *   the next n_keep rows    <- source rows [keep_from, keep_from + n_keep). Keys with cos / sin given ([n_keep, rot] contiguous
+ *                              of dt): row i is rotated again, out = rnd(rnd(k * cos[i]) + rnd(rotate_half(k) * sin[i])) over the
+ *                              first rot columns (rotate_half = cat(-k[rot / 2:rot], k[:rot / 2]); rnd rounds to dt, every
+ *                              product and the sum on its own, no fused multiply-add); columns >= rot are copied
+ *                              (partial_rotation_size). Values, and keys without cos / sin: copied.
+ *   the next n_new rows     <- the new states [B, H, n_new, D] with the element strides new_stride_b / _h / _t shared by both
+ *                              tensors (the [B, T, H, D].transpose(1, 2) view of an attention module is read in place)
+ * A cached element is read once and written once. src == dst is allowed only with n_sink == n_keep == 0 (append in place at
+ * dst_row0; src may then be NULL); src and dst must not overlap otherwise. Stream-ordered, no workspace, no allocation.
+ * LLMC_EINVAL, before anything is launched: bad dt, B, H, D < 1, a negative count or row, nothing to write, cos without sin, rot
+ * odd or outside (0, D] (rot is ignored without cos / sin), dst_row0 + n_sink + n_keep + n_new > dst_cap, n_sink or
+ * keep_from + n_keep > src_cap, a missing pointer, src == dst while rows are moved.
+ * LLMC_ENOTSUP (callers compose the update from tensor ops): D or rot / 2 not a multiple of the 16-byte vector, a source,
+ * destination, table or new-row pointer or a new-row stride that is not 16-byte aligned, B * H * rows * vectors >= 2^31. */
+int llmc_kv_sink_update(int dt, int64_t B, int64_t H, int64_t D, int64_t n_sink, int64_t keep_from, int64_t n_keep, int64_t n_new,
+                        int64_t src_cap, int64_t dst_cap, int64_t dst_row0, int64_t rot, const void* cos, const void* sin,
+                        const void* k_src, void* k_dst, const void* k_new, const void* v_src, void* v_dst, const void* v_new,
+                        int64_t new_stride_b, int64_t new_stride_h, int64_t new_stride_t, llmc_stream_t stream);
 
 #ifdef __cplusplus
 }

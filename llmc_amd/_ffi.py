@@ -137,6 +137,8 @@ SIGNATURES = {
     'llmc_sparsegpt_prune': (_i32, [_vp, _vp, _i64, _i64, _f64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _vp]),
     'llmc_kv_cache_update': (_i32, [_i32, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp,
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
+    'llmc_kv_sink_update': (_i32, [_i32, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
     'llmc_test_sgemm': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                _i32, _i32, _vp]),
     'llmc_test_sgemm_phased': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -84,6 +84,21 @@ class BlockwiseOpt(ABC):
 
         return hook_fn
 
+    @torch.no_grad()
+    def register_kv_cache(self, block):
+        """base_…:540-546: the block's attention module carries the shared cache and receives it as a keyword on every call."""
+        if hasattr(self.model, 'get_attn_in_block'):
+            attn_layers = self.model.get_attn_in_block(block)
+            attn_layer = attn_layers[list(attn_layers.keys())[0]]
+        else:
+            found = [m for n, m in block.named_modules() if n.split('.')[-1] in ('self_attn', 'attn', 'attention')]
+            if not found:
+                raise NotImplementedError('register_kv_cache: the model adapter has no get_attn_in_block and the block no '
+                                          'self_attn / attn / attention module')
+            attn_layer = found[0]
+        setattr(attn_layer, 'kvcache', self.kv_module)
+        attn_layer.register_forward_pre_hook(self.kv_cache_input_hook(attn_layer), with_kwargs=True)
+
     @abstractmethod
     def block_opt(self, block):
         ...

@@ -233,7 +233,8 @@ class BaseBlockwiseQuantization(BlockwiseOpt):
         from llmc_amd.utils.registry_factory import KV_REGISTRY
         from . import kvquant  # noqa: F401  (registers 'Naive' and 'Kivi')
         method = _get(kv, 'method')
-        if method not in KV_REGISTRY:
+        # the registry also holds the KV-sparse caches ('SinkKV') once the sparsification package is imported: those are sparse.kvcache's
+        if method not in KV_REGISTRY or not issubclass(KV_REGISTRY[method], kvquant.NaiveQuantKVCache):
             raise NotImplementedError(f'KV-cache method {method!r} is not implemented (have: {sorted(KV_REGISTRY)})')
         kv = dict(kv)
         kv['static'] = self.act_static
@@ -242,21 +243,6 @@ class BaseBlockwiseQuantization(BlockwiseOpt):
         self.kv_module = KV_REGISTRY[method](kv.get('quant_type', 'int-quant'), kv, num_layers, **(kv.get('special') or {}))
         self.quant_kvcache = True
         self.model.kvcache_buffer.append(self.kv_module)
-
-    @torch.no_grad()
-    def register_kv_cache(self, block):
-        """base_…:540-546: the block's attention module carries the shared cache and receives it as a keyword on every call."""
-        if hasattr(self.model, 'get_attn_in_block'):
-            attn_layers = self.model.get_attn_in_block(block)
-            attn_layer = attn_layers[list(attn_layers.keys())[0]]
-        else:
-            found = [m for n, m in block.named_modules() if n.split('.')[-1] in ('self_attn', 'attn', 'attention')]
-            if not found:
-                raise NotImplementedError('register_kv_cache: the model adapter has no get_attn_in_block and the block no '
-                                          'self_attn / attn / attention module')
-            attn_layer = found[0]
-        setattr(attn_layer, 'kvcache', self.kv_module)
-        attn_layer.register_forward_pre_hook(self.kv_cache_input_hook(attn_layer), with_kwargs=True)
 
     def set_model_config(self):
         mc = getattr(self.model, 'model_config', None)

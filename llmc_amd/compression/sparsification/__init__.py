@@ -2,3 +2,5 @@ from .base_blockwise_sparsification import BaseBlockwiseSparsification  # noqa: 
 from .wanda import Wanda  # noqa: F401
 from .magnitude import Magnitude  # noqa: F401
 from .sparsegpt import SparseGPT  # noqa: F401
+from .dense import Dense  # noqa: F401
+from .kvsparse import SinkKVCache  # noqa: F401

@@ -12,8 +12,14 @@ Config (the `sparse` section, configs/sparsification/methods/Wanda/wanda.yml):
   weight.sparsity_type    new key. 'unstructured' (default), or 'n:m' — zero n of every m consecutive input channels, m in
                           {2, 4, 8, 16} ('2:4' is the pattern the CDNA sparse matrix instructions consume). With n:m, `sparsity`
                           must be absent or equal to n / m.
-  kvcache                 NotImplementedError: the KV-sparse caches (ShadowKV, SinkKV) are inference-time hooks outside the
-                          weight-compression path, like KV-cache quantization in the quantization base.
+  kvcache                 the KV-sparse caches (configs/sparsification/methods/Kvsparse/*.yml). Only `method: Dense` accepts the
+                          section. method SinkKV with window_length and num_sink_tokens (each refused by name when absent)
+                          builds a kvsparse.SinkKVCache, appends it to model.kvcache_buffer and sets sparse_kvcache; block_opt
+                          then hangs it on every block's attention module (register_kv_cache). method ShadowKV is refused by
+                          name: it needs an SVD of the keys, a replaced attention module and a gathered low-rank GEMM, none of
+                          which is built. Under Wanda, Magnitude and SparseGPT the section is refused: they run every
+                          calibration sample through the hooked attention, which in the reference feeds all samples into one
+                          shared, never-reset window.
 
 Departures from the reference, which does not run as shipped:
   * block_transform (base_blockwise_sparsification.py:156-177) calls subset_transform with six positional arguments
@@ -57,6 +63,7 @@ def parse_sparsity_type(value):
 
 class BaseBlockwiseSparsification(BlockwiseOpt):
     needs_input_feat = True          # a method that reads no activations (Magnitude) registers no hooks
+    accepts_kvcache = False          # only Dense: it runs no calibration forward through the hooked attention
 
     def __init__(self, model, sparsity_config, input, padding_mask, config):
         super().__init__(model, sparsity_config, input, padding_mask, config)
@@ -68,10 +75,9 @@ class BaseBlockwiseSparsification(BlockwiseOpt):
     def set_sparsity_config(self):
         cfg = self.sparsity_config
         self.sparsity_out = bool(_has(cfg, 'sparsity_out') and cfg['sparsity_out'])
-        if _has(cfg, 'kvcache'):
-            raise NotImplementedError('KV-cache sparsification (ShadowKV / SinkKV) is an inference-time hook outside the '
-                                      'weight-compression path')
         self.sparse_kvcache = False
+        if _has(cfg, 'kvcache'):
+            self.set_kv_sparse_config()
         self.nm = None
         if _has(cfg, 'weight'):
             w = cfg['weight']
@@ -89,6 +95,34 @@ class BaseBlockwiseSparsification(BlockwiseOpt):
                 self.n_prune_layers = w['n_prune_layers']
         if hasattr(self, 'sparsity'):
             self.sparser = SimpleNamespace(sparsity=self.sparsity)
+
+    def set_kv_sparse_config(self):
+        """base_…:46-62: the `kvcache` section builds the cache named by its method and hands it to the model's kvcache_buffer."""
+        kv = self.sparsity_config['kvcache']
+        method = kv['method'] if _has(kv, 'method') else None
+        if not self.accepts_kvcache:
+            raise NotImplementedError(
+                f'a KV-cache section under sparse.method {type(self).__name__}: only Dense accepts it. A weight-pruning method runs '
+                "every calibration sample through the hooked attention, which in the reference feeds all samples into one shared, "
+                'never-reset window')
+        if method == 'ShadowKV':
+            raise NotImplementedError('KV-cache method ShadowKV is not built: it needs an SVD of the prompt keys, a replaced attention '
+                                      'module (replace_attention) and a gathered low-rank GEMM; SinkKV is the KV-sparse cache built here')
+        from llmc_amd.utils.registry_factory import KV_REGISTRY
+        from . import kvsparse
+        if method not in KV_REGISTRY or not issubclass(KV_REGISTRY[method], kvsparse.SinkKVCache):
+            raise NotImplementedError(f'KV-cache method {method!r} is not a KV-sparse cache (have: SinkKV)')
+        missing = [k for k in ('window_length', 'num_sink_tokens') if not _has(kv, k) or kv[k] is None]
+        if missing:
+            raise NotImplementedError(f"KV-cache method SinkKV needs kvcache.{' / kvcache.'.join(missing)}: the section has no "
+                                      'defaults for them')
+        if _has(kv, 'replace_attn') and kv['replace_attn']:
+            self.replace_attention(None)
+        mc = getattr(self.model, 'model_config', None)
+        num_layers = getattr(mc, 'num_hidden_layers', None) or self.num_blocks
+        self.kv_module = KV_REGISTRY[method](num_layers, kv['window_length'], kv['num_sink_tokens'])
+        self.sparse_kvcache = True
+        self.model.kvcache_buffer.append(self.kv_module)
 
     def replace_attention(self, block):
         raise NotImplementedError('replace_attention belongs to the KV-sparse caches, which are outside the weight-compression path')

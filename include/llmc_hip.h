@@ -97,6 +97,8 @@ int llmc_hip_set_cu_reserve(int n_cus);
  *                     128 x 128 tiles of its last columns ride on the next group's in-block launches instead (k_gptq_block_riders,
  *                     one tile per CU the chain leaves free); same bits
  *   kv_sink_max_grid  n > 0: llmc_kv_sink_update launches at most n blocks per tensor and grid-strides the rest (tests); same bits
+ *   block_influence_max_grid  n > 0: llmc_block_influence's row kernel launches at most n blocks and grid-strides the rest (tests);
+ *                     same bits
  * set: returns the previous value, or LLMC_EINVAL for an unknown key / negative value. get: the value, or LLMC_EINVAL.
  * option_name: the key of index 0, 1, ... (copied into buf), LLMC_EINVAL past the last one. No reference counterpart. */
 int llmc_hip_set_option(const char* key, int value);
@@ -795,6 +797,34 @@ int llmc_kv_sink_update(int dt, int64_t B, int64_t H, int64_t D, int64_t n_sink,
                         int64_t src_cap, int64_t dst_cap, int64_t dst_row0, int64_t rot, const void* cos, const void* sin,
                         const void* k_src, void* k_dst, const void* k_new, const void* v_src, void* v_dst, const void* v_new,
                         int64_t new_stride_b, int64_t new_stride_h, int64_t new_stride_t, llmc_stream_t stream);
+
+/* ShortGPT.compute_bi (shortgpt.py:40-55: Block Influence, one cosine per token between a block's input and its output) without
+ * the reference's N x N product. X, Y [N, d] of dt with unit column stride and row strides ldx, ldy >= d elements; each element
+ * of the two is read once.
+ *   per row: dot = sum x y, sx = sum x x, sy = sum y y in fp32, every product and every add rounded on its own (no fused
+ *   multiply-add); sim = dot / (sqrtf(sx) * sqrtf(sy)), IEEE square roots and division (the reference's dot / (norm_in *
+ *   norm_out)); a NaN sim becomes 0.5 and +-inf becomes +-FLT_MAX (nan_to_num(nan=0.5)); bi[row] = 1 - sim. bi fp32 [N] is
+ *   always written.
+ *   total (one fp64 on the device): the fp64 sum of bi[0 .. N - 1]; init != 0: written, else total = total + batch.
+ * The order of summation, a function of (N, d, dt) alone, so equal calls give equal bits whatever the grid:
+ *   a row is cut into slots of v = 16 / sizeof(dt) consecutive elements, the last one partial when d % v != 0. One wave owns the
+ *   row; lane l folds the slots l, l + 64, l + 128, ... in that order, the elements of a slot in index order, onto three
+ *   sums that start at +0: s = s + x y. The 64 lane values are joined by the xor butterfly with the offsets 32, 16, 8, 4, 2, 1:
+ *   at every step lane l's value becomes v[l] + v[l ^ offset] (a lane without a slot holds +0).
+ *   total: the rows are cut into chunks of 4096 consecutive rows. In a chunk starting at row r0, thread t of 256 adds
+ *   bi[r0 + t], bi[r0 + t + 256], ... in that order onto an fp64 0; the 256 values are joined by the tree
+ *   for s = 128, 64, ..., 1: v[t] = v[t] + v[t + s] (t < s). The chunk values are summed the same way: thread t of 256 adds
+ *   the chunks t, t + 256, ..., then the same tree.
+ * The alignment of the operands changes the loads, not this order: one 16-byte load per slot when d % v == 0 and X, Y, ldx and
+ * ldy keep every row 16-byte aligned, element loads of the same slots otherwise.
+ * Three launches on `stream`, complete in stream order; no atomics, no allocation, nothing read on the host.
+ * ws: llmc_block_influence_ws_bytes(N) bytes, 8-byte aligned (a pure host call; 0 for invalid arguments).
+ * LLMC_EINVAL, before anything is launched: bad dt, a null pointer, N < 1 or N > 2^31, d < 1, ldx or ldy < d.
+ * LLMC_ENOTSUP: d >= 2^31 (the slot index of a row is a 32-bit integer).
+ * Bit-exact against tests/shortgpt_oracle.py. */
+size_t llmc_block_influence_ws_bytes(int64_t N);
+int llmc_block_influence(const void* X, const void* Y, int dt, int64_t N, int64_t d, int64_t ldx, int64_t ldy, int init,
+                         float* bi, double* total, void* ws, llmc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,7 @@ def register_into(registry, names=('GPTQ', 'Awq', 'RTN', 'SpQR')):
     llmc/utils/registry_factory.py:9-23). Uses item assignment, which llmc's Register supports and which REPLACES an
     existing key, so it works before or after llmc has registered its own classes, in any import order; returns the
     bound classes. `llmc/__main__.py:43,62` then picks ours up through `ALGO_REGISTRY[config.quant.method]`. A name is looked
-    up in the quantization package first, then in the sparsification one (`names=(..., 'Wanda', 'Magnitude', 'SparseGPT')`,
+    up in the quantization package first, then in the sparsification one (`names=(..., 'Wanda', 'Magnitude', 'SparseGPT', 'ShortGPT')`,
     `ALGO_REGISTRY[config.sparse.method]`)."""
     from .compression import quantization as Q
     from .compression import sparsification as S

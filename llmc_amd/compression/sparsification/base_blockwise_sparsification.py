@@ -8,7 +8,9 @@ Config (the `sparse` section, configs/sparsification/methods/Wanda/wanda.yml):
                           inputs); True: a second forward runs after pruning and feeds the next block.
   weight.sparsity         the fraction of every row (Wanda), of every tensor (Magnitude) or of every 128-column block of a
                           tensor (SparseGPT) that is zeroed.
-  weight.n_prune_layers   read and kept, as the reference does (ShortGPT's key; that method is not built here).
+  weight.n_prune_layers   ShortGPT's key (shortgpt.py): the number of whole blocks it removes; read when the section has no
+                          `sparsity`, as in the reference. ShortGPT refuses a section without it or a count outside
+                          [0, number of blocks).
   weight.sparsity_type    new key. 'unstructured' (default), or 'n:m' — zero n of every m consecutive input channels, m in
                           {2, 4, 8, 16} ('2:4' is the pattern the CDNA sparse matrix instructions consume). With n:m, `sparsity`
                           must be absent or equal to n / m.

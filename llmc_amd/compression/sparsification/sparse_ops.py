@@ -12,6 +12,9 @@ magnitude_prune    in place: the global |w| threshold of rank kth and w[|w| <= t
 path               the launch path prune_rows takes, by name (a pure host call).
 sparsegpt_prune    SparseGPT's blocked column loop on an upper factor of the inverse Hessian (csrc/sparsegpt_loop.hip): mask by
                    score w^2 / d^2, the pruning error fed to the later columns. Timings: profiles/sparsegpt.txt.
+block_influence    ShortGPT's per-token 1 - cos(input, output) of a block and its fp64 sum, one streaming pass
+                   (csrc/block_influence.hip); block_influence_composed is the same quantity row-wise from torch ops, on any
+                   device. Timings: profiles/shortgpt.txt.
 
 Dispatch: the kernel measured 0.04x - 0.15x of the composition's time per row and 0.002x - 0.007x for 2:4 at every shape timed
 (bf16 4096 x 4096, 1024 x 4096, 14336 x 4096, 4096 x 14336; profiles/prune.txt, tools/bench_prune.py), magnitude_prune 0.05x and
@@ -208,3 +211,63 @@ def sparsegpt_prune(W, Hinv, sparsity=None, nm=None, want_losses=False, want_mas
     _ffi.check(L.llmc_sparsegpt_prune(_ffi.ptr(W), _ffi.ptr(Hinv), R, K, sparsity, n, m, _ffi.ptr(Wout), _ffi.ptr(losses),
                                       _ffi.ptr(mask), SPARSEGPT_BLOCKSIZE, _ffi.ptr(ws), _ffi.stream()), 'llmc_sparsegpt_prune')
     return Wout, losses, mask
+
+
+def _rows(t, what):
+    if t.dim() < 1 or t.numel() == 0:
+        raise ValueError(f'{what} takes non-empty [..., d] tensors')
+    t2 = t.reshape(-1, t.shape[-1])
+    return t2 if _operand(t2) else t2.contiguous()
+
+
+def block_influence_composed(x, y):
+    """ShortGPT's per-token score 1 - cos(x, y) row-wise from torch ops in fp32, on any device: three row sums, two square
+    roots, one product, one division, nan_to_num(nan=0.5) (shortgpt.py:49-55 without the N x N product). x, y [..., d] -> fp32
+    [N]. It is what the tests compare the kernel against and what CPU tensors run."""
+    if x.shape != y.shape:
+        raise ValueError(f'block_influence: x is {tuple(x.shape)}, y is {tuple(y.shape)}')
+    xf, yf = _rows(x, 'block_influence').float(), _rows(y, 'block_influence').float()
+    dot, sx, sy = (xf * yf).sum(-1), (xf * xf).sum(-1), (yf * yf).sum(-1)
+    sim = (dot / (sx.sqrt() * sy.sqrt())).nan_to_num(nan=0.5)
+    return 1 - sim
+
+
+def block_influence(x, y, total=None, init=True, max_grid=None):
+    """x, y [..., d] of one dtype -> (bi fp32 [N], total): bi[n] = 1 - cos(x[n], y[n]) in fp32 and total, one fp64 element on the
+    device, = sum(bi) (init) or total + sum(bi) (init False: `total` is updated in place; a one-element view such as
+    importances[i] is written where it lies). On the GPU one pass of llmc_block_influence (csrc/block_influence.hip) in the order
+    include/llmc_hip.h states; rows with a non-unit last stride are copied, any row stride >= d is read in place. Stream-ordered:
+    nothing is read on the host. max_grid caps the row kernel's grid (tests: the grid-stride loop; same bits). CPU tensors run
+    block_influence_composed and torch's fp64 sum.
+
+    Dispatch: no shape is routed to the composition for speed: the kernel's call took 0.08x - 0.09x of its time in bf16 and
+    0.20x - 0.22x in fp32 at 65536 x 4096 and 65536 x 8192, 0.23x and 0.38x at 4096 x 4096, with no overlap of the min..max
+    ranges (profiles/shortgpt.txt, tools/bench_shortgpt.py)."""
+    if x.shape != y.shape or x.dtype != y.dtype or x.device != y.device:
+        raise ValueError(f'block_influence: x is {tuple(x.shape)} {x.dtype} on {x.device}, y is {tuple(y.shape)} {y.dtype} on '
+                         f'{y.device}')
+    x2, y2 = _rows(x, 'block_influence'), _rows(y, 'block_influence')
+    N, d = x2.shape
+    if total is None:
+        if not init:
+            raise ValueError('block_influence: folding (init=False) needs the running `total`')
+        total = torch.empty((), dtype=torch.float64, device=x.device)
+    elif total.dtype != torch.float64 or total.numel() != 1 or total.device != x.device:
+        raise ValueError('block_influence: total must be one fp64 element on the device of x')
+    if not x.is_cuda:
+        bi = block_influence_composed(x2, y2)
+        batch = bi.double().sum()
+        if init:
+            total.copy_(batch.reshape(total.shape))
+        else:
+            total.add_(batch.reshape(total.shape))
+        return bi, total
+    _ffi.require_gpu(x2, y2, total)
+    L = _ffi.lib()
+    bi = torch.empty(N, dtype=torch.float32, device=x.device)
+    ws = _ffi.workspace(L.llmc_block_influence_ws_bytes(N), x.device)
+    with _ffi.option(block_influence_max_grid=int(max_grid or 0)):
+        _ffi.check(L.llmc_block_influence(_ffi.ptr(x2), _ffi.ptr(y2), _ffi.dt(x2), N, d, x2.stride(0), y2.stride(0),
+                                          int(bool(init)), _ffi.ptr(bi), _ffi.ptr(total), _ffi.ptr(ws), _ffi.stream()),
+                   'llmc_block_influence')
+    return bi, total

@@ -72,6 +72,7 @@ enum Opt : int {
     OPT_GEMM3_NO_WIDE,      // K3's far updates on k_gemm3s (one 512-thread workgroup per CU) instead of k_gemm3w (two 128 x 128 workgroups)
     OPT_NO_RIDERS,          // K4 one-stream schedule: a group's far update as one launch instead of near-far launch + rider tiles on the next group's in-block launches
     OPT_KV_SINK_MAX_GRID,   // block cap of llmc_kv_sink_update's launch per tensor (0 = the built-in 8 blocks per CU)
+    OPT_BLOCK_INFLUENCE_MAX_GRID,   // block cap of llmc_block_influence's row kernel (0 = the built-in 8 blocks per CU)
     OPT_COUNT
 };
 int opt(int id);

@@ -574,6 +574,36 @@ int llmc_fp8_act_quant(const void* X, int dt, int64_t n_elem, int block, void* o
 int llmc_fp8_block_gemm(const void* A8, const float* a_s, const void* B8, const float* b_s, int64_t M, int64_t N,
                         int64_t K, int out_dt, const void* bias, void* C, llmc_stream_t stream);
 
+/* ---- OCP MX (csrc/mx_gemm.hip; an extension: the reference's real-quant Linears raise in forward) ------------------------------
+ * The stored form: element codes + one e8m0 scale byte (2^(byte - 127)) per 32 consecutive elements of a row. e2m1 codes are
+ * packed two per byte, element 2i in the low nibble (llmc_fp4_pack's form); e4m3 codes (OCP e4m3fn) take one byte each.
+ *
+ * llmc_mx_act_quant: X [M, K] contiguous bf16 / fp16 (16-byte aligned), K % 32 == 0 -> out_codes ([M, K/2] for fmt 2 = e2m1,
+ * [M, K] for fmt 4 = e4m3; 8-byte aligned) and out_scales [M, K/32] uint8, in one pass. Per 1 x 32 block:
+ *   absmax  fmaxf over |x| starting from 0: a NaN element is ignored, an infinity gives the exponent field 255 (llmc_fpx_quant)
+ *   scale   byte = clamp(floor(log2(absmax)) - emax + 127, 0, 254), 127 for an all-zero block; emax = 2 (e2m1), 8 (e4m3)
+ *   t       x * 2^(127 - byte), exact
+ *   e2m1    round to nearest even onto the OCP grid, saturating at +-6 (infinities too); a NaN gives 6 with the input's sign; the
+ *           sign survives on a zero: bit for bit llmc_fpx_quant(mode = ocp | e8m0, g = 32) followed by llmc_fp4_pack
+ *   e4m3    round to nearest even, saturating at +-448 (infinities too); a NaN gives the NaN code 0x7f with the input's sign
+ * LLMC_ENOTSUP: another fmt, K % 32 != 0. LLMC_EINVAL: null / misaligned pointers, another dtype.
+ *
+ * llmc_mx_gemm: A [M, K] codes in a_fmt (2 = packed e2m1 [M, K/2], 4 = e4m3) with a_s [M, K/32]; B4 [N, K/2] packed e2m1 (a
+ * weight) with b_s [N, K/32];
+ *   C[m, n] = sum over 32-deep blocks kb of 2^(a_s[m, kb] + b_s[n, kb] - 254) * sum_{k in kb} a[m, k] * b[n, k]
+ * accumulated in fp32 by v_mfma_scale_f32_16x16x128_f8f6f4, which applies the scales itself (no per-block accumulator update), rounded
+ * once to out_dt (bf16, fp16, fp32); bias [N] (out_dt, may be null) is added after that rounding, like llmc_fp8_block_gemm.
+ * Numerics (measured): the instruction aligns the products of one 32-block to the block's largest product and
+ * cuts off what lies more than 13 binary places below its leading bit. e2m1 x e2m1 products never reach that window. e4m3
+ * activation codes are therefore fed one exponent class at a time (fields 0-7, 8-14, 15: three instructions per fragment,
+ * each sum exact, joined in the fp32 accumulator), at a third of the instruction's e4m3 rate.
+ * Any M, N >= 1 (edge tiles masked). LLMC_ENOTSUP (nothing is launched): K % 128 != 0, K >= 2^24, another a_fmt.
+ * LLMC_EINVAL: null operands, codes not 16-byte / scales not 4-byte aligned, another out_dt. */
+int llmc_mx_act_quant(const void* X, int dt, int64_t M, int64_t K, int fmt, void* out_codes, void* out_scales,
+                      llmc_stream_t stream);
+int llmc_mx_gemm(const void* A, int a_fmt, const void* a_s, const void* B4, const void* b_s, int64_t M, int64_t N, int64_t K,
+                 int out_dt, const void* bias, void* C, llmc_stream_t stream);
+
 /* ---- SmoothQuant / OS+ (smoothquant.py:39-59, osplus.py:61-170) ------------------------------------------------------------
  * Column statistics of X [N, K] dt (N up to 2^31 rows): run[0:K] = max, run[K:2K] = min, run[2K:3K] = max |x| per column, fp32
  * (exact: they are values of dt). init != 0: the buffers are written; else the batch is folded into them (running max / min

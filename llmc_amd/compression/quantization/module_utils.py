@@ -430,6 +430,72 @@ class LlmcFp8Linear(nn.Module):
                 f'block_size={self.block_size})')
 
 
+class MxFp4RealQuantLinear(nn.Module):
+    """A Linear on the OCP MXFP4 stored form (no reference counterpart: its real-quant Linears raise in forward):
+    `weight_packed` uint8 [R, K/2] (e2m1, element 2i in the low nibble) + `weight_scale` uint8 [R, K/32] (e8m0), what
+    FloatQuantizer(bit='e2m1', float_semantics='ocp', scale_format='e8m0', per_group, group_size=32) returns. With an activation
+    section (`bit` e2m1 or e4m3, dynamic) forward quantizes the activation per 1 x 32 block and runs the block-scaled MFMA GEMM
+    (mx_ops.mx_linear_forward); weight-only, or in_features % 128 != 0: the weight is de-quantized and goes through hip_linear."""
+
+    _WEIGHT = {'bit': 'e2m1', 'granularity': 'per_group', 'group_size': 32, 'float_semantics': 'ocp', 'scale_format': 'e8m0'}
+    _ACT_BITS = ('e2m1', 'e4m3')
+
+    def __init__(self, weight, bias, scales, act_bit):
+        super().__init__()
+        self.register_buffer('weight_packed', weight)
+        self.register_buffer('weight_scale', scales)
+        if bias is not None:
+            self.register_buffer('bias', bias)
+        else:
+            self.bias = None
+        self.act_bit = act_bit
+
+    @classmethod
+    def check_config(cls, quant_config):
+        """The activation format (None: weight-only) of a configuration this module takes; ValueError with the reason otherwise."""
+        w = quant_config['weight']
+        for k, want in cls._WEIGHT.items():
+            if w.get(k) != want:
+                raise ValueError(f"mxfp4_quant: the weight section needs {k}: {want} (the OCP MX stored form: e2m1 codes, one "
+                                 f"e8m0 scale per 32 elements), got {k}: {w.get(k)!r}")
+        a = quant_config.get('act')
+        if a is None:
+            return None
+        if a.get('bit') not in cls._ACT_BITS:
+            raise ValueError(f"mxfp4_quant: activations are quantized per 1 x 32 block to e2m1 or e4m3 with e8m0 scales, got act bit: "
+                             f"{a.get('bit')!r} (e3m2 has no dense packing, e5m2 is not provided)")
+        if a.get('static', False):
+            raise ValueError('mxfp4_quant: static activation scales are not provided (the MX block scales are dynamic)')
+        return a['bit']
+
+    @torch.no_grad()
+    def forward(self, x):
+        from .quant import dequant_fpx
+        if self.act_bit is not None and self.in_features % 128 == 0:
+            from .mx_ops import mx_linear_forward
+            return mx_linear_forward(x, self.weight_packed, self.weight_scale, self.act_bit, self.bias)
+        w = dequant_fpx(self.weight_packed, self.weight_scale, 'e2m1', 32, x.dtype)
+        return hip_linear(x, w, self.bias)
+
+    @classmethod
+    @torch.no_grad()
+    def new(cls, module, w_q, quant_config):
+        act_bit = cls.check_config(quant_config)
+        weight, scales, _ = w_q(module)
+        bias = module.bias.data if module.bias is not None else None
+        m = cls(weight.contiguous(), bias, scales.reshape(weight.shape[0], -1).contiguous(), act_bit)
+        m.in_features, m.out_features = module.in_features, module.out_features
+        m.weight_shape, m.weight_dtype = weight.shape, weight.dtype
+        m.scales_shape, m.scales_dtype = m.weight_scale.shape, m.weight_scale.dtype
+        m.zeros_shape = m.zeros_dtype = None
+        return m
+
+    def __repr__(self):
+        return (f'MxFp4RealQuantLinear(in_features={self.in_features}, out_features={self.out_features}, '
+                f'bias={self.bias is not None}, weight_shape={self.weight_shape}, weight_dtype={self.weight_dtype}, '
+                f'scales_shape={self.scales_shape}, scales_dtype={self.scales_dtype}, act_bit={self.act_bit})')
+
+
 _TRANSFORMERS_LINEAR_TYPES_ = [nn.Linear]
 _TRANSFORMERS_LN_TYPES_ = [nn.LayerNorm]
 try:  # RMSNorm-style layers of HF models count as LN types for apply_scale
@@ -442,7 +508,7 @@ if hasattr(nn, 'RMSNorm') and nn.RMSNorm not in _TRANSFORMERS_LN_TYPES_:
 
 _LLMC_LN_TYPES_ = [LlmcRMSNorm]
 _LLMC_LINEAR_TYPES_ = [LlmcFp8Linear, RotateLinear, OriginFloatLinear, FakeQuantLinear, EffcientFakeQuantLinear, VllmRealQuantLinear,
-                       SglRealQuantLinear, AutoawqRealQuantLinear, MlcllmRealQuantLinear, LightllmRealQuantLinear]
+                       SglRealQuantLinear, AutoawqRealQuantLinear, MlcllmRealQuantLinear, LightllmRealQuantLinear, MxFp4RealQuantLinear]
 _REALQUANT_LINEAR_MAP_ = {
     'vllm_quant': VllmRealQuantLinear,
     'lightllm_quant': LightllmRealQuantLinear,
@@ -450,4 +516,5 @@ _REALQUANT_LINEAR_MAP_ = {
     'autoawq_quant': AutoawqRealQuantLinear,
     'mlcllm_quant': MlcllmRealQuantLinear,
     'lightx2v_quant': Lightx2vRealQuantLinear,
+    'mxfp4_quant': MxFp4RealQuantLinear,
 }

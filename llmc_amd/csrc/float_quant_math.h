@@ -3,7 +3,7 @@
 // :1061-1081 (quant / dequant): scale = absmax.clamp(1e-5) / qmax, scales[scales == 0] = 1, q = float_quantize(x / scale + 0),
 // q * scale. The formats themselves (the rounding onto each grid, the codes) are fp8_math.h's.
 // Users: k_fp8_cast (fp8_quant.hip), k_fpx_seg / k_fpx_row / k_fpx_flat (fp4_quant.hip), the FP8 arm of k_osplus_act_step
-// (smooth_osplus.hip).
+// (smooth_osplus.hip), k_mx_act_quant (mx_gemm.hip).
 #pragma once
 #include "common.h"
 
@@ -130,6 +130,24 @@ template <int DT> struct DivFreeGuard {
     }
     __device__ __forceinline__ bool reaches(uint32_t t_limit) const { return big >= t_limit; }
 };
+
+// ---- absmax of a group that L neighbouring lanes hold (k_fpx_seg of fp4_quant.hip, k_mx_act_quant of mx_gemm.hip) -------------
+// max over the L lanes of a group (L a power of two, whole groups active or idle together). Inside a 16-lane row the partner's
+// value arrives by DPP: quad_perm [1,0,3,2] and [2,3,0,1], then row_half_mirror and row_mirror (every lane ends with the max of
+// its quad / half / row); 32 and 64 lanes add the cross-row exchanges.
+__device__ __forceinline__ float fpx_seg_max(float m, int L) {
+    auto dpp = [](float x, auto ctrl) {
+        const int y = __builtin_amdgcn_update_dpp(0, __float_as_int(x), decltype(ctrl)::value, 0xf, 0xf, true);
+        return fmaxf(x, __int_as_float(y));
+    };
+    if (L > 1) m = dpp(m, std::integral_constant<int, 0xB1>{});
+    if (L > 2) m = dpp(m, std::integral_constant<int, 0x4E>{});
+    if (L > 4) m = dpp(m, std::integral_constant<int, 0x141>{});
+    if (L > 8) m = dpp(m, std::integral_constant<int, 0x140>{});
+    if (L > 16) m = fmaxf(m, __shfl_xor(m, 16, 64));
+    if (L > 32) m = fmaxf(m, __shfl_xor(m, 32, 64));
+    return m;
+}
 
 // ---- the row of vector i (vpr vectors per row, nv in all): a 32-bit division where the index fits -----------------------------
 __device__ __forceinline__ int64_t row_of_vector(int64_t i, int64_t nv, int64_t vpr) {

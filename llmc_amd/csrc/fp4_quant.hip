@@ -144,22 +144,7 @@ __device__ __forceinline__ float fpx_load_vec(const FpxArgs& a, int64_t i, T (&w
     return m;
 }
 
-// max over the L lanes of a group (L a power of two, whole groups active or idle together). Inside a 16-lane row the partner's
-// value arrives by DPP: quad_perm [1,0,3,2] and [2,3,0,1], then row_half_mirror and row_mirror (every lane ends with the max of
-// its quad / half / row); 32 and 64 lanes add the cross-row exchanges.
-__device__ __forceinline__ float fpx_seg_max(float m, int L) {
-    auto dpp = [](float x, auto ctrl) {
-        const int y = __builtin_amdgcn_update_dpp(0, __float_as_int(x), decltype(ctrl)::value, 0xf, 0xf, true);
-        return fmaxf(x, __int_as_float(y));
-    };
-    if (L > 1) m = dpp(m, std::integral_constant<int, 0xB1>{});
-    if (L > 2) m = dpp(m, std::integral_constant<int, 0x4E>{});
-    if (L > 4) m = dpp(m, std::integral_constant<int, 0x141>{});
-    if (L > 8) m = dpp(m, std::integral_constant<int, 0x140>{});
-    if (L > 16) m = fmaxf(m, __shfl_xor(m, 16, 64));
-    if (L > 32) m = fmaxf(m, __shfl_xor(m, 32, 64));
-    return m;
-}
+// fpx_seg_max (the max over the L lanes of a group, by DPP inside a 16-lane row): float_quant_math.h
 
 template <typename T, int KIND>
 __global__ __launch_bounds__(XB) void k_fpx_seg(const FpxArgs a, int L, int lshift) {

@@ -1,7 +1,7 @@
 // mfma_common.h — the toolkit of the matrix-pipe kernels, each hardware rule of gfx950 written down once: vector types, the
 // MFMA wrappers, counted waits, the transposing fragment read, buffer descriptors, the LDS-DMA pieces and the split of an
 // fp32 value into three bf16 terms. Included by hessian_syrk.hip, linear_eval.hip, gemm3.hip, gemm3_wide.hip,
-// sgemm_wide_tile.h (sgemm_wide.hip, gptq_loop.hip) and fp8_block.hip; sgemm.hip and cholesky.hip take the vector types.
+// sgemm_wide_tile.h (sgemm_wide.hip, gptq_loop.hip), fp8_block.hip and mx_gemm.hip; sgemm.hip and cholesky.hip take the vector types.
 // Everything here is __forceinline__: a kernel's instruction stream is what it was with the helper written out in place.
 #pragma once
 #include "common.h"
@@ -36,6 +36,15 @@ template <> struct Mfma<LLMC_F16> {
                                                       __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
     }
 };
+
+// ---- the block-scaled form v_mfma_scale_f32_16x16x128_f8f6f4: A and B in formats FA / FB (the instruction's cbsz / blgp codes),
+// lane l holds row / column l & 15; an e2m1 operand's k 32 g .. + 31 (g = l >> 4) in the first 4 of its 8 registers, an e4m3 / e5m2
+// operand's k 16 g .. + 15 in registers 0-3 and 64 + 16 g .. + 15 in registers 4-7; byte 0 of lane l's scale register is the e8m0
+// scale (2^(byte - 127)) of row l & 15, k block g, for either format (csrc/mx_gemm.hip has the probe's account).
+constexpr int MFMA_FMT_E4M3 = 0, MFMA_FMT_E5M2 = 1, MFMA_FMT_E2M1 = 4;
+template <int FA, int FB> __device__ __forceinline__ f32x4 mfma_scale_16x16x128(i32x8 a, i32x8 b, f32x4 c, int scale_a, int scale_b) {
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, FA, FB, 0, scale_a, 0, scale_b);
+}
 
 // ---- waits. The LDS-DMA pieces below are inline asm, so hipcc's own vmcnt bookkeeping does not count them: the kernels wait
 // by hand, for "all but the N youngest vector-memory requests of this wave" (requests complete in issue order).

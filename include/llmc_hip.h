@@ -856,6 +856,55 @@ size_t llmc_block_influence_ws_bytes(int64_t N);
 int llmc_block_influence(const void* X, const void* Y, int dt, int64_t N, int64_t d, int64_t ldx, int64_t ldy, int init,
                          float* bi, double* total, void* ws, llmc_stream_t stream);
 
+/* Pairwise cosine distance of token features (pairwise_cosine_similarity and the `1.0 -` of divprune, divprune.py:13-27 of the
+ * reference's token_reduction package; the same matrix ToMe, DART, VisionZip, FastVID and DyCoke form). X [N, d] of dt with unit
+ * column stride and row stride ldx >= d elements; D fp32 [N, N], contiguous.
+ *   G = X X^T accumulated in fp32 on the matrix pipe (v_mfma_f32_32x32x16_bf16 / _f16; fp32 inputs take v_mfma_f32_32x32x2f32
+ *   in the same template, so their products are fp32 products, not split ones). Both operands are rows of X, 8 (fp32: 4)
+ *   consecutive k per lane: no transposed and no normalised copy of X is written.
+ *   D[i][j] = 1 - G[i][j] / (sqrtf(G[i][i]) * sqrtf(G[j][j])), IEEE square roots, product, division and subtraction. G[i][i] is
+ *   the diagonal element of the same accumulation, so D[i][i] is a rounding or two away from 0 and is not forced to 0; a zero
+ *   row gives NaN in its row and column (0 / 0). Both as in the reference.
+ *   Only the 128 x 128 tiles on or above the diagonal are multiplied; below the diagonal D is a copy, so D[i][j] and D[j][i]
+ *   have equal bits (inside a diagonal tile both take the element above the diagonal).
+ * The order of summation, a function of (N, d, dt) alone, so equal calls give equal bits:
+ *   tiles = nt (nt + 1) / 2 with nt = ceil(N / 128); S = min(ceil(512 / tiles), ceil(d / 256)) slices are wanted; a slice is
+ *   ks = ceil(ceil(d / S) / 32) * 32 consecutive k and there are ceil(d / ks) of them. Inside a slice k advances by 16 (fp32: 8)
+ *   per step onto one accumulator per element that starts at +0; a step is one 32x32x16 instruction (fp32: four 32x32x2
+ *   instructions, instruction e taking k0 + e and k0 + 4 + e); k at or past d enters as +0. The slices' fp32 values are then
+ *   added in slice order starting from slice 0's.
+ * Any alignment of X and ldx is accepted: 16-byte loads when X and ldx * sizeof(dt) are multiples of 16, element loads of the
+ * same values otherwise; the order does not change.
+ * Two launches on `stream`, complete in stream order; no atomics, no allocation, nothing read on the host.
+ * ws: llmc_cosine_dist_ws_bytes(N, d) bytes, 16-byte aligned: the slices' partial tiles (a pure host call; 0 for arguments the
+ * entry refuses).
+ * LLMC_EINVAL, before anything is launched: bad dt, a null pointer, N < 1, d < 1, ldx < d.
+ * LLMC_ENOTSUP: N > 46340 or d > 2^31 - 64 (an element index of D or of a row would leave 32 bits).
+ * Error bound and exact cases: tests/divprune_oracle.py. */
+size_t llmc_cosine_dist_ws_bytes(int64_t N, int64_t d);
+int llmc_cosine_dist(const void* X, int dt, int64_t N, int64_t d, int64_t ldx, float* D, void* ws, llmc_stream_t stream);
+
+/* DivPrune's greedy max-min selection (divprune.py:29-53) on a distance matrix D [N, N] of dt (f32, bf16 or f16: a matrix the
+ * caller supplies keeps its dtype, values are only compared) with unit column stride and row stride ldd >= N elements.
+ * sel int64 [k]. torch's ordering rules, stated outright:
+ *   step 0: score[j] = the second smallest element of COLUMN j, a NaN sorting after every number (topk(2, dim=0, largest=False));
+ *   step i >= 1: score[j] = min(score[j], D[sel[i - 1]][j]), a NaN in either operand giving NaN; before step 1 the scores are
+ *   reset, so step 1's score is row sel[0] alone (the reference reduces the chosen rows only);
+ *   every step: sel[i] = the index of the greatest score, a NaN greater than every number (and equal to another NaN), -0 equal to
+ *   +0, the lowest index among equals (torch.argmax on the CPU). Nothing excludes an index already chosen: with duplicate tokens
+ *   the reference selects again, and so does this; k > N is legal.
+ * Two launches on `stream`: a pass over D for the step-0 statistic, then one workgroup of 1024 threads that runs all k steps,
+ * each thread holding the running minimum of up to 16 columns in registers and a step reading one row of D (N * sizeof(dt)
+ * bytes); the argmax is one reduction over (value, index) keys. No atomics, no allocation, nothing read on the host.
+ * ws: llmc_maxmin_select_ws_bytes(N) bytes, 4-byte aligned (a pure host call; 0 for an N the entry refuses).
+ * LLMC_EINVAL, before anything is launched: bad dt, N < 2 (the reference's topk(2) raises there), k < 0, ldd < N, a null pointer
+ * with k > 0. k == 0 writes nothing and launches nothing.
+ * LLMC_ENOTSUP: N > llmc_maxmin_select_max_n() = 16384, the columns one workgroup keeps resident (callers compose the
+ * reference's loop). Bit-exact against tests/divprune_oracle.py: select. */
+int llmc_maxmin_select_max_n(void);
+size_t llmc_maxmin_select_ws_bytes(int64_t N);
+int llmc_maxmin_select(const void* D, int dt, int64_t N, int64_t ldd, int64_t k, int64_t* sel, void* ws, llmc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

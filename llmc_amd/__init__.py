@@ -14,12 +14,13 @@ def register_into(registry, names=('GPTQ', 'Awq', 'RTN', 'SpQR')):
     existing key, so it works before or after llmc has registered its own classes, in any import order; returns the
     bound classes. `llmc/__main__.py:43,62` then picks ours up through `ALGO_REGISTRY[config.quant.method]`. A name is looked
     up in the quantization package first, then in the sparsification one (`names=(..., 'Wanda', 'Magnitude', 'SparseGPT', 'ShortGPT')`,
-    `ALGO_REGISTRY[config.sparse.method]`)."""
+    `ALGO_REGISTRY[config.sparse.method]`), then in the token-reduction one (`'TokenReduction'`)."""
     from .compression import quantization as Q
     from .compression import sparsification as S
+    from .compression import token_reduction as T
     bound = {}
     for n in names:
-        cls = getattr(Q, n, None) or getattr(S, n)
+        cls = getattr(Q, n, None) or getattr(S, n, None) or getattr(T, n)
         registry[n] = cls
         bound[n] = cls
     _announce_wrappers()

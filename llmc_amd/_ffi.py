@@ -143,6 +143,11 @@ SIGNATURES = {
                                    _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
     'llmc_block_influence_ws_bytes': (_sz, [_i64]),
     'llmc_block_influence': (_i32, [_vp, _vp, _i32, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
+    'llmc_cosine_dist_ws_bytes': (_sz, [_i64, _i64]),
+    'llmc_cosine_dist': (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp]),
+    'llmc_maxmin_select_max_n': (_i32, []),
+    'llmc_maxmin_select_ws_bytes': (_sz, [_i64]),
+    'llmc_maxmin_select': (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp]),
     'llmc_test_sgemm': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                _i32, _i32, _vp]),
     'llmc_test_sgemm_phased': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -1,7 +1,8 @@
 // mfma_common.h — the toolkit of the matrix-pipe kernels, each hardware rule of gfx950 written down once: vector types, the
 // MFMA wrappers, counted waits, the transposing fragment read, buffer descriptors, the LDS-DMA pieces and the split of an
 // fp32 value into three bf16 terms. Included by hessian_syrk.hip, linear_eval.hip, gemm3.hip, gemm3_wide.hip,
-// sgemm_wide_tile.h (sgemm_wide.hip, gptq_loop.hip), fp8_block.hip and mx_gemm.hip; sgemm.hip and cholesky.hip take the vector types.
+// sgemm_wide_tile.h (sgemm_wide.hip, gptq_loop.hip), fp8_block.hip, mx_gemm.hip and token_select.hip; sgemm.hip and cholesky.hip
+// take the vector types.
 // Everything here is __forceinline__: a kernel's instruction stream is what it was with the helper written out in place.
 #pragma once
 #include "common.h"

@@ -78,3 +78,4 @@ Register = Registry  # llmc's name for the class
 ALGO_REGISTRY = Registry('algorithm')
 MODEL_REGISTRY = Registry('model')
 KV_REGISTRY = Registry('kv cache')
+TOKEN_REDUCTION_REGISTRY = Registry('token reduction')

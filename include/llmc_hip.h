@@ -604,6 +604,33 @@ int llmc_mx_act_quant(const void* X, int dt, int64_t M, int64_t K, int fmt, void
 int llmc_mx_gemm(const void* A, int a_fmt, const void* a_s, const void* B4, const void* b_s, int64_t M, int64_t N, int64_t K,
                  int out_dt, const void* bias, void* C, llmc_stream_t stream);
 
+/* ---- plain W8A8-FP8 Linear (csrc/fp8_linear.hip; an extension: the reference's real-quant Linears raise in forward) -----------
+ * The stored form of configs/quantization/backend/{vllm,sglang}/fp8: OCP e4m3fn codes whose scales are constant along K.
+ * A8 [M, K] codes with a_s fp32 [a_s_n], a_s_n = M (one per token) or 1 (per tensor); B8 [N, K] codes (a weight) with b_s fp32
+ * [b_s_n], b_s_n = N (one per output channel) or 1.
+ *   acc[m, n] = sum_k a[m, k] * b[n, k]                   fp32, on the fp8 matrix pipe
+ *   C[m, n]   = rnd_out(fl(fl(acc * a_s[m]) * b_s[n]))    the two fp32 products in this order, one rounding to out_dt
+ * bias [N] (out_dt, may be null) is added after that rounding, like llmc_fp8_block_gemm and llmc_mx_gemm. out_dt: bf16, fp16, fp32.
+ * Both scales act in the epilogue: the K loop has no VALU work (llmc_fp8_block_gemm pays two ops per element and K block).
+ * Instruction: the non-scaled forms — v_mfma_f32_32x32x16_fp8_fp8 on the tile rung, v_mfma_f32_16x16x32_fp8_fp8 on the decode
+ * rung. Numerics (measured): the instruction aligns the 8 products of one lane's 8 operand bytes to the largest of
+ * them and cuts off what lies more than 13 binary places below its leading bit; groups, instructions and the accumulator are added
+ * at fp32 width. The loss is one-sided and below 7 * 2^-13 of sum |a b|; on top come at most K fp32 additions. The block-scaled
+ * f8f6f4 form (twice the rate) has the same window over 32 products (K22), a loss of up to 31 * 2^-13, and is not used. Data whose
+ * products within a group lie within 13 binary places of each other, and whose partial sums are fp32 numbers, gives the exact
+ * result rounded once.
+ * Rungs (one table in the source, set from profiles/fp8_linear.txt): 0 decode, M <= 64 — 16 columns per workgroup, the K blocks of
+ * 128 dealt round 8 waves whose partial tiles are added in wave order in LDS (no atomics: the same bits on every run); 1 tile128 —
+ * 128 x 128 outputs per workgroup. llmc_fp8_scaled_gemm_on_rung runs rung r whatever the shape (r = -1:
+ * the table; for the measuring tool and the tests; the decode rung with M > 64 is LLMC_EINVAL). llmc_fp8_scaled_gemm_rung: the rung the table gives a shape, a pure host call.
+ * Any M, N >= 1 (edge tiles masked). LLMC_ENOTSUP (nothing is launched): K % 128 != 0, K >= 2^24 (or 2^31 tiles).
+ * LLMC_EINVAL: null operands, codes not 16-byte / scales not 4-byte aligned, another out_dt, a_s_n / b_s_n not in the allowed set. */
+int llmc_fp8_scaled_gemm(const void* A8, const float* a_s, int64_t a_s_n, const void* B8, const float* b_s, int64_t b_s_n,
+                         int64_t M, int64_t N, int64_t K, int out_dt, const void* bias, void* C, llmc_stream_t stream);
+int llmc_fp8_scaled_gemm_on_rung(const void* A8, const float* a_s, int64_t a_s_n, const void* B8, const float* b_s, int64_t b_s_n,
+                                 int64_t M, int64_t N, int64_t K, int out_dt, const void* bias, void* C, int rung, llmc_stream_t stream);
+int llmc_fp8_scaled_gemm_rung(int64_t M, int64_t N);
+
 /* ---- SmoothQuant / OS+ (smoothquant.py:39-59, osplus.py:61-170) ------------------------------------------------------------
  * Column statistics of X [N, K] dt (N up to 2^31 rows): run[0:K] = max, run[K:2K] = min, run[2K:3K] = max |x| per column, fp32
  * (exact: they are values of dt). init != 0: the buffers are written; else the batch is folded into them (running max / min

@@ -114,6 +114,9 @@ SIGNATURES = {
     'llmc_fp8_block_gemm': (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
     'llmc_mx_act_quant': (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _vp, _vp]),
     'llmc_mx_gemm': (_i32, [_vp, _i32, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
+    'llmc_fp8_scaled_gemm': (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
+    'llmc_fp8_scaled_gemm_on_rung': (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _i32, _vp]),
+    'llmc_fp8_scaled_gemm_rung': (_i32, [_i64, _i64]),
     'llmc_pack_awq_gemm': (_i32, [_vp, _i32, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     'llmc_col_stats_ws_bytes': (_sz, [_i64, _i64]),
     'llmc_col_stats': (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),

@@ -271,7 +271,16 @@ class EffcientFakeQuantLinear(nn.Module):
 
 class VllmRealQuantLinear(nn.Module):
     """module_utils.py:762-876: compressed-tensors layout (weight_packed int32 [R, K*b/32] or weight int8/fp8,
-    weight_scale, input_scale)."""
+    weight_scale, input_scale).
+
+    forward (an extension: the reference raises) runs the plain FP8 form — `weight` float8_e4m3fn with a per-channel or
+    per-tensor `weight_scale`: with an e4m3 `act` section, dynamic per_token or static per_tensor, the activation is quantized
+    and the epilogue-scaled FP8 GEMM runs (fp8_linear_ops.fp8_linear_forward); weight-only, the weight is de-quantized and goes
+    through hip_linear. `new` records what that needs from quant_config (act_cfg, act_mode). Every other stored form raises
+    NotImplementedError, naming itself."""
+
+    act_cfg = None          # the `act` section `new` saw (None: weight-only, or a module built by hand)
+    act_mode = None         # fp8_linear_ops.act_mode(act_cfg), or the NotImplementedError it raised, kept for forward
 
     def __init__(self, weight, bias, scales, input_scale, need_pack, scales_name):
         super().__init__()
@@ -285,7 +294,28 @@ class VllmRealQuantLinear(nn.Module):
 
     @torch.no_grad()
     def forward(self, x):
-        raise NotImplementedError
+        from . import fp8_linear_ops as F8
+        name = type(self).__name__
+        if getattr(self, 'weight', None) is None:
+            raise NotImplementedError(f'{name}.forward: packed integer weights (weight_packed) are not provided; the INT4 / INT8 '
+                                      'de-quantize GEMM is separate work')
+        if getattr(self, 'weight_scale', None) is None:
+            raise NotImplementedError(f'{name}.forward: per_block scales (weight_scale_inv) are not provided here; block-128 '
+                                      'checkpoints run on LlmcFp8Linear')
+        if self.weight.dtype != torch.float8_e4m3fn:
+            raise NotImplementedError(f'{name}.forward: weight dtype {self.weight.dtype} is not provided (float8_e4m3fn is; int8 '
+                                      'and e5m2 are not)')
+        if isinstance(self.act_mode, NotImplementedError):
+            raise NotImplementedError(f'{name}.forward: {self.act_mode}')
+        if self.act_mode is None:
+            if self.input_scale is not None:      # a module built by hand or loaded without its configuration
+                F8._announce(name, tuple(self.weight.shape), 'the module holds an input_scale but no `act` section was '
+                             'recorded (act_cfg is None)', 'weight-only forward, activations NOT quantized; set act_cfg / act_mode')
+            return hip_linear(x, F8.fp8_dequant(self.weight, self.weight_scale, x.dtype), self.bias)
+        if getattr(self, '_aquantizer', None) is None:
+            self._aquantizer = F8._quantizer(self.act_cfg)
+        input_scale = self.input_scale if self.act_mode == 'static_per_tensor' else None
+        return F8.fp8_linear_forward(x, self.weight, self.weight_scale, self._aquantizer, input_scale, self.bias)
 
     @classmethod
     @torch.no_grad()
@@ -303,6 +333,13 @@ class VllmRealQuantLinear(nn.Module):
         m.weight_shape, m.weight_dtype = weight.shape, weight.dtype
         m.scales_shape, m.scales_dtype = scales.shape, scales.dtype
         m.zeros_shape = m.zeros_dtype = None
+        # what forward needs from the configuration; a pairing it does not run is kept as the error it will raise
+        from .fp8_linear_ops import act_mode
+        m.act_cfg = dict(quant_config['act']) if 'act' in quant_config else None
+        try:
+            m.act_mode = act_mode(m.act_cfg)
+        except NotImplementedError as e:
+            m.act_mode = e
         return m
 
     @classmethod

@@ -631,6 +631,32 @@ int llmc_fp8_scaled_gemm_on_rung(const void* A8, const float* a_s, int64_t a_s_n
                                  int64_t M, int64_t N, int64_t K, int out_dt, const void* bias, void* C, int rung, llmc_stream_t stream);
 int llmc_fp8_scaled_gemm_rung(int64_t M, int64_t N);
 
+/* ---- W4A16 Linear on AutoAWQ's GEMM layout (csrc/awq_gemm.hip; an extension: the reference's AutoawqRealQuantLinear raises in
+ * forward) ---- the stored form llmc_pack_awq_gemm writes: qweight int32 [K, R/8], qzeros int32 [K/g, R/8], scales f16 [K/g, R];
+ * column 8 c + j of a word c sits in nibble INV[j], INV = 0,4,1,5,2,6,3,7 (the inverse of the packing order 0,2,4,6,1,3,5,7).
+ *   code(k, n) = nibble INV[n % 8] of qweight[k][n / 8], read as stored (a group maximum that spilled into the neighbouring
+ *                nibble at packing is whatever the nibbles hold); zero(k / g, n) the same way from qzeros
+ *   W~[k][n]   = rnd_dt(float(code - zero) * float(scales[k / g][n]))   one rounding: the fp32 product of a 5-bit integer and an
+ *                f16 is exact. For f16 this is bit for bit AutoAWQ's (q - z) * s in half precision (the kernels take the packed
+ *                route: (0x6400 | q) - (1024 + z) is exact, then one v_pk_mul_f16); bf16 goes through fp32 and v_cvt_pk_bf16_f32.
+ * llmc_awq_gemm: y[M, R] = rnd_dt(sum_k x[m, k] W~[k][n] (+ bias[n])); x [M, K], y and bias [R] in dt = f16 or bf16; fp32
+ * accumulation on v_mfma_f32_32x32x16; the bias is added to the fp32 sum before the single rounding (llmc_linear_eval's rule).
+ * Any M >= 1 and any R % 8 == 0 (edges masked), K % g == 0.
+ * rung: -1 the ladder; 0 stream — small M: one wave per 256 columns x K slice de-quantizes in registers, the slices' fp32
+ * partials (ws: llmc_awq_gemm_ws_bytes, required by this rung) are added in ascending slice order by a second kernel, no atomics:
+ * the same bits on every run; 1 tile — 128 x 256 outputs per workgroup, the weight tile de-quantized once per workgroup into
+ * LDS, K % 64 == 0 (the ladder sends another K to the stream rung). A named rung runs whatever M.
+ * LLMC_ENOTSUP (nothing is launched; callers de-quantize and run the 16-bit GEMM): g % 16 != 0; K >= 2^22, M or R >= 2^31 or
+ * 2^24 tiles of 32 x 256 (element indices would leave 32 bits); x, y, scales or ws not 16-byte, the words not 4-byte aligned; the
+ * tile rung named with K % 64 != 0. LLMC_EINVAL: null operands, another dt, R % 8 != 0, K % g != 0, no such rung, no ws.
+ * llmc_awq_dequant: out [R, K] = W~ transposed (the layout of a Linear's weight), out_dt f16, bf16 or fp32; g % 8 == 0, else
+ * LLMC_ENOTSUP. */
+size_t llmc_awq_gemm_ws_bytes(int64_t M, int64_t K, int64_t R);
+int llmc_awq_gemm(const void* x, int dt, int64_t M, int64_t K, int64_t R, const int32_t* qweight, const int32_t* qzeros,
+                  const void* scales, int64_t g, const void* bias, void* y, void* ws, llmc_stream_t stream, int rung);
+int llmc_awq_dequant(const int32_t* qweight, const int32_t* qzeros, const void* scales, int64_t K, int64_t R, int64_t g,
+                     void* out, int out_dt, llmc_stream_t stream);
+
 /* ---- SmoothQuant / OS+ (smoothquant.py:39-59, osplus.py:61-170) ------------------------------------------------------------
  * Column statistics of X [N, K] dt (N up to 2^31 rows): run[0:K] = max, run[K:2K] = min, run[2K:3K] = max |x| per column, fp32
  * (exact: they are values of dt). init != 0: the buffers are written; else the batch is folded into them (running max / min

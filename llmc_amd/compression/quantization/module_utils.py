@@ -375,7 +375,14 @@ class SglRealQuantLinear(VllmRealQuantLinear):
 
 
 class AutoawqRealQuantLinear(nn.Module):
-    """module_utils.py:936-1065: AutoAWQ GEMM layout (qweight [K, R/8], qzeros [K/g, R/8], scales [K/g, R] f16)."""
+    """module_utils.py:936-1065: AutoAWQ GEMM layout (qweight [K, R/8], qzeros [K/g, R/8], scales [K/g, R] f16).
+
+    forward (an extension: the reference raises) runs the fused int4 de-quantize MFMA GEMM on the packed buffers
+    (awq_gemm_ops.awq_linear_forward): W~ = rnd((code - zero) * scale) in the activation's dtype, fp32 accumulation, the bias
+    added before the single rounding. `new` records group_size from quant_config; a module built by hand derives it from the
+    shapes (K // scales.shape[0])."""
+
+    group_size = None
 
     def __init__(self, weight, bias, scales, zeros):
         super().__init__()
@@ -392,7 +399,9 @@ class AutoawqRealQuantLinear(nn.Module):
 
     @torch.no_grad()
     def forward(self, x):
-        raise NotImplementedError
+        from .awq_gemm_ops import awq_linear_forward
+        g = self.group_size or self.qweight.shape[0] // self.scales.shape[0]
+        return awq_linear_forward(x, self.qweight, self.qzeros, self.scales, g, self.bias)
 
     @classmethod
     @torch.no_grad()
@@ -400,6 +409,7 @@ class AutoawqRealQuantLinear(nn.Module):
         weight, scales, zeros = cls.quant_pack(module, w_q, quant_config)
         bias = module.bias.data if module.bias is not None else None
         m = cls(weight, bias, scales, zeros)
+        m.group_size = quant_config['weight']['group_size']
         m.in_features, m.out_features = module.in_features, module.out_features
         m.weight_shape, m.weight_dtype = weight.shape, weight.dtype
         m.scales_shape, m.scales_dtype = scales.shape, scales.dtype

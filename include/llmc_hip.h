@@ -99,6 +99,8 @@ int llmc_hip_set_cu_reserve(int n_cus);
  *   kv_sink_max_grid  n > 0: llmc_kv_sink_update launches at most n blocks per tensor and grid-strides the rest (tests); same bits
  *   block_influence_max_grid  n > 0: llmc_block_influence's row kernel launches at most n blocks and grid-strides the rest (tests);
  *                     same bits
+ *   i8_split_slices   n > 0: llmc_i8_scaled_gemm's decode_split rung cuts K into n slices (at most 16 and one per 128 bytes of K;
+ *                     llmc_i8_scaled_gemm_ws_bytes follows) instead of one workgroup per CU (the measuring tool, tests); same bits
  * set: returns the previous value, or LLMC_EINVAL for an unknown key / negative value. get: the value, or LLMC_EINVAL.
  * option_name: the key of index 0, 1, ... (copied into buf), LLMC_EINVAL past the last one. No reference counterpart. */
 int llmc_hip_set_option(const char* key, int value);
@@ -630,6 +632,38 @@ int llmc_fp8_scaled_gemm(const void* A8, const float* a_s, int64_t a_s_n, const 
 int llmc_fp8_scaled_gemm_on_rung(const void* A8, const float* a_s, int64_t a_s_n, const void* B8, const float* b_s, int64_t b_s_n,
                                  int64_t M, int64_t N, int64_t K, int out_dt, const void* bias, void* C, int rung, llmc_stream_t stream);
 int llmc_fp8_scaled_gemm_rung(int64_t M, int64_t N);
+
+/* ---- W8A8 integer Linear (csrc/i8_linear.hip; an extension: the reference's real-quant Linears raise in forward) --------------
+ * The stored form of configs/quantization/backend/{vllm,sglang}/{smoothquant,awq,rtn}_w8a8: symmetric int8 codes whose scales are
+ * constant along K. A8 [M, K] codes with a_s fp32 [a_s_n], a_s_n = M (one per token) or 1 (per tensor); B8 [N, K] codes (a
+ * weight) with b_s fp32 [b_s_n], b_s_n = N (one per output channel) or 1.
+ *   acc[m, n] = sum_k a[m, k] * b[n, k]                          int32, exact, on the integer matrix pipe
+ *   C[m, n]   = rnd_out(fl(fl(float(acc) * a_s[m]) * b_s[n]))    float(): the int32 -> fp32 conversion, round to nearest even;
+ *                                                                the two fp32 products in this order, one rounding to out_dt
+ * bias [N] (out_dt, may be null) is added after that rounding, like llmc_fp8_scaled_gemm. out_dt: bf16, fp16, fp32.
+ * Instructions: v_mfma_i32_32x32x32_i8 (tile rung), v_mfma_i32_16x16x64_i8 (decode rungs). Integer sums have no accumulation
+ * window and do not depend on their order: every rung returns the same bits, on every run.
+ * K rules: K % 16 == 0 (a ragged last block of 128 is zero-padded in registers, at no cost) and K <= 65536 (the worst case
+ * 128 * 128 * K stays below 2^31). Any M, N >= 1 (edge tiles masked).
+ * Rungs (one table in the source, set from profiles/i8_linear.txt): 0 decode, M <= 64 — 16 columns per workgroup, the K blocks of
+ * 128 dealt round 8 waves whose partial tiles meet in LDS; 1 tile128 — 128 x 128 outputs per workgroup; 2 decode_split, M <= 64 —
+ * the decode rung with K also cut into S slices across workgroups for layers whose N / 16 column tiles leave CUs idle: each slice
+ * stores its int32 tile to ws [S, M, N] with plain stores, a second kernel adds the S tiles and applies the epilogue (no atomics,
+ * two launches). The library does not allocate: ws holds llmc_i8_scaled_gemm_ws_bytes(M, N, K) bytes (S follows N, K and the CU
+ * count; 0 for M > 64) and may be null when decode_split does not run. llmc_i8_scaled_gemm_on_rung runs rung r whatever the shape
+ * (r = -1: the table; for the measuring tool and the tests; a decode rung with M > 64 is LLMC_EINVAL). llmc_i8_scaled_gemm_rung:
+ * the rung the table gives a shape, a pure host call.
+ * LLMC_ENOTSUP (nothing is launched; callers de-quantize and run the 16-bit GEMM): K % 16 != 0, K > 65536, N or the tile count
+ * >= 2^31. LLMC_EINVAL: null operands, codes not 16-byte / scales or ws not 4-byte aligned, another out_dt, a_s_n / b_s_n not in
+ * the allowed set, no such rung, decode_split with ws null or ws_bytes too small. */
+size_t llmc_i8_scaled_gemm_ws_bytes(int64_t M, int64_t N, int64_t K);
+int llmc_i8_scaled_gemm(const void* A8, const float* a_s, int64_t a_s_n, const void* B8, const float* b_s, int64_t b_s_n,
+                        int64_t M, int64_t N, int64_t K, int out_dt, const void* bias, void* C, void* ws, size_t ws_bytes,
+                        llmc_stream_t stream);
+int llmc_i8_scaled_gemm_on_rung(const void* A8, const float* a_s, int64_t a_s_n, const void* B8, const float* b_s, int64_t b_s_n,
+                                int64_t M, int64_t N, int64_t K, int out_dt, const void* bias, void* C, void* ws, size_t ws_bytes,
+                                int rung, llmc_stream_t stream);
+int llmc_i8_scaled_gemm_rung(int64_t M, int64_t N, int64_t K);
 
 /* ---- W4A16 Linear on AutoAWQ's GEMM layout (csrc/awq_gemm.hip; an extension: the reference's AutoawqRealQuantLinear raises in
  * forward) ---- the stored form llmc_pack_awq_gemm writes: qweight int32 [K, R/8], qzeros int32 [K/g, R/8], scales f16 [K/g, R];

@@ -22,8 +22,10 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=o
 # per-file additions. fp8_block.hip: the accumulator update of the K = 64 GEMM is written as scalar fp32 ops on purpose (packed
 # fp32 VALU beside MFMAs costs extra issue time on gfx950); keep the SLP vectoriser from re-packing it.
 # awq_gemm.hip: no packed fp32 VALU forms at all (the bf16 de-quantize multiplies pairs of fp32 values beside MFMAs).
+# i8_linear.hip: the same for its epilogue's two scale products.
 FILE_FLAGS = {'fp8_block.hip': ['-fno-slp-vectorize'],
-              'awq_gemm.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}
+              'awq_gemm.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
+              'i8_linear.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}
 
 
 def _sources():

@@ -277,10 +277,15 @@ class VllmRealQuantLinear(nn.Module):
     per-tensor `weight_scale`: with an e4m3 `act` section, dynamic per_token or static per_tensor, the activation is quantized
     and the epilogue-scaled FP8 GEMM runs (fp8_linear_ops.fp8_linear_forward); weight-only, the weight is de-quantized and goes
     through hip_linear. `new` records what that needs from quant_config (act_cfg, act_mode). Every other stored form raises
-    NotImplementedError, naming itself."""
+    NotImplementedError, naming itself.
+
+    The W8A8 integer form — `weight` int8 with a per-channel or per-tensor `weight_scale` and an 8-bit symmetric int-quant `act`
+    section, dynamic per_token or static per_tensor — runs the same way on the int8 matrix instructions
+    (i8_linear_ops.i8_linear_forward). Weight-only int8 / int4 and the packed (`need_pack`) form do not run."""
 
     act_cfg = None          # the `act` section `new` saw (None: weight-only, or a module built by hand)
-    act_mode = None         # fp8_linear_ops.act_mode(act_cfg), or the NotImplementedError it raised, kept for forward
+    act_mode = None         # fp8_linear_ops / i8_linear_ops.act_mode(act_cfg) by the weight's dtype, or the NotImplementedError it
+                            # raised, kept for forward
 
     def __init__(self, weight, bias, scales, input_scale, need_pack, scales_name):
         super().__init__()
@@ -302,11 +307,19 @@ class VllmRealQuantLinear(nn.Module):
         if getattr(self, 'weight_scale', None) is None:
             raise NotImplementedError(f'{name}.forward: per_block scales (weight_scale_inv) are not provided here; block-128 '
                                       'checkpoints run on LlmcFp8Linear')
-        if self.weight.dtype != torch.float8_e4m3fn:
-            raise NotImplementedError(f'{name}.forward: weight dtype {self.weight.dtype} is not provided (float8_e4m3fn is; int8 '
-                                      'and e5m2 are not)')
+        i8 = self.weight.dtype == torch.int8 and self.act_mode is not None
+        if self.weight.dtype != torch.float8_e4m3fn and not i8:
+            raise NotImplementedError(f'{name}.forward: weight dtype {self.weight.dtype} is not provided (float8_e4m3fn is, and '
+                                      'int8 with an 8-bit `act` section: W8A8; weight-only int8 / int4, the packed need_pack '
+                                      'form and e5m2 are not)')
         if isinstance(self.act_mode, NotImplementedError):
             raise NotImplementedError(f'{name}.forward: {self.act_mode}')
+        if i8:
+            from . import i8_linear_ops as I8
+            if getattr(self, '_aquantizer', None) is None:
+                self._aquantizer = I8._quantizer(self.act_cfg)
+            input_scale = self.input_scale if self.act_mode == 'static_per_tensor' else None
+            return I8.i8_linear_forward(x, self.weight, self.weight_scale, self._aquantizer, input_scale, self.bias)
         if self.act_mode is None:
             if self.input_scale is not None:      # a module built by hand or loaded without its configuration
                 F8._announce(name, tuple(self.weight.shape), 'the module holds an input_scale but no `act` section was '
@@ -334,7 +347,10 @@ class VllmRealQuantLinear(nn.Module):
         m.scales_shape, m.scales_dtype = scales.shape, scales.dtype
         m.zeros_shape = m.zeros_dtype = None
         # what forward needs from the configuration; a pairing it does not run is kept as the error it will raise
-        from .fp8_linear_ops import act_mode
+        if weight.dtype == torch.int8:
+            from .i8_linear_ops import act_mode
+        else:
+            from .fp8_linear_ops import act_mode
         m.act_cfg = dict(quant_config['act']) if 'act' in quant_config else None
         try:
             m.act_mode = act_mode(m.act_cfg)

@@ -73,6 +73,7 @@ enum Opt : int {
     OPT_NO_RIDERS,          // K4 one-stream schedule: a group's far update as one launch instead of near-far launch + rider tiles on the next group's in-block launches
     OPT_KV_SINK_MAX_GRID,   // block cap of llmc_kv_sink_update's launch per tensor (0 = the built-in 8 blocks per CU)
     OPT_BLOCK_INFLUENCE_MAX_GRID,   // block cap of llmc_block_influence's row kernel (0 = the built-in 8 blocks per CU)
+    OPT_I8_SPLIT_SLICES,    // K slices of llmc_i8_scaled_gemm's decode_split rung (0 = one workgroup per CU, at most 16)
     OPT_COUNT
 };
 int opt(int id);

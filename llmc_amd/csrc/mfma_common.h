@@ -1,8 +1,8 @@
 // mfma_common.h — the toolkit of the matrix-pipe kernels, each hardware rule of gfx950 written down once: vector types, the
 // MFMA wrappers, counted waits, the transposing fragment read, buffer descriptors, the LDS-DMA pieces and the split of an
 // fp32 value into three bf16 terms. Included by hessian_syrk.hip, linear_eval.hip, gemm3.hip, gemm3_wide.hip,
-// sgemm_wide_tile.h (sgemm_wide.hip, gptq_loop.hip), fp8_block.hip, mx_gemm.hip and token_select.hip; sgemm.hip and cholesky.hip
-// take the vector types.
+// sgemm_wide_tile.h (sgemm_wide.hip, gptq_loop.hip), fp8_block.hip, mx_gemm.hip, token_select.hip and i8_linear.hip; sgemm.hip and
+// cholesky.hip take the vector types.
 // Everything here is __forceinline__: a kernel's instruction stream is what it was with the helper written out in place.
 #pragma once
 #include "common.h"
@@ -19,6 +19,7 @@ typedef __attribute__((__vector_size__(4 * sizeof(short)))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(8))) int i32x8;
+typedef __attribute__((ext_vector_type(16))) int i32x16;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
@@ -45,6 +46,16 @@ template <> struct Mfma<LLMC_F16> {
 constexpr int MFMA_FMT_E4M3 = 0, MFMA_FMT_E5M2 = 1, MFMA_FMT_E2M1 = 4;
 template <int FA, int FB> __device__ __forceinline__ f32x4 mfma_scale_16x16x128(i32x8 a, i32x8 b, f32x4 c, int scale_a, int scale_b) {
     return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, FA, FB, 0, scale_a, 0, scale_b);
+}
+
+// ---- the integer forms: int8 x int8 products added exactly into int32. 32x32x32: lane l holds 16 consecutive operand bytes of
+// row / column l & 31, k half l >> 5; accumulator register r of lane l is row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31.
+// 16x16x64: lane l holds 16 bytes of row / column l & 15, k quarter l >> 4; register q of lane l is row 4 (l >> 4) + q, column l & 15.
+__device__ __forceinline__ i32x16 mfma_i32_32x32x32_i8(i32x4 a, i32x4 b, i32x16 c) {
+    return __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ i32x4 mfma_i32_16x16x64_i8(i32x4 a, i32x4 b, i32x4 c) {
+    return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0);
 }
 
 // ---- waits. The LDS-DMA pieces below are inline asm, so hipcc's own vmcnt bookkeeping does not count them: the kernels wait

@@ -606,6 +606,42 @@ int llmc_mx_act_quant(const void* X, int dt, int64_t M, int64_t K, int fmt, void
 int llmc_mx_gemm(const void* A, int a_fmt, const void* a_s, const void* B4, const void* b_s, int64_t M, int64_t N, int64_t K,
                  int out_dt, const void* bias, void* C, llmc_stream_t stream);
 
+/* ---- OCP MXFP6 (csrc/mx6_gemm.hip; an extension) -------------------------------------------------------------------------------
+ * The stored form: e3m2 codes (s eee mm, bias 3, no infinity / NaN, largest value 28) + one e8m0 scale byte per 32 consecutive
+ * elements of a row, as FloatQuantizer(bit='e3m2', 'ocp', 'e8m0', per_group, 32) writes them, one code per byte. The dense form
+ * these entry points exchange: a row is a little-endian bit stream with code i of the row at bits 6 i .. 6 i + 5 — bit (6 i + j)
+ * % 8 of byte (6 i + j) / 8 is bit j of code i. 4 codes fill 3 bytes, an MX block of 32 fills 24, a row [3K/4] bytes. This is
+ * the order in which v_mfma_scale_f32_16x16x128_f8f6f4 takes a 6-bit operand: a lane's six registers are a copy of its block.
+ *
+ * llmc_mx6_pack: codes [R, K] uint8, one per byte (bits 6, 7 ignored; 16-byte aligned), K % 32 == 0 -> packed [R, 3K/4] (4-byte
+ * aligned). LLMC_ENOTSUP: K % 32 != 0.
+ *
+ * llmc_mx6_act_quant: X [M, K] contiguous bf16 / fp16 (16-byte aligned), K % 32 == 0 -> out_codes [M, 3K/4] dense (4-byte
+ * aligned) and out_scales [M, K/32] uint8, in one pass. The rules of llmc_mx_act_quant with emax = 4: absmax ignores a NaN;
+ * byte = clamp(exponent_field(absmax) - 4, 0, 254), 127 for an all-zero block; t = x * 2^(127 - byte); round to nearest even onto
+ * the OCP e3m2 grid, saturating at +-28 (infinities too); a NaN gives 28 with the input's sign. Bit for bit llmc_fpx_quant(mode =
+ * ocp | e8m0, fmt 3, g = 32) followed by llmc_mx6_pack. LLMC_ENOTSUP: K % 32 != 0. LLMC_EINVAL: null / misaligned, another dtype.
+ *
+ * llmc_mx6_gemm: A6 [M, 3K/4] dense e3m2 with a_s [M, K/32]; B6 [N, 3K/4] dense e3m2 (a weight) with b_s [N, K/32];
+ *   C[m, n] = sum over 32-deep blocks kb of 2^(a_s[m, kb] + b_s[n, kb] - 254) * sum_{k in kb} a[m, k] * b[n, k]
+ * accumulated in fp32 by the block-scaled instruction, rounded once to out_dt (bf16, fp16, fp32); bias [N] (out_dt, may be null) is
+ * added after that rounding, like llmc_mx_gemm. Numerics (measured): the instruction cuts off what lies more than 13
+ * binary places below 2^(ea + eb) of a block's largest product, and e3m2 x e3m2 products span 18; the A codes are therefore fed in
+ * two exponent classes (fields 0-3, 4-7: two instructions per fragment pair, each block sum exact, joined in the fp32 accumulator).
+ * Rungs (one table in the source): 0 decode, M <= 16 — 16 columns per workgroup, the K steps of 128 dealt round 8 waves whose
+ * partial tiles are added in wave order in LDS (no atomics: the same bits on every run); 1 tile128 — 128 x 128 outputs per
+ * workgroup. llmc_mx6_gemm_on_rung runs rung r whatever the shape (r = -1: the table; for the measuring tool and the tests; the
+ * decode rung with M > 16 is LLMC_EINVAL). llmc_mx6_gemm_rung: the rung the table gives a shape, a pure host call.
+ * Any M, N >= 1 (edge tiles masked). LLMC_ENOTSUP (nothing is launched): K % 128 != 0, K >= 2^24 (or 2^31 tiles).
+ * LLMC_EINVAL: null operands, codes not 16-byte / scales not 4-byte aligned, another out_dt, no such rung. */
+int llmc_mx6_pack(const void* codes, int64_t R, int64_t K, void* packed, llmc_stream_t stream);
+int llmc_mx6_act_quant(const void* X, int dt, int64_t M, int64_t K, void* out_codes, void* out_scales, llmc_stream_t stream);
+int llmc_mx6_gemm(const void* A6, const void* a_s, const void* B6, const void* b_s, int64_t M, int64_t N, int64_t K, int out_dt,
+                  const void* bias, void* C, llmc_stream_t stream);
+int llmc_mx6_gemm_on_rung(const void* A6, const void* a_s, const void* B6, const void* b_s, int64_t M, int64_t N, int64_t K,
+                          int out_dt, const void* bias, void* C, int rung, llmc_stream_t stream);
+int llmc_mx6_gemm_rung(int64_t M, int64_t N, int64_t K);
+
 /* ---- plain W8A8-FP8 Linear (csrc/fp8_linear.hip; an extension: the reference's real-quant Linears raise in forward) -----------
  * The stored form of configs/quantization/backend/{vllm,sglang}/fp8: OCP e4m3fn codes whose scales are constant along K.
  * A8 [M, K] codes with a_s fp32 [a_s_n], a_s_n = M (one per token) or 1 (per tensor); B8 [N, K] codes (a weight) with b_s fp32

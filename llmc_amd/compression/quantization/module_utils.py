@@ -559,6 +559,74 @@ class MxFp4RealQuantLinear(nn.Module):
                 f'scales_shape={self.scales_shape}, scales_dtype={self.scales_dtype}, act_bit={self.act_bit})')
 
 
+class MxFp6RealQuantLinear(nn.Module):
+    """A Linear on the OCP MXFP6 stored form (no reference counterpart): `weight_packed` uint8 [R, 3K/4] (e3m2 codes in the dense
+    form of mx_ops.mx6_pack: 32 codes in 24 bytes) + `weight_scale` uint8 [R, K/32] (e8m0) — what FloatQuantizer(bit='e3m2',
+    float_semantics='ocp', scale_format='e8m0', per_group, group_size=32) returns, packed once. With an activation section (`bit`
+    e3m2, dynamic) forward quantizes the activation per 1 x 32 block and runs the block-scaled MFMA GEMM
+    (mx_ops.mx6_linear_forward); weight-only, or in_features % 128 != 0: the weight is unpacked, de-quantized and goes through
+    hip_linear. e2m1 / e4m3 activations against e3m2 weights are not provided."""
+
+    _WEIGHT = {'bit': 'e3m2', 'granularity': 'per_group', 'group_size': 32, 'float_semantics': 'ocp', 'scale_format': 'e8m0'}
+
+    def __init__(self, weight, bias, scales, act_bit):
+        super().__init__()
+        self.register_buffer('weight_packed', weight)
+        self.register_buffer('weight_scale', scales)
+        if bias is not None:
+            self.register_buffer('bias', bias)
+        else:
+            self.bias = None
+        self.act_bit = act_bit
+
+    @classmethod
+    def check_config(cls, quant_config):
+        """The activation format (None: weight-only) of a configuration this module takes; ValueError with the reason otherwise."""
+        w = quant_config['weight']
+        for k, want in cls._WEIGHT.items():
+            if w.get(k) != want:
+                raise ValueError(f"mxfp6_quant: the weight section needs {k}: {want} (the OCP MX stored form: e3m2 codes, one "
+                                 f"e8m0 scale per 32 elements), got {k}: {w.get(k)!r}")
+        a = quant_config.get('act')
+        if a is None:
+            return None
+        if a.get('bit') != 'e3m2':
+            raise ValueError(f"mxfp6_quant: activations are quantized per 1 x 32 block to e3m2 with e8m0 scales, got act bit: "
+                             f"{a.get('bit')!r} (e2m1, e4m3 and e5m2 activations against e3m2 weights are not provided)")
+        if a.get('static', False):
+            raise ValueError('mxfp6_quant: static activation scales are not provided (the MX block scales are dynamic)')
+        return a['bit']
+
+    @torch.no_grad()
+    def forward(self, x):
+        from .mx_ops import mx6_linear_forward, mx6_unpack
+        from .quant import dequant_fpx
+        if self.act_bit is not None and self.in_features % 128 == 0:
+            return mx6_linear_forward(x, self.weight_packed, self.weight_scale, self.bias)
+        w = dequant_fpx(mx6_unpack(self.weight_packed), self.weight_scale, 'e3m2', 32, x.dtype)
+        return hip_linear(x, w, self.bias)
+
+    @classmethod
+    @torch.no_grad()
+    def new(cls, module, w_q, quant_config):
+        from .mx_ops import mx6_pack
+        act_bit = cls.check_config(quant_config)
+        codes, scales, _ = w_q(module)
+        weight = mx6_pack(codes.reshape(module.out_features, -1))
+        bias = module.bias.data if module.bias is not None else None
+        m = cls(weight, bias, scales.reshape(weight.shape[0], -1).contiguous(), act_bit)
+        m.in_features, m.out_features = module.in_features, module.out_features
+        m.weight_shape, m.weight_dtype = weight.shape, weight.dtype
+        m.scales_shape, m.scales_dtype = m.weight_scale.shape, m.weight_scale.dtype
+        m.zeros_shape = m.zeros_dtype = None
+        return m
+
+    def __repr__(self):
+        return (f'MxFp6RealQuantLinear(in_features={self.in_features}, out_features={self.out_features}, '
+                f'bias={self.bias is not None}, weight_shape={self.weight_shape}, weight_dtype={self.weight_dtype}, '
+                f'scales_shape={self.scales_shape}, scales_dtype={self.scales_dtype}, act_bit={self.act_bit})')
+
+
 _TRANSFORMERS_LINEAR_TYPES_ = [nn.Linear]
 _TRANSFORMERS_LN_TYPES_ = [nn.LayerNorm]
 try:  # RMSNorm-style layers of HF models count as LN types for apply_scale
@@ -571,7 +639,8 @@ if hasattr(nn, 'RMSNorm') and nn.RMSNorm not in _TRANSFORMERS_LN_TYPES_:
 
 _LLMC_LN_TYPES_ = [LlmcRMSNorm]
 _LLMC_LINEAR_TYPES_ = [LlmcFp8Linear, RotateLinear, OriginFloatLinear, FakeQuantLinear, EffcientFakeQuantLinear, VllmRealQuantLinear,
-                       SglRealQuantLinear, AutoawqRealQuantLinear, MlcllmRealQuantLinear, LightllmRealQuantLinear, MxFp4RealQuantLinear]
+                       SglRealQuantLinear, AutoawqRealQuantLinear, MlcllmRealQuantLinear, LightllmRealQuantLinear, MxFp4RealQuantLinear,
+                       MxFp6RealQuantLinear]
 _REALQUANT_LINEAR_MAP_ = {
     'vllm_quant': VllmRealQuantLinear,
     'lightllm_quant': LightllmRealQuantLinear,
@@ -580,4 +649,5 @@ _REALQUANT_LINEAR_MAP_ = {
     'mlcllm_quant': MlcllmRealQuantLinear,
     'lightx2v_quant': Lightx2vRealQuantLinear,
     'mxfp4_quant': MxFp4RealQuantLinear,
+    'mxfp6_quant': MxFp6RealQuantLinear,
 }

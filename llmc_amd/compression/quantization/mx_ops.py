@@ -75,3 +75,67 @@ def mx_linear_forward(x, w_packed, w_s, act_bit, bias):
     """Quantize the activation per 1 x 32 block, multiply by the MXFP4 weight; the output takes the activation's dtype."""
     codes, scales = mx_act_quant(x.contiguous(), act_bit)
     return mx_gemm(codes, scales, act_bit, w_packed, w_s, dtype=x.dtype, bias=bias)
+
+
+# ---- MXFP6: e3m2 codes in the dense form of csrc/mx6_gemm.hip (code i of a row at bits 6 i .. 6 i + 5 of a little-endian bit
+# stream: 32 codes in 24 bytes) + e8m0 block scales ---------------------------------------------------------------------------------
+def mx6_pack(codes):
+    """e3m2 codes [R, K] (uint8, one per byte, K % 32 == 0) -> the dense form [R, 3K/4]."""
+    _ffi.require_gpu(codes)
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.shape[1] % MX_BLOCK:
+        raise ValueError(f'mx6_pack: uint8 codes [R, K] with K % {MX_BLOCK} == 0, got {codes.dtype} {tuple(codes.shape)}')
+    codes = codes.contiguous()
+    R, K = codes.shape
+    packed = torch.empty((R, K // 4 * 3), dtype=torch.uint8, device=codes.device)
+    _ffi.check(_ffi.lib().llmc_mx6_pack(_ffi.ptr(codes), R, K, _ffi.ptr(packed), _ffi.stream()), 'llmc_mx6_pack')
+    return packed
+
+
+def mx6_unpack(packed):
+    """The dense form [R, 3K/4] back to one code per byte [R, K] (torch ops; the de-quantize route of MxFp6RealQuantLinear)."""
+    b = packed.reshape(packed.shape[0], -1, 3).to(torch.int32)
+    b0, b1, b2 = b[..., 0], b[..., 1], b[..., 2]
+    c = torch.stack((b0 & 63, (b0 >> 6) | ((b1 & 15) << 2), (b1 >> 4) | ((b2 & 3) << 4), b2 >> 2), dim=-1)
+    return c.to(torch.uint8).reshape(packed.shape[0], -1)
+
+
+def mx6_act_quant(x):
+    """x [..., K] bf16 / fp16, K % 32 == 0 -> (codes uint8 [..., 3K/4] dense e3m2, scales uint8 [..., K/32] e8m0): per 1 x 32 block
+    scale = 2^(floor(log2 absmax) - 4), element = RNE onto the OCP e3m2 grid, saturating at 28. Bit for bit FloatQuantizer's
+    real-quant route followed by mx6_pack, in one pass."""
+    _ffi.require_gpu(x)
+    assert x.is_contiguous(), 'Input tensor must be contiguous'
+    K = x.size(-1)
+    assert K % MX_BLOCK == 0, f'Last dimension size must be divisible by the MX block ({MX_BLOCK})'
+    M = x.numel() // K
+    codes = torch.empty(*x.shape[:-1], K // 4 * 3, dtype=torch.uint8, device=x.device)
+    scales = torch.empty(*x.shape[:-1], K // MX_BLOCK, dtype=torch.uint8, device=x.device)
+    _ffi.check(_ffi.lib().llmc_mx6_act_quant(_ffi.ptr(x), _ffi.dt(x), M, K, _ffi.ptr(codes), _ffi.ptr(scales), _ffi.stream()),
+               'llmc_mx6_act_quant')
+    return codes, scales
+
+
+def mx6_gemm(a, a_s, w_packed, w_s, dtype=torch.bfloat16, bias=None, rung=-1):
+    """c[..., N] = sum over 32-deep blocks of 2^(a_s + w_s - 254) * (a_blk . w_blk^T): a [..., 3K/4] and w_packed [N, 3K/4] dense
+    e3m2 with a_s [..., K/32], w_s [N, K/32]; K % 128 == 0. fp32 accumulation inside the block-scaled MFMA, one rounding to `dtype`,
+    then the bias in `dtype`. rung: -1 the ladder (llmc_mx6_gemm_rung), 0 decode (M <= 16), 1 tile128."""
+    _ffi.require_gpu(a, a_s, w_packed, w_s, bias)
+    assert a.is_contiguous() and w_packed.is_contiguous(), 'Input tensors must be contiguous'
+    assert a_s.is_contiguous() and w_s.is_contiguous(), 'Scaling factor tensors must be contiguous'
+    assert a.dtype == torch.uint8 and w_packed.dtype == torch.uint8 and a_s.dtype == torch.uint8 and w_s.dtype == torch.uint8
+    N, K = w_packed.size(0), w_packed.size(1) // 3 * 4
+    assert a.size(-1) == K // 4 * 3, 'activation and weight disagree on K'
+    assert a_s.size(-1) == K // MX_BLOCK and tuple(w_s.shape) == (N, K // MX_BLOCK), 'one scale byte per 32 elements'
+    M = a.numel() // a.size(-1)
+    c = torch.empty(*a.shape[:-1], N, dtype=dtype, device=a.device)
+    if bias is not None:
+        bias = bias.to(dtype).contiguous()
+    _ffi.check(_ffi.lib().llmc_mx6_gemm_on_rung(_ffi.ptr(a), _ffi.ptr(a_s), _ffi.ptr(w_packed), _ffi.ptr(w_s), M, N, K, _ffi.dt(dtype),
+                                                _ffi.ptr(bias), _ffi.ptr(c), rung, _ffi.stream()), 'llmc_mx6_gemm')
+    return c
+
+
+def mx6_linear_forward(x, w_packed, w_s, bias):
+    """Quantize the activation per 1 x 32 block to e3m2, multiply by the MXFP6 weight; the output takes the activation's dtype."""
+    codes, scales = mx6_act_quant(x.contiguous())
+    return mx6_gemm(codes, scales, w_packed, w_s, dtype=x.dtype, bias=bias)

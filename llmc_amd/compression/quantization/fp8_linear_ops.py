@@ -3,23 +3,16 @@ deploy('vllm_quant' | 'sgl_quant' | 'lightllm_quant' | 'lightx2v_quant') writes 
 configurations — a float8_e4m3fn weight [R, K] with a per-channel or per-tensor `weight_scale`, activations quantized per token
 on the fly or per tensor with a calibrated `input_scale`. Both scales are constant along K and are applied to the fp32
 accumulator in the GEMM's epilogue. An extension: the reference's real-quant Linears raise in forward."""
-import sys
-
 import torch
 
 from llmc_amd import _ffi
 
+from . import scaled8_ops
 from .quant import FloatQuantizer
+from .scaled8_ops import _FALLBACK_SEEN, _announce          # noqa: F401  (awq_gemm_ops, module_utils and the tests take them here)
 
 FP8 = torch.float8_e4m3fn
 RUNGS = {'decode': 0, 'tile128': 1}         # llmc_fp8_scaled_gemm's launch rungs (include/llmc_hip.h)
-_FALLBACK_SEEN = set()
-
-
-def _announce(what, sig, why, instead):
-    if (what, sig) not in _FALLBACK_SEEN:
-        _FALLBACK_SEEN.add((what, sig))
-        print(f'[llmc_amd] {what} {sig}: {why} -> {instead}', file=sys.stderr)
 
 
 def act_mode(act_cfg):
@@ -71,39 +64,12 @@ def fp8_act_quant(x, act_cfg, input_scale=None):
     return codes.reshape(x.shape), scales.float()           # widening a 16-bit scale is exact
 
 
-def _check_gemm(a8, a_s, w8, w_s, dtype, bias):
-    """Shapes and dtypes of an fp8_scaled_gemm call; returns (M, N, K). Raises before anything touches the GPU."""
-    for name, t in (('a8', a8), ('w8', w8)):
-        if t.dtype not in (FP8, torch.uint8):
-            raise TypeError(f'fp8_scaled_gemm: {name} holds e4m3fn codes (float8_e4m3fn or uint8), got {t.dtype}')
-    if w8.dim() != 2 or a8.dim() < 1:
-        raise ValueError(f'fp8_scaled_gemm: the weight is [N, K] and the activation [..., K], got {tuple(w8.shape)} and {tuple(a8.shape)}')
-    N, K = w8.shape
-    if a8.shape[-1] != K:
-        raise ValueError(f'fp8_scaled_gemm: activation and weight disagree on K ({a8.shape[-1]} and {K})')
-    M = a8.numel() // max(K, 1)
-    if M < 1 or N < 1 or K < 1:
-        raise ValueError(f'fp8_scaled_gemm: empty operand (M, N, K = {M}, {N}, {K})')
-    if a_s.numel() not in (1, M):
-        raise ValueError(f'fp8_scaled_gemm: a_s holds one scale per token ({M}) or one, got {a_s.numel()}')
-    if w_s.numel() not in (1, N):
-        raise ValueError(f'fp8_scaled_gemm: w_s holds one scale per output channel ({N}) or one, got {w_s.numel()}')
-    for name, t in (('a_s', a_s), ('w_s', w_s)):
-        if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            raise TypeError(f'fp8_scaled_gemm: {name} is fp32, fp16 or bf16, got {t.dtype}')
-    if dtype not in (torch.float32, torch.float16, torch.bfloat16):
-        raise TypeError(f'fp8_scaled_gemm: the output is fp32, fp16 or bf16, got {dtype}')
-    if bias is not None and bias.numel() != N:
-        raise ValueError(f'fp8_scaled_gemm: the bias holds {N} elements, got {bias.numel()}')
-    return M, N, K
-
-
 def fp8_scaled_gemm(a8, a_s, w8, w_s, dtype=torch.bfloat16, bias=None, rung=None):
     """c[..., N] = rnd(((a8 . w8^T) * a_s) * w_s) (+ bias in `dtype`): a8 [..., K] and w8 [N, K] e4m3fn codes, a_s one scale per
     token or one, w_s one per output channel or one; fp32 accumulation of exact products, the two scale products in this order,
     one rounding. K % 128 == 0 (else NotImplementedError: fp8_linear_forward has the fallback). rung: None (the library's
     table), or 'decode' / 'tile128' to name the launch rung (tools, tests)."""
-    M, N, K = _check_gemm(a8, a_s, w8, w_s, dtype, bias)
+    M, N, K = scaled8_ops.check_gemm('fp8_scaled_gemm', (FP8, torch.uint8), 'e4m3fn codes (float8_e4m3fn or uint8)', a8, a_s, w8, w_s, dtype, bias)
     _ffi.require_gpu(a8, a_s, w8, w_s, bias)
     a8, w8 = a8.contiguous(), w8.contiguous()
     a_s, w_s = a_s.reshape(-1).float().contiguous(), w_s.reshape(-1).float().contiguous()
@@ -119,23 +85,10 @@ def fp8_scaled_gemm(a8, a_s, w8, w_s, dtype=torch.bfloat16, bias=None, rung=None
 
 
 def fp8_dequant(codes, scales, dtype):
-    """decode(code) * scale, an fp32 product rounded once to `dtype`: the weight (scales [R, 1] or one) or the activation
-    (scales [..., 1] or one) back as numbers."""
-    if codes.dtype == torch.uint8:
-        codes = codes.view(FP8)
-    s = scales.float()
-    return (codes.float() * (s.reshape(()) if s.numel() == 1 else s.reshape(*codes.shape[:-1], 1))).to(dtype)
+    """scaled8_ops.dequant; raw bytes (uint8) are e4m3fn codes."""
+    return scaled8_ops.dequant(codes.view(FP8) if codes.dtype == torch.uint8 else codes, scales, dtype)
 
 
 def fp8_linear_forward(x, w8, w_s, act_cfg, input_scale, bias):
-    """Quantize the activation (fp8_act_quant), multiply by the FP8 weight; the output takes the activation's dtype. A depth the
-    GEMM does not take (K % 128 != 0) goes, said once per shape on stderr, through the 16-bit GEMM on the two de-quantized operands:
-    the fake-quant Linear of the same codes. Nothing takes that way for speed."""
-    codes, scales = fp8_act_quant(x.contiguous(), act_cfg, input_scale)
-    try:
-        return fp8_scaled_gemm(codes, scales, w8, w_s, dtype=x.dtype, bias=bias)
-    except NotImplementedError as e:          # LLMC_ENOTSUP: nothing was launched
-        why = str(e)
-    from .module_utils import hip_linear
-    _announce('fp8_linear', (tuple(x.shape), tuple(w8.shape), str(x.dtype)), why, 'de-quantized operands through the 16-bit HIP GEMM')
-    return hip_linear(fp8_dequant(codes, scales, x.dtype), fp8_dequant(w8, w_s, x.dtype), bias)
+    """scaled8_ops.linear_forward on fp8_act_quant and fp8_scaled_gemm; the GEMM does not take K % 128 != 0."""
+    return scaled8_ops.linear_forward('fp8_linear', fp8_act_quant, fp8_scaled_gemm, fp8_dequant, x, w8, w_s, act_cfg, input_scale, bias)

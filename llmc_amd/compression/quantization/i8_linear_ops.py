@@ -8,8 +8,9 @@ import torch
 
 from llmc_amd import _ffi
 
-from .fp8_linear_ops import _FALLBACK_SEEN, _announce          # one "said once" record for both Linears
+from . import scaled8_ops
 from .quant import IntegerQuantizer
+from .scaled8_ops import _FALLBACK_SEEN, _announce          # noqa: F401  (the tests take them here)
 
 RUNGS = {'decode': 0, 'tile128': 1, 'decode_split': 2}         # llmc_i8_scaled_gemm's launch rungs (include/llmc_hip.h)
 DECODE_MAX_M = 64                                              # the most rows the two decode rungs take
@@ -72,29 +73,8 @@ def i8_act_quant(x, act_cfg, input_scale=None):
 
 
 def _check_gemm(a8, a_s, w8, w_s, dtype, bias, rung):
-    """Shapes and dtypes of an i8_scaled_gemm call; returns (M, N, K). Raises before anything touches the GPU."""
-    for name, t in (('a8', a8), ('w8', w8)):
-        if t.dtype != torch.int8:
-            raise TypeError(f'i8_scaled_gemm: {name} holds int8 codes, got {t.dtype}')
-    if w8.dim() != 2 or a8.dim() < 1:
-        raise ValueError(f'i8_scaled_gemm: the weight is [N, K] and the activation [..., K], got {tuple(w8.shape)} and {tuple(a8.shape)}')
-    N, K = w8.shape
-    if a8.shape[-1] != K:
-        raise ValueError(f'i8_scaled_gemm: activation and weight disagree on K ({a8.shape[-1]} and {K})')
-    M = a8.numel() // max(K, 1)
-    if M < 1 or N < 1 or K < 1:
-        raise ValueError(f'i8_scaled_gemm: empty operand (M, N, K = {M}, {N}, {K})')
-    if a_s.numel() not in (1, M):
-        raise ValueError(f'i8_scaled_gemm: a_s holds one scale per token ({M}) or one, got {a_s.numel()}')
-    if w_s.numel() not in (1, N):
-        raise ValueError(f'i8_scaled_gemm: w_s holds one scale per output channel ({N}) or one, got {w_s.numel()}')
-    for name, t in (('a_s', a_s), ('w_s', w_s)):
-        if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            raise TypeError(f'i8_scaled_gemm: {name} is fp32, fp16 or bf16, got {t.dtype}')
-    if dtype not in (torch.float32, torch.float16, torch.bfloat16):
-        raise TypeError(f'i8_scaled_gemm: the output is fp32, fp16 or bf16, got {dtype}')
-    if bias is not None and bias.numel() != N:
-        raise ValueError(f'i8_scaled_gemm: the bias holds {N} elements, got {bias.numel()}')
+    """scaled8_ops.check_gemm and the rung's name and row limit; returns (M, N, K)."""
+    M, N, K = scaled8_ops.check_gemm('i8_scaled_gemm', (torch.int8,), 'int8 codes', a8, a_s, w8, w_s, dtype, bias)
     if rung is not None and rung not in RUNGS:
         raise ValueError(f'i8_scaled_gemm: rung is one of {sorted(RUNGS)} or None, got {rung!r}')
     if rung in ('decode', 'decode_split') and M > DECODE_MAX_M:
@@ -125,22 +105,9 @@ def i8_scaled_gemm(a8, a_s, w8, w_s, dtype=torch.bfloat16, bias=None, rung=None)
     return c
 
 
-def i8_dequant(codes, scales, dtype):
-    """code * scale, an fp32 product rounded once to `dtype`: the weight (scales [R, 1] or one) or the activation (scales
-    [..., 1] or one) back as numbers."""
-    s = scales.float()
-    return (codes.float() * (s.reshape(()) if s.numel() == 1 else s.reshape(*codes.shape[:-1], 1))).to(dtype)
+i8_dequant = scaled8_ops.dequant
 
 
 def i8_linear_forward(x, w8, w_s, act_cfg, input_scale, bias):
-    """Quantize the activation (i8_act_quant), multiply by the int8 weight; the output takes the activation's dtype. A depth the
-    GEMM does not take (K % 16 != 0, K > 65536) goes, said once per shape on stderr, through the 16-bit GEMM on the two
-    de-quantized operands: the fake-quant Linear of the same codes. Nothing takes that way for speed."""
-    codes, scales = i8_act_quant(x.contiguous(), act_cfg, input_scale)
-    try:
-        return i8_scaled_gemm(codes, scales, w8, w_s, dtype=x.dtype, bias=bias)
-    except NotImplementedError as e:          # LLMC_ENOTSUP: nothing was launched
-        why = str(e)
-    from .module_utils import hip_linear
-    _announce('i8_linear', (tuple(x.shape), tuple(w8.shape), str(x.dtype)), why, 'de-quantized operands through the 16-bit HIP GEMM')
-    return hip_linear(i8_dequant(codes, scales, x.dtype), i8_dequant(w8, w_s, x.dtype), bias)
+    """scaled8_ops.linear_forward on i8_act_quant and i8_scaled_gemm; the GEMM does not take K % 16 != 0 or K > 65536."""
+    return scaled8_ops.linear_forward('i8_linear', i8_act_quant, i8_scaled_gemm, i8_dequant, x, w8, w_s, act_cfg, input_scale, bias)

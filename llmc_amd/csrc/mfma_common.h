@@ -1,8 +1,8 @@
 // mfma_common.h — the toolkit of the matrix-pipe kernels, each hardware rule of gfx950 written down once: vector types, the
 // MFMA wrappers, counted waits, the transposing fragment read, buffer descriptors, the LDS-DMA pieces and the split of an
 // fp32 value into three bf16 terms. Included by hessian_syrk.hip, linear_eval.hip, gemm3.hip, gemm3_wide.hip,
-// sgemm_wide_tile.h (sgemm_wide.hip, gptq_loop.hip), fp8_block.hip, mx_gemm.hip, token_select.hip and i8_linear.hip; sgemm.hip and
-// cholesky.hip take the vector types.
+// sgemm_wide_tile.h (sgemm_wide.hip, gptq_loop.hip), fp8_block.hip, mx_gemm.hip, token_select.hip and scaled8_gemm.h
+// (fp8_linear.hip, i8_linear.hip); sgemm.hip and cholesky.hip take the vector types.
 // Everything here is __forceinline__: a kernel's instruction stream is what it was with the helper written out in place.
 #pragma once
 #include "common.h"
@@ -20,6 +20,7 @@ typedef __attribute__((ext_vector_type(8))) short s16x8;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 typedef __attribute__((ext_vector_type(16))) int i32x16;
+typedef __attribute__((ext_vector_type(2))) long i64x2;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
@@ -56,6 +57,15 @@ __device__ __forceinline__ i32x16 mfma_i32_32x32x32_i8(i32x4 a, i32x4 b, i32x16 
 }
 __device__ __forceinline__ i32x4 mfma_i32_16x16x64_i8(i32x4 a, i32x4 b, i32x4 c) {
     return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0);
+}
+
+// ---- the non-scaled fp8 form of the 32 x 32 tile (e4m3 x e4m3 into fp32; its accumulation window: csrc/fp8_linear.hip) takes 8 operand bytes per
+// lane and instruction: a lane's 16 bytes are two consecutive instructions, the low 8 bytes first. Lanes, rows and accumulator
+// registers as in the integer form of the same tile.
+__device__ __forceinline__ f32x16 mfma_f32_32x32x16_fp8_x2(i32x4 a, i32x4 b, f32x16 c) {
+    const i64x2 a2 = __builtin_bit_cast(i64x2, a), b2 = __builtin_bit_cast(i64x2, b);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(a2[0], b2[0], c, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(a2[1], b2[1], c, 0, 0, 0);
 }
 
 // ---- waits. The LDS-DMA pieces below are inline asm, so hipcc's own vmcnt bookkeeping does not count them: the kernels wait

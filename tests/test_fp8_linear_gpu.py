@@ -118,6 +118,25 @@ def test_one_hot_rows_against_an_asymmetric_weight():
             assert np.array_equal(got, E), (M, N, rung, np.argwhere(got != E)[:6].tolist())
 
 
+@pytest.mark.parametrize('M,N,rung', [(17, 130, 'decode'), (17, 130, 'tile128'), (65, 130, 'tile128')])
+def test_nan_in_the_last_rows_stays_in_its_own_row_and_column(M, N, rung):
+    """Rows past M / N are loaded from the last valid row and not masked: their products must never reach a stored output. The
+    last valid row of A and of B hold the NaN code 0x7f, so every padding row of the last tiles is a copy of a NaN row: row M - 1
+    and column N - 1 of C are NaN and every other element is the exact result, bit for bit."""
+    K = 128
+    a, _, b, _ = O.exact_case(M, N, K, seed=31 * M + N)
+    ok, ratio = O.exact_in_any_order(a, b)
+    assert ok, ratio
+    want = rounded_once(O.decode_e4m3fn(a) @ O.decode_e4m3fn(b).T, 'f32')
+    a, b = a.copy(), b.copy()
+    a[M - 1], b[N - 1] = 0x7f, 0x7f
+    one = gpu(np.ones(1, np.float32))
+    got = gemm(gpu(a), one, gpu(b), one, 'f32', None, rung).cpu()
+    assert bool(got[M - 1].isnan().all()) and bool(got[:, N - 1].isnan().all()), (M, N, rung)
+    bad = bits_of(got[:M - 1, :N - 1]) != bits_of(want[:M - 1, :N - 1])
+    assert not bad.any(), (M, N, rung, int(bad.sum()), np.argwhere(bad)[:4].tolist())
+
+
 def test_what_the_instruction_keeps():
     """The part of the measured accumulation behaviour the bound's derivation relies on (oracle header), kept as a
     regression test: a product 13 binary places below the leading bit of the largest product of its own group of 8 survives

@@ -727,6 +727,29 @@ int llmc_awq_gemm(const void* x, int dt, int64_t M, int64_t K, int64_t R, const 
 int llmc_awq_dequant(const int32_t* qweight, const int32_t* qzeros, const void* scales, int64_t K, int64_t R, int64_t g,
                      void* out, int out_dt, llmc_stream_t stream);
 
+/* ---- W4A8 Linear on the same stored form (csrc/awq_i8_gemm.hip): the packed nibbles times int8 activation codes a8 [M, K] with
+ * a_s fp32 [a_s_n], a_s_n = M (one scale per token) or 1 (per tensor), on v_mfma_i32_32x32x32_i8.
+ *   d(k, n)    = code(k, n) - zero(k / g, n)                   integers in [-15, 15], nibbles read as stored (as above)
+ *   S_g(m, n)  = sum over the k of group g of a8(m, k) d(k, n)  int32, exact
+ *   acc(m, n)  = fmaf(float(S_g), float(scales[g][n]), acc)    for g ascending, from 0: fp32, ONE fused multiply-add per group;
+ *                                                              float(S_g) is exact (g * 128 * 15 < 2^24)
+ *   y(m, n)    = rnd_dt(a_s(m) * acc(m, n) + bias(n))          an fp32 product, then an fp32 sum, one rounding to dt = f16 or bf16
+ * Any M >= 1 and any R % 8 == 0 (edges masked), K % g == 0.
+ * rung: -1 the ladder (llmc_awq_i8_gemm_rung: the rung it gives a shape, a pure host call); 0 stream — small M: one wave per 256
+ * columns x 32 rows x K slice of whole groups opens the nibbles in registers; the slices' fp32 partials (ws, ws_bytes:
+ * llmc_awq_i8_gemm_ws_bytes, a pure host call; required by this rung) are added in ascending slice order by a second kernel that
+ * applies a_s and the bias, no atomics: the same bits on every run; 1 tile — 128 x 256 outputs per workgroup, each 128-k block of
+ * the weight tile opened once per workgroup into LDS. A named rung runs whatever M.
+ * LLMC_ENOTSUP (nothing is launched; callers de-quantize the codes and take llmc_awq_gemm's route): g % 32 != 0 (a 32-k MFMA step
+ * would straddle a group); g > 8192; K >= 2^22, M or R >= 2^31 or 2^24 tiles of 32 x 256; a8, y, scales or ws not 16-byte, the
+ * words or a_s not 4-byte aligned. LLMC_EINVAL: null operands, another dt, R % 8 != 0, K % g != 0, a_s_n not 1 or M, no such rung,
+ * the stream rung with ws null or ws_bytes too small. */
+size_t llmc_awq_i8_gemm_ws_bytes(int64_t M, int64_t K, int64_t R, int64_t g);
+int llmc_awq_i8_gemm_on_rung(const void* a8, const float* a_s, int64_t a_s_n, int64_t M, int64_t K, int64_t R,
+                             const int32_t* qweight, const int32_t* qzeros, const void* scales, int64_t g, int out_dt,
+                             const void* bias, void* y, void* ws, size_t ws_bytes, int rung, llmc_stream_t stream);
+int llmc_awq_i8_gemm_rung(int64_t M, int64_t K, int64_t R);
+
 /* ---- SmoothQuant / OS+ (smoothquant.py:39-59, osplus.py:61-170) ------------------------------------------------------------
  * Column statistics of X [N, K] dt (N up to 2^31 rows): run[0:K] = max, run[K:2K] = min, run[2K:3K] = max |x| per column, fp32
  * (exact: they are values of dt). init != 0: the buffers are written; else the batch is folded into them (running max / min

@@ -129,6 +129,9 @@ SIGNATURES = {
     'llmc_awq_gemm_ws_bytes': (_sz, [_i64, _i64, _i64]),
     'llmc_awq_gemm': (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32]),
     'llmc_awq_dequant': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp]),
+    'llmc_awq_i8_gemm_ws_bytes': (_sz, [_i64, _i64, _i64, _i64]),
+    'llmc_awq_i8_gemm_on_rung': (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _sz, _i32, _vp]),
+    'llmc_awq_i8_gemm_rung': (_i32, [_i64, _i64, _i64]),
     'llmc_pack_awq_gemm': (_i32, [_vp, _i32, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     'llmc_col_stats_ws_bytes': (_sz, [_i64, _i64]),
     'llmc_col_stats': (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),

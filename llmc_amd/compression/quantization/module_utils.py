@@ -396,9 +396,16 @@ class AutoawqRealQuantLinear(nn.Module):
     forward (an extension: the reference raises) runs the fused int4 de-quantize MFMA GEMM on the packed buffers
     (awq_gemm_ops.awq_linear_forward): W~ = rnd((code - zero) * scale) in the activation's dtype, fp32 accumulation, the bias
     added before the single rounding. `new` records group_size from quant_config; a module built by hand derives it from the
-    shapes (K // scales.shape[0])."""
+    shapes (K // scales.shape[0]).
+
+    With an 8-bit symmetric int-quant `act` section, dynamic per_token or static per_tensor (W4A8), `new` records act_cfg, act_mode
+    and, for static activations, the `input_scale` buffer; forward then quantizes the activation and multiplies the packed
+    nibbles on the int8 matrix instructions (awq_gemm_ops.awq_i8_linear_forward). No `act` section, or a module built by hand:
+    the W4A16 path."""
 
     group_size = None
+    act_cfg = None          # the `act` section `new` saw (None: weight-only, or a module built by hand)
+    act_mode = None         # i8_linear_ops.act_mode(act_cfg), or the NotImplementedError it raised, kept for forward
 
     def __init__(self, weight, bias, scales, zeros):
         super().__init__()
@@ -415,9 +422,17 @@ class AutoawqRealQuantLinear(nn.Module):
 
     @torch.no_grad()
     def forward(self, x):
-        from .awq_gemm_ops import awq_linear_forward
+        from .awq_gemm_ops import awq_i8_linear_forward, awq_linear_forward
         g = self.group_size or self.qweight.shape[0] // self.scales.shape[0]
-        return awq_linear_forward(x, self.qweight, self.qzeros, self.scales, g, self.bias)
+        if isinstance(self.act_mode, NotImplementedError):
+            raise NotImplementedError(f'{type(self).__name__}.forward: {self.act_mode}')
+        if self.act_mode is None:
+            return awq_linear_forward(x, self.qweight, self.qzeros, self.scales, g, self.bias)
+        if getattr(self, '_aquantizer', None) is None:
+            from .i8_linear_ops import _quantizer
+            self._aquantizer = _quantizer(self.act_cfg)
+        input_scale = getattr(self, 'input_scale', None) if self.act_mode == 'static_per_tensor' else None
+        return awq_i8_linear_forward(x, self.qweight, self.qzeros, self.scales, g, self._aquantizer, input_scale, self.bias)
 
     @classmethod
     @torch.no_grad()
@@ -431,6 +446,15 @@ class AutoawqRealQuantLinear(nn.Module):
         m.scales_shape, m.scales_dtype = scales.shape, scales.dtype
         m.zeros_shape = zeros.shape if zeros is not None else None
         m.zeros_dtype = zeros.dtype if zeros is not None else None
+        # what a W4A8 forward needs from the configuration; a pairing it does not run is kept as the error it will raise
+        from .i8_linear_ops import act_mode
+        m.act_cfg = dict(quant_config['act']) if 'act' in quant_config else None
+        try:
+            m.act_mode = act_mode(m.act_cfg)
+        except NotImplementedError as e:
+            m.act_mode = e
+        if m.act_mode == 'static_per_tensor':
+            m.register_buffer('input_scale', module.buf_act_scales_0.unsqueeze(0))
         return m
 
     @classmethod

@@ -701,6 +701,34 @@ int llmc_i8_scaled_gemm_on_rung(const void* A8, const float* a_s, int64_t a_s_n,
                                 int rung, llmc_stream_t stream);
 int llmc_i8_scaled_gemm_rung(int64_t M, int64_t N, int64_t K);
 
+/* ---- QUIK real-quant Linear (csrc/quik_gemm.hip; an extension: the reference has QUIK's fake-quant method only) ---- the K input
+ * channels are n_int = K - F integer channels and F outlier channels. Stored form: W8 int8 [N, Ki] (the integer channels' codes,
+ * Ki = n_int rounded up to 64, padding code 0), w_s fp32 [N], W_fp f16 / bf16 [N, Fp] (the outlier channels' own bits, Fp = F
+ * rounded up to 32, padding +0).
+ * llmc_quik_act_split: x [M, K] (f16 / bf16) -> codes int8 [M, Ki], scales fp32 [M], a_fp [M, Fp] in x's dtype, in one pass.
+ * col_map int32 [K] gives source column c its slot: j < Ki for integer slot j, Ki + j for outlier slot j (a permutation onto the
+ * first n_int integer and first F outlier slots; an entry outside [0, Ki + Fp) is skipped). Codes and scale are bit for bit what
+ * llmc_quant_dynamic (symmetric, 8 bit, one group per row, LLMC_OUT_I8) gives on the gathered integer channels; padding slots are
+ * code 0 / +0. LLMC_ENOTSUP (nothing is launched; llmc_quik_act_split_fits answers 0, a pure host call): another dtype,
+ * K % 8 != 0, or a permuted row that does not fit the LDS of a CU (above about 81900 slots). a_fp may be null when Fp == 0.
+ * llmc_quik_gemm: C[m, n] = rnd_out(fl(fl(float(sum_k a8[m, k] w8[n, k]) * a_s[m]) * w_s[n]) + sum_j a_fp[m, j] w_fp[n, j]), then
+ * the bias in out_dt (f16 / bf16 / f32; fp_dt: the dtype of a_fp and w_fp, f16 or bf16). The integer sum is exact int32, the
+ * 16-bit products are accumulated in fp32 by the matrix instructions on top of the scaled integer part (rung 1, tile128: in one
+ * accumulator set, retyped in place) or per wave and then added in wave order (rung 0, decode, M <= 64). No atomics, no
+ * workspace: the same bits on every call. llmc_quik_gemm_on_rung runs rung r whatever the shape (r = -1: the table; a decode
+ * rung with M > 64 is LLMC_EINVAL); llmc_quik_gemm_rung: the rung the table gives a shape, a pure host call.
+ * LLMC_ENOTSUP (nothing is launched): Ki % 64 != 0, Fp % 32 != 0, Ki > 65536, Fp > 32768, N or the tile count >= 2^31.
+ * LLMC_EINVAL: null operands (a_fp / w_fp may be null when Fp == 0), misaligned operands, another dtype, no such rung. */
+int llmc_quik_act_split_fits(int dt, int64_t K, int64_t Ki, int64_t Fp);
+int llmc_quik_act_split(const void* X, int dt, int64_t M, int64_t K, const int32_t* col_map, int64_t Ki, int64_t Fp, void* codes, float* scales, void* a_fp, llmc_stream_t stream);
+int llmc_quik_gemm(const void* A8, const float* a_s, const void* A_fp, const void* W8, const float* w_s, const void* W_fp,
+                   int64_t M, int64_t N, int64_t Ki, int64_t Fp, int fp_dt, int out_dt, const void* bias, void* C,
+                   llmc_stream_t stream);
+int llmc_quik_gemm_on_rung(const void* A8, const float* a_s, const void* A_fp, const void* W8, const float* w_s, const void* W_fp,
+                           int64_t M, int64_t N, int64_t Ki, int64_t Fp, int fp_dt, int out_dt, const void* bias, void* C,
+                           int rung, llmc_stream_t stream);
+int llmc_quik_gemm_rung(int64_t M, int64_t N);
+
 /* ---- W4A16 Linear on AutoAWQ's GEMM layout (csrc/awq_gemm.hip; an extension: the reference's AutoawqRealQuantLinear raises in
  * forward) ---- the stored form llmc_pack_awq_gemm writes: qweight int32 [K, R/8], qzeros int32 [K/g, R/8], scales f16 [K/g, R];
  * column 8 c + j of a word c sits in nibble INV[j], INV = 0,4,1,5,2,6,3,7 (the inverse of the packing order 0,2,4,6,1,3,5,7).

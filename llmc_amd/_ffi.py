@@ -126,6 +126,11 @@ SIGNATURES = {
     'llmc_i8_scaled_gemm': (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
     'llmc_i8_scaled_gemm_on_rung': (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _sz, _i32, _vp]),
     'llmc_i8_scaled_gemm_rung': (_i32, [_i64, _i64, _i64]),
+    'llmc_quik_act_split_fits': (_i32, [_i32, _i64, _i64, _i64]),
+    'llmc_quik_act_split': (_i32, [_vp, _i32, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    'llmc_quik_gemm': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
+    'llmc_quik_gemm_on_rung': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _i32, _vp]),
+    'llmc_quik_gemm_rung': (_i32, [_i64, _i64]),
     'llmc_awq_gemm_ws_bytes': (_sz, [_i64, _i64, _i64]),
     'llmc_awq_gemm': (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32]),
     'llmc_awq_dequant': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp]),

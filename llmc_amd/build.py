@@ -24,10 +24,12 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=o
 # awq_gemm.hip: no packed fp32 VALU forms at all (the bf16 de-quantize multiplies pairs of fp32 values beside MFMAs).
 # i8_linear.hip: the same for its epilogue's two scale products.
 # mx6_gemm.hip: the same for the decode rung's sum of the waves' partial tiles and the activation quantizer's scaling products.
+# quik_gemm.hip: the same for the accumulators' retyping (two scale products each) between its two MFMA phases.
 FILE_FLAGS = {'fp8_block.hip': ['-fno-slp-vectorize'],
               'awq_gemm.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
               'i8_linear.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
-              'mx6_gemm.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}
+              'mx6_gemm.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
+              'quik_gemm.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}
 
 
 def _sources():

@@ -651,6 +651,101 @@ class MxFp6RealQuantLinear(nn.Module):
                 f'scales_shape={self.scales_shape}, scales_dtype={self.scales_dtype}, act_bit={self.act_bit})')
 
 
+class QuikRealQuantLinear(nn.Module):
+    """A Linear on QUIK's stored form (no reference counterpart: the reference has the fake-quant method only). With
+    F = fp_ids.numel(), n_int = K - F, Ki = n_int rounded up to 64 and Fp = F rounded up to 32:
+    `weight` int8 [R, Ki] (the codes of the columns int_ids, in that order; padding 0) + `weight_scale` fp32 [R, 1] — the weight
+    quantizer's real_quant_weight_dynamic on W.index_select(1, int_ids), the per-row range over the int columns only;
+    `weight_fp` [R, Fp] in the Linear's 16-bit dtype (the columns fp_ids, their own bits; padding +0); `int_ids`, `fp_ids` int32;
+    `col_map` int32 [K]: source column -> slot (j for int slot j, Ki + j for fp slot j), what the activation split reads.
+    forward (quik_ops.quik_linear_forward) splits the activation into int8 codes with one scale per token and the outlier values,
+    then runs the int8 MFMA GEMM with the 16-bit outlier product added into the same accumulators. `new` records act_cfg and
+    act_mode; a pairing the kernels do not take is kept as the NotImplementedError forward raises."""
+
+    act_cfg = None
+    act_mode = None         # 'dynamic_per_token', or the NotImplementedError forward raises
+
+    def __init__(self, weight, bias, scales, weight_fp, int_ids, fp_ids, col_map):
+        super().__init__()
+        self.register_buffer('weight', weight)
+        self.register_buffer('weight_scale', scales)
+        self.register_buffer('weight_fp', weight_fp)
+        self.register_buffer('int_ids', int_ids)
+        self.register_buffer('fp_ids', fp_ids)
+        self.register_buffer('col_map', col_map)
+        if bias is not None:
+            self.register_buffer('bias', bias)
+        else:
+            self.bias = None
+
+    @staticmethod
+    def check_config(quant_config):
+        """'dynamic_per_token' for a configuration the kernels run; NotImplementedError with the reason otherwise."""
+        from .i8_linear_ops import act_mode
+        w = quant_config['weight']
+        if w.get('granularity') != 'per_channel' or not w.get('symmetric', False):
+            raise NotImplementedError("quik_quant runs symmetric per_channel weights (one scale per output channel leaves the K loop; "
+                                      f"a zero point or per_group scales do not), got granularity {w.get('granularity')!r}, "
+                                      f"symmetric {w.get('symmetric', False)!r}")
+        if not isinstance(w.get('bit'), int) or w['bit'] > 8:
+            raise NotImplementedError(f"quik_quant stores one integer code per byte: weight bit <= 8, got {w.get('bit')!r}")
+        if 'act' not in quant_config:
+            raise NotImplementedError('quik_quant needs an `act` section (8-bit symmetric per_token): the int8 product is the point '
+                                      'of the form, weight-only is not provided')
+        mode = act_mode(dict(quant_config['act']))
+        if mode != 'dynamic_per_token':
+            raise NotImplementedError('quik_quant takes dynamic per_token activation scales (the split kernel reduces them per row), '
+                                      'got static per_tensor')
+        return mode
+
+    def aquantizer(self):
+        if getattr(self, '_aquantizer', None) is None:
+            from .i8_linear_ops import _quantizer
+            self._aquantizer = _quantizer(self.act_cfg)
+        return self._aquantizer
+
+    @torch.no_grad()
+    def forward(self, x):
+        from .quik_ops import quik_linear_forward
+        if isinstance(self.act_mode, NotImplementedError):
+            raise NotImplementedError(f'{type(self).__name__}.forward: {self.act_mode}')
+        return quik_linear_forward(x, self)
+
+    @classmethod
+    @torch.no_grad()
+    def new(cls, module, w_q, quant_config):
+        from .quik_ops import padded
+        int_ids, fp_ids = module.buf_int_ids, module.buf_fp_ids
+        K, n_int, F = module.in_features, int_ids.numel(), fp_ids.numel()
+        Ki, Fp = padded(n_int, F)
+        codes, scales, _ = w_q(module)                       # of the gathered int columns (QUIK.w_q)
+        dev = codes.device
+        weight = torch.zeros(module.out_features, Ki, dtype=torch.int8, device=dev)
+        weight[:, :n_int] = codes.reshape(module.out_features, n_int)
+        weight_fp = torch.zeros(module.out_features, Fp, dtype=module.weight.dtype, device=dev)
+        weight_fp[:, :F] = module.weight.data.index_select(1, fp_ids.to(module.weight.device)).to(dev)
+        col_map = torch.empty(K, dtype=torch.int32, device=dev)
+        col_map[int_ids.to(dev)] = torch.arange(n_int, dtype=torch.int32, device=dev)
+        col_map[fp_ids.to(dev)] = Ki + torch.arange(F, dtype=torch.int32, device=dev)
+        bias = module.bias.data if module.bias is not None else None
+        m = cls(weight, bias, scales.reshape(-1, 1).float(), weight_fp, int_ids.to(dev, torch.int32), fp_ids.to(dev, torch.int32), col_map)
+        m.in_features, m.out_features = module.in_features, module.out_features
+        m.weight_shape, m.weight_dtype = weight.shape, weight.dtype
+        m.scales_shape, m.scales_dtype = m.weight_scale.shape, m.weight_scale.dtype
+        m.zeros_shape = m.zeros_dtype = None
+        m.act_cfg = dict(quant_config['act']) if 'act' in quant_config else None
+        try:
+            m.act_mode = cls.check_config(quant_config)
+        except NotImplementedError as e:
+            m.act_mode = e
+        return m
+
+    def __repr__(self):
+        return (f'QuikRealQuantLinear(in_features={self.in_features}, out_features={self.out_features}, '
+                f'bias={self.bias is not None}, weight_shape={self.weight_shape}, weight_fp_shape={tuple(self.weight_fp.shape)}, '
+                f'scales_shape={self.scales_shape})')
+
+
 _TRANSFORMERS_LINEAR_TYPES_ = [nn.Linear]
 _TRANSFORMERS_LN_TYPES_ = [nn.LayerNorm]
 try:  # RMSNorm-style layers of HF models count as LN types for apply_scale
@@ -664,7 +759,7 @@ if hasattr(nn, 'RMSNorm') and nn.RMSNorm not in _TRANSFORMERS_LN_TYPES_:
 _LLMC_LN_TYPES_ = [LlmcRMSNorm]
 _LLMC_LINEAR_TYPES_ = [LlmcFp8Linear, RotateLinear, OriginFloatLinear, FakeQuantLinear, EffcientFakeQuantLinear, VllmRealQuantLinear,
                        SglRealQuantLinear, AutoawqRealQuantLinear, MlcllmRealQuantLinear, LightllmRealQuantLinear, MxFp4RealQuantLinear,
-                       MxFp6RealQuantLinear]
+                       MxFp6RealQuantLinear, QuikRealQuantLinear]
 _REALQUANT_LINEAR_MAP_ = {
     'vllm_quant': VllmRealQuantLinear,
     'lightllm_quant': LightllmRealQuantLinear,
@@ -674,4 +769,5 @@ _REALQUANT_LINEAR_MAP_ = {
     'lightx2v_quant': Lightx2vRealQuantLinear,
     'mxfp4_quant': MxFp4RealQuantLinear,
     'mxfp6_quant': MxFp6RealQuantLinear,
+    'quik_quant': QuikRealQuantLinear,
 }

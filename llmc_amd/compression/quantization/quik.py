@@ -136,5 +136,22 @@ class QUIK(BaseBlockwiseQuantization):
         return wquantizer.fake_quant_weight_dynamic(module.weight, self._mixed_args(module))
 
     @torch.no_grad()
+    def w_q(self, module, wquantizer):
+        """Under deploy('quik_quant'): codes and scales of the int columns alone, in the order of buf_int_ids — the range
+        fake_quant_weight_dynamic takes with int_indices (QuikRealQuantLinear.new reads the index buffers and the outlier columns
+        from the module itself). Every other real-quant format has no place for outlier columns and gets the whole weight, as
+        before."""
+        if not self._quik_format:
+            return super().w_q(module, wquantizer)
+        return wquantizer.real_quant_weight_dynamic(module.weight.data.index_select(1, module.buf_int_ids))
+
+    _quik_format = False
+
+    @torch.no_grad()
+    def deploy(self, quant_format, keep_device=False):
+        self._quik_format = quant_format == 'quik_quant'
+        super().deploy(quant_format, keep_device=keep_device)
+
+    @torch.no_grad()
     def a_qdq(self, act, module, aquantizer, input_index=0):
         return aquantizer.fake_quant_act_dynamic(act, self._mixed_args(module))
